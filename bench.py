@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — the LDPC BP hot path on MI355X, one BASELINE.json configuration per run.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1,2,2n,2f,3,4,4n,5,5bec}]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1,2,2n,2f,3,4,4n,5,5bec}] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of synthetic frames of the reference's noise stream
 mt19937_64(seed 0): noise generation, acceptance scan, fused channel + LLR init + flooding BP decode with syndrome
@@ -18,7 +18,12 @@ are summed on each rank's device and reduced ONCE after the last step.  At every
 min / max over ranks: decode-kernel and noise-stream milliseconds, host time inside the exchange and waiting for the noise
 stream, frames per step, communicator set-up seconds (outside the timed region), and the min / median / max step time.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0 (contract in the task statement).
+--dump-outputs DIR then writes what the last timed step handed its caller as DIR/<name>.npy (float32 / float64): per-frame
+`iters` and `bit_errors` and the step's five `counters` (config 1: the frame's `llr_out` and `iters`); the inputs depend on
+the arguments only (stream seed 0), so two builds can be compared output for output.
+
+--full adds the side measurements, each in child processes before this process touches the GPU:
   roofline      of the dominant kernel, from SQ / TCC counters collected by rocprofv3 in separate passes of the same
                 workload inside this run (tools/pmc_probe.py).  Sum-product configurations: WORK-NORMALISED — binary64
                 operations retired per second against the 78.6 TFLOP/s vector peak (bound "valu-fp64"), with the
@@ -27,6 +32,9 @@ Prints ONE JSON line on rank 0 (contract in the task statement), with
                 algorithmic_equiv_GBs and is not a physical bandwidth
   cpu_baseline  the reference CLI (oracle/_ref/ldpcsim_ref) on this box's host cores, bounded sample, with the
                 one-thread rate beside it
+  other_configs (default configuration only) short runs of the other BASELINE.json configurations
+Without --full, `roofline` keeps the figures computed from the timed run (kernel_ms_avg, algorithmic bytes) and its
+counter-derived fields are null.
 """
 import argparse
 import csv
@@ -248,7 +256,7 @@ def other_configs(budget_s=75.0):
         if time.time() - t0 > budget_s:
             out[key] = {"error": "skipped: time budget of the default run spent"}
             continue
-        cmd = [sys.executable, os.path.abspath(__file__), "--config", key, "--no-cpu-baseline", "--no-other-configs", *extra]
+        cmd = [sys.executable, os.path.abspath(__file__), "--config", key, "--full", "--no-cpu-baseline", "--no-other-configs", *extra]
         cmd.append("--pmc-passes=sq,mix" if with_mix else "--no-pmc")
         try:
             p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
@@ -302,7 +310,9 @@ def run_latency(args, w):
     its = np.array(its)
     assert (its == llr["iters"][W:]).all(), "C-ABI decode() and the batch path disagree on iteration counts"
     executed = int((its + (its < w["iterations"])).sum())
-    return {"frames": K, "dt": dt, "edge_updates": executed * dec.nnz, "kernel_ms": None,
+    # what the last timed decode() call handed its caller: the return value and llrOut
+    outputs = {"iters": its[-1:].astype(np.float64), "llr_out": np.ctypeslib.as_array(vout).astype(np.float64)}
+    return {"frames": K, "dt": dt, "edge_updates": executed * dec.nnz, "kernel_ms": None, "outputs": outputs,
             "extra": {"latency_us": {"median": float(np.median(lat) * 1e6), "p99": float(np.percentile(lat, 99) * 1e6),
                                      "min": float(lat.min() * 1e6), "mean": float(lat.mean() * 1e6)},
                       "avg_iter": float(its.mean()), "call": "ldpc_setup + decode(decoder_param, llr[nct], llrOut[nct]) of include/ldpc_amd.h"}}
@@ -416,6 +426,10 @@ def run_rank(args, w):
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    outputs = None
+    if args.dump_outputs:  # what the last timed step handed its caller: the rank's per-frame results and the step's counters
+        outputs = {"iters": iters_d[:own[-1]].float().cpu().numpy(), "bit_errors": be_d[:own[-1]].float().cpu().numpy(),
+                   "counters": c.double().cpu().numpy()}
     # HIP events around every decode launch (on the launch stream) and every noise-stream refill (on the engine's
     # internal stream), queued during the loop and read back here: mean over the K timed steps
     kernel_ms, rng_ms = dec.last_ms(0), dec.last_ms(1)
@@ -457,7 +471,7 @@ def run_rank(args, w):
              "transport": per_rank[0]["transport"],
              "per_rank": per_rank}
     return ({"frames": frames, "dt": dt, "edge_updates": edge_updates, "kernel_ms": max(r["kernel_ms_avg"] for r in per_rank),
-             "extra": {"fer": fec / frames, "ber": bec / (frames * d["nc"]), "avg_iter": it_sum / frames, "rng_ms_avg": rng_ms,
+             "outputs": outputs, "extra": {"fer": fec / frames, "ber": bec / (frames * d["nc"]), "avg_iter": it_sum / frames, "rng_ms_avg": rng_ms,
                        "step_ms": ranks["step_ms"], "ranks": ranks,
                        "counters": {"frames": frames, "fec": fec, "bec": bec, "iters": it_sum, "converged": conv},
                        "timed_frame_span": span, "residency": dec.residency,
@@ -485,6 +499,11 @@ def main():
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 counter passes (roofline fields become null)")
     ap.add_argument("--pmc-passes", default="sq,mix,fetch,write", help="which counter passes to run (comma-separated)")
     ap.add_argument("--no-other-configs", action="store_true", help="default run only: skip the short runs of the other BASELINE configurations")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (N = 1): rocprofv3 counter passes for the roofline, the CPU baseline and, "
+                         "for the default configuration, the other BASELINE configurations; the --no-* options above apply to them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
     w = workloads.get(args.config)
     if args.steps is None:
@@ -502,9 +521,11 @@ def main():
 
     # ---- legs that need child processes: before this process (or its rank children) touches a GPU ----
     # (N = 1 only: the counters describe one GPU's kernel, the CPU baseline is a per-box figure; at N > 1 the other ranks
-    # would sit in the rendezvous while rank 0 profiles)
+    # would sit in the rendezvous while rank 0 profiles).  A plain run has none of them: --full runs them.
     legs = {}
-    if leader and args.gpus == 1:
+    if leader and args.gpus == 1 and not args.full:
+        legs["pmc"] = {"error": "counter passes not run (bench.py --full runs them)"}
+    if leader and args.gpus == 1 and args.full:
         if not args.no_pmc and args.config != "1":
             legs["pmc"] = pmc_passes(args.config, args.batch or w["batch"], passes=tuple(args.pmc_passes.split(",")))
         if not args.no_cpu_baseline:
@@ -517,6 +538,8 @@ def main():
         port = free_port()
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup",
                str(args.warmup), "--config", args.config, "--batch", str(args.batch), "--no-cpu-baseline", "--no-pmc"]
+        if args.dump_outputs:
+            cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]  # (rank 0 writes its own frames' outputs)
         procs = []
         for r in range(args.gpus):
             env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(args.gpus), MASTER_ADDR="127.0.0.1",
@@ -558,9 +581,28 @@ def main():
         }
         if not os.environ.get("LDPC_BENCH_CHILD"):
             finish(res, legs, w)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, m["outputs"])
         print(json.dumps(res))
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_MAX_FRAMES = 1 << 21  # per-frame arrays beyond this are sampled: 2 x float32 + the float64 index = 32 MB at most
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: one DIR/<name>.npy per output of the last timed step.  Per-frame arrays longer than DUMP_MAX_FRAMES are
+    cut to a fixed sample of frames (seed 0, in frame order) and `frame_index.npy` lists the frames kept."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(outputs["iters"])
+    if "bit_errors" in outputs and n > DUMP_MAX_FRAMES:
+        keep = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_FRAMES, replace=False))
+        outputs = dict(outputs, iters=outputs["iters"][keep], bit_errors=outputs["bit_errors"][keep], frame_index=keep.astype(np.float64))
+    for name, a in outputs.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def finish(res, legs, w):

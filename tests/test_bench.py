@@ -69,9 +69,55 @@ def test_roofline_arithmetic_is_a_fraction():
     assert r0["frac"] is None and r0["traffic"] is None
 
 
+def test_dump_outputs_writes_float_arrays(tmp_path, monkeypatch):
+    """--dump-outputs and --full exist; dump_outputs writes float32 / float64 .npy files and cuts long per-frame arrays to
+    the same fixed sample of frames every time."""
+    p = run_bench("--help")
+    assert "--dump-outputs" in p.stdout and "--full" in p.stdout
+    sys.path.insert(0, ROOT)
+    import bench
+    it = np.arange(10, dtype=np.float32) % 7
+    out = {"iters": it, "bit_errors": it * 3, "counters": np.array([10.0, 8.0, 135.0, 42.0, 1.0])}
+    bench.dump_outputs(str(tmp_path / "all"), out)
+    assert sorted(os.listdir(tmp_path / "all")) == ["bit_errors.npy", "counters.npy", "iters.npy"]
+    for k, v in out.items():
+        got = np.load(tmp_path / "all" / f"{k}.npy")
+        assert got.dtype == v.dtype and np.array_equal(got, v)
+    monkeypatch.setattr(bench, "DUMP_MAX_FRAMES", 4)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), out)
+    idx = np.load(tmp_path / "s1" / "frame_index.npy")
+    assert idx.dtype == np.float64 and len(idx) == 4 and (np.diff(idx) > 0).all()
+    assert np.array_equal(idx, np.load(tmp_path / "s2" / "frame_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "s1" / "bit_errors.npy"), out["bit_errors"][idx.astype(int)])
+    assert np.array_equal(np.load(tmp_path / "s1" / "counters.npy"), out["counters"])
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """A plain run (no side measurements) times exactly --steps steps, and --dump-outputs holds the per-frame results and
+    the counters of the last timed step: those of a single-process decode of that step's frames."""
+    import libldpc_amd
+    B, K, W = 4096, 3, 2
+    j = last_json(run_bench("--steps", str(K), "--warmup", str(W), "--batch", str(B), "--dump-outputs", str(tmp_path)))
+    assert j["steps"] == K and j["ms_per_step"] > 0 and "cpu_baseline" not in j and "other_configs" not in j
+    assert j["roofline"]["frac"] is None and j["roofline"]["kernel_ms_avg"] > 0
+    first, end = j["timed_frame_span"]
+    assert end - first == K * B == j["counters"]["frames"]
+    got = {k: np.load(tmp_path / f"{k}.npy") for k in ("iters", "bit_errors", "counters")}
+    assert got["iters"].dtype == got["bit_errors"].dtype == np.float32 and got["counters"].dtype == np.float64
+    dec = libldpc_amd.HipDecoder(os.path.join(ROOT, "tests", "golden", "h.txt"))
+    dec.stream_begin("AWGN", 0, -4.0)
+    dec.stream_skip(end - B)
+    r = dec.stream_decode(B)
+    it, be = r["iters"].astype(np.int64), r["bit_errors"].astype(np.int64)
+    assert np.array_equal(got["iters"], it) and np.array_equal(got["bit_errors"], be)
+    assert got["counters"].tolist() == [B, int((be > 0).sum()), int(be.sum()), int(it.sum()), int((it < 50).sum())]
+
+
 @pytest.mark.gpu
 def test_bench_line_headline():
-    j = last_json(run_bench("--steps", "3", "--warmup", "2", "--no-cpu-baseline"))
+    j = last_json(run_bench("--full", "--steps", "3", "--warmup", "2", "--no-cpu-baseline"))
     assert j["n_gpus"] == 1 and j["unit"] == "frames/s" and j["config"]["baseline_config"] == "2"
     assert j["config"]["frames_per_step"] == 65536 and j["dtype"] == "f64" and j["vs_baseline"] is None
     r = j["roofline"]
@@ -89,7 +135,7 @@ def test_bench_line_headline():
 @pytest.mark.parametrize("cfg", ["1", "3", "4", "5", "5bec"])
 def test_bench_line_other_configs(cfg):
     extra = ["--steps", "200", "--warmup", "20"] if cfg == "1" else ["--steps", "2", "--warmup", "1"]
-    j = last_json(run_bench("--config", cfg, "--no-cpu-baseline", *extra))
+    j = last_json(run_bench("--full", "--config", cfg, "--no-cpu-baseline", *extra))
     assert j["config"]["baseline_config"] == cfg and j["value"] > 0
     if cfg == "1":
         assert j["latency_us"]["median"] < 2000 and j["config"]["frames_per_step"] == 1

@@ -73,7 +73,7 @@ def test_sharded_state_table_costs_the_same_for_every_world_size(lib):
                 assert tasks == (m + 1) * 39 and launches.value == 39, (m, world, rank, tasks, launches.value)
 
 
-def test_struct_layouts_match_reference_abi():
+def test_struct_layouts_match_reference_abi(tmp_path):
     """x86-64 SysV sizes/offsets of the by-value structs (functions.h:107-127)."""
     from libldpc_amd.binding import channel_param, decoder_param, sim_results_t, simulation_param
     assert ct.sizeof(decoder_param) == 16 and decoder_param.iterations.offset == 4 and decoder_param.type.offset == 8
@@ -87,7 +87,7 @@ def test_struct_layouts_match_reference_abi():
     int main(void){ printf("%zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(decoder_param), offsetof(decoder_param, iterations),
       offsetof(decoder_param, type), sizeof(channel_param), offsetof(channel_param, type), sizeof(simulation_param),
       offsetof(simulation_param, resultFile), sizeof(sim_results_t)); return 0; }'''
-    exe = "/tmp/ldpc_abi_probe"
+    exe = str(tmp_path / "ldpc_abi_probe")
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=src, text=True, check=True)
     assert subprocess.check_output([exe], text=True).split() == ["16", "4", "8", "40", "32", "32", "24", "48"]
 

@@ -14,7 +14,7 @@ export TMPDIR=/tmp
 if [ "$part" = a ] || [ "$part" = all ]; then
     : > "$out/configs.jsonl"
     for c in 2 1 3 4 5 5bec 2n 4n 2f 2l 2h; do
-        timeout -k 10 300 python3 bench.py --config $c --steps 40 --warmup 10 2> "$out/bench_cfg$c.err" | tail -1 >> "$out/configs.jsonl" || echo "bench config $c failed"
+        timeout -k 10 300 python3 bench.py --full --config $c --steps 40 --warmup 10 2> "$out/bench_cfg$c.err" | tail -1 >> "$out/configs.jsonl" || echo "bench config $c failed"
         echo "config $c done"
     done
 fi

@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 B="python3 bench.py --steps 5 --warmup 5 --no-cpu-baseline"
 SQ="SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE"
 if [ "$what" = all ]; then
-    timeout -k 10 600 python3 bench.py --steps 20 --warmup 10 > "$out/bench_full.json" 2> "$out/bench_full.err"
+    timeout -k 10 600 python3 bench.py --full --steps 20 --warmup 10 > "$out/bench_full.json" 2> "$out/bench_full.err"
     timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$out/stats" -o run --output-format csv -- \
         python3 bench.py --steps 10 --warmup 10 --no-cpu-baseline > "$out/bench_stats.log" 2>&1
     timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d "$out/fetch" -o run --output-format csv -- $B > "$out/fetch.log" 2>&1
