@@ -20,21 +20,6 @@ std::string hip_error_string(int err) { return hipGetErrorString(static_cast<hip
 
 namespace
 {
-// LDPC_AMD_TRACE=1: host wall-clock of the phases of a batch, on stderr
-struct PhaseTrace
-{
-    bool on = std::getenv("LDPC_AMD_TRACE") != nullptr;
-    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    void mark(const char *what)
-    {
-        if (!on)
-            return;
-        auto t1 = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "[ldpc_amd] %-18s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
-        t0 = t1;
-    }
-};
-
 void check(hipError_t e, const char *what)
 {
     if (e != hipSuccess)
@@ -55,6 +40,8 @@ bool is_device_ptr(const void *p)
     }
     return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
 }
+
+} // namespace
 
 // routes an output either straight to the caller's device pointer or through a staging buffer
 struct OutStage
@@ -127,8 +114,6 @@ struct OutStage
     }
     static constexpr size_t kPinnedLimit = 1 << 20;
 };
-
-} // namespace
 
 // ---------------------------------------------------------------------------------------------
 PinnedBuffer::~PinnedBuffer()
@@ -282,7 +267,7 @@ void MtDevice::apply(const std::vector<StateOp> &ops, uint64_t *table, void *str
                   "state copy");
             break;
         case StateOp::kJump:
-            check(launch_mt_jump(table, op.mod, op.src, op.dst, device_poly(op.stride, stream), op.n, jump_pack_, jump_groups_, s), "mt_jump");
+            check(launch_mt_jump(table, op.mod, op.src, op.dst, device_poly(op.stride, stream), op.n, jump_groups_, s), "mt_jump");
             jump_tasks_ += op.n;
             break;
         }
@@ -336,7 +321,7 @@ void MtDevice::drain_ahead(void *stream, uint64_t below)
 
 void MtDevice::prefetch_ring(uint64_t c_hi)
 {
-    if (!ring_.valid() || !ring_polys_ready_ || std::getenv("LDPC_AMD_NO_LOOKAHEAD"))
+    if (!ring_.valid() || !ring_polys_ready_)
         return;
     const uint64_t hi_before = ring_.hi();
     std::vector<StateOp> ops;
@@ -398,7 +383,7 @@ uint64_t *MtDevice::ensure_strided(uint64_t first, uint32_t n, uint64_t stride, 
 
 void MtDevice::prefetch_strided()
 {
-    if (std::getenv("LDPC_AMD_NO_LOOKAHEAD") || !strided_buf_.get())
+    if (!strided_buf_.get())
         return;
     std::vector<StateOp> ops;
     strided_.look_ahead(ops);
@@ -469,35 +454,51 @@ Engine::Engine(const std::string &pc_file, const std::string &gen_file, int devi
     if (code_->min_cn_degree() < 2)
         throw std::runtime_error("check nodes of degree < 2 are not supported (undefined in the reference decoder)");
     plan_ = build_plan(*code_);
-    if (plan_.lds_ok && !std::getenv("LDPC_AMD_NO_FUSED")) // (the variable: experiments only — results change by ulps)
-        fused_plan_ = build_fused_plan(*code_, plan_);
-    if (!plan_.lds_ok)
-        for (int r = 0; r < code_->H.rows && !shared6_; ++r)
-            shared6_ = code_->H.rptr[r + 1] - code_->H.rptr[r] == 6;
-    if (!plan_.lds_ok) // register-resident decoder: the smallest register tile the code fits
+    const size_t nc = plan_.nc, nnz = plan_.nnz;
+    if (plan_.lds_ok)
     {
-        // One frame per CU (1024 threads, 128 VGPRs, 160 KB mailbox) first: measured 1.37x faster on the n=8192
-        // code than two frames per CU (512 threads, 256 VGPRs, 80 KB mailboxes, one more exchange round), which
-        // remains available for tiles that do not fit 128 registers (LDPC_AMD_REG_NT512=1 forces it).
-        struct Tile { int nt, kc, maxd; };
-        const bool two_per_cu = std::getenv("LDPC_AMD_REG_NT512") != nullptr;
-        for (Tile t : {Tile{1024, 4, 6}, Tile{1024, 8, 4}, Tile{1024, 2, 8}, Tile{512, 8, 6}, Tile{512, 16, 4}, Tile{512, 4, 8}})
-        {
-            if (two_per_cu && t.nt != 512)
-                continue;
-            reg_plan_ = build_reg_plan(*code_, plan_, t.nt, t.kc, t.maxd, t.nt == 512 ? 80 * 1024 : 160 * 1024);
-            if (reg_plan_.ok)
-                break;
-        }
+        residency_ = Residency::kLds;
+        fused_plan_ = build_fused_plan(*code_, plan_);
+        // Input LLRs: in registers when that frees the LDS for one more resident frame per CU (n=1024 code: 40 KB -> 31 KB,
+        // five frames instead of four) and the plan allows it; in LDS otherwise.  (Device memory also reached five frames
+        // but paid for it in memory reads: measured, no net gain.)
+        const size_t cu_lds = 160 * 1024, with_llr = plan_.lds_bytes, without = plan_.lds_bytes - 8 * nc;
+        if (cu_lds / without > cu_lds / with_llr && plan_.vn_work_stride <= 8 && !plan_.has_isolated_vn && plan_.nc <= plan_.nnz &&
+            !plan_.vn_packed.empty())
+            lds_llr_mode_ = 2;
+        return;
+    }
+    for (int r = 0; r < code_->H.rows && !shared6_; ++r)
+        shared6_ = code_->H.rptr[r + 1] - code_->H.rptr[r] == 6;
+    // register-resident decoder: the smallest register tile the code fits.  One frame per CU (1024 threads, 128 VGPRs,
+    // 160 KB mailbox) first: measured 1.37x faster on the n=8192 code than two frames per CU (512 threads, 256 VGPRs, 80 KB
+    // mailboxes, one more exchange round), which remains for tiles that do not fit 128 registers.
+    struct Tile { int nt, kc, maxd; };
+    for (Tile t : {Tile{1024, 4, 6}, Tile{1024, 8, 4}, Tile{1024, 2, 8}, Tile{512, 8, 6}, Tile{512, 16, 4}, Tile{512, 4, 8}})
+    {
+        reg_plan_ = build_reg_plan(*code_, plan_, t.nt, t.kc, t.maxd, t.nt == 512 ? 80 * 1024 : 160 * 1024);
+        if (reg_plan_.ok)
+            break;
+    }
+    if (reg_plan_.ok)
+    {
         // second form (totals come back instead of messages): preferred when the code fits its one instantiation
-        if (reg_plan_.ok && !std::getenv("LDPC_AMD_NO_REG2"))
-            reg2_plan_ = build_reg2_plan(*code_, plan_, 1024, 4, 6, 4, 4);
+        reg2_plan_ = build_reg2_plan(*code_, plan_, 1024, 4, 6, 4, 4);
+        residency_ = reg2_plan_.ok ? Residency::kRegTotals : Residency::kRegMessages;
         // a register-resident decode workgroup owns its CU: keep the noise generator of the next batch, which runs
         // beside it, on a quarter of the CUs (config 4: 4.89 -> 4.62 ms per step)
         // ... and in chunks of 2240 blocks: half as many jump-ahead tasks per batch as the LDS-resident decoders' 1120 — here
         // every task holds a CU that a frame could have, and the generator's longer chain still ends before the 4.6 ms launch
-        if (reg_plan_.ok)
-            noise_.set_pack(4), noise_.st.set_jump_pack(3), noise_.st.set_default_chunk_blocks(2240);
+        noise_.set_pack(4), noise_.st.set_default_chunk_blocks(2240);
+    }
+    else if (plan_.hbm_ok)
+    {
+        residency_ = Residency::kMemory;
+        // resident frames per CU are bounded through a dummy LDS request so that the frames in flight
+        // (256 CUs x frames/CU x state bytes) stay inside the 256 MiB Infinity Cache
+        const uint64_t per_frame = 8ull * nnz + 8ull * nc + nnz;
+        const uint64_t frames_per_cu = std::clamp<uint64_t>((224ull << 20) / (256 * per_frame), 1, 8);
+        mem_occ_lds_ = frames_per_cu >= 8 ? 0 : static_cast<uint32_t>((160 * 1024) / (frames_per_cu + 1) + 1024) & ~15u;
     }
 }
 
@@ -716,10 +717,66 @@ uint64_t Engine::max_sub_batch() const
     const uint64_t kMaxSlabs = std::max<uint64_t>(4, 476ull * 2240 / noise_.st.chunk_blocks());
     const uint64_t pairs_per_frame = std::max<uint64_t>(1, (static_cast<uint64_t>(plan_.nct) + 1) / 2 + 1);
     const uint64_t by_noise = std::max<uint64_t>(1, (kMaxSlabs - 2) * noise_.st.chunk_trials() * 3 / 4 / pairs_per_frame);
-    if (plan_.lds_ok || reg_plan_.ok)
+    if (residency_ == Residency::kLds || register_resident())
         return std::min<uint64_t>(1u << 17, by_noise);
     const uint64_t per_frame = 8ull * plan_.nnz + 8ull * plan_.nc + plan_.nnz;
     return std::max<uint64_t>(1, std::min<uint64_t>({1u << 17, (8ull << 30) / per_frame, by_noise}));
+}
+
+// The layered schedule of non-parity modes 2 / 3 (kernels_layered.hip): built and uploaded at the first launch that needs it
+void Engine::ensure_layer_plan()
+{
+    if (layer_plan_.ok || !layer_plan_.steps.empty())
+        return;
+    layer_plan_ = build_layer_plan(*code_, plan_);
+    if (!layer_plan_.ok)
+        return;
+    const size_t nc = plan_.nc;
+    std::vector<uint32_t> steps;
+    for (const LayerStep &l : layer_plan_.steps)
+        steps.push_back(l.off), steps.push_back(static_cast<uint32_t>(l.count) | static_cast<uint32_t>(l.degree) << 16);
+    // the steps' neighbour tables as the kernel fetches them: four words per lane, two VN ranks per word
+    std::vector<uint32_t> vn4(layer_plan_.steps.size() * 4 * kWaveSize, 0);
+    for (size_t si = 0; si < layer_plan_.steps.size(); ++si)
+        for (int j = 0; j < layer_plan_.steps[si].degree; ++j)
+            for (int l = 0; l < kWaveSize; ++l)
+                vn4[(si * 4 + j / 2) * kWaveSize + l] |=
+                    static_cast<uint32_t>(layer_plan_.vn[layer_plan_.steps[si].off + static_cast<size_t>(j) * kWaveSize + l]) << (16 * (j & 1));
+    void *d_steps = nullptr, *d_vn = nullptr;
+    check(hipMalloc(&d_steps, steps.size() * 4), "hipMalloc layer plan");
+    owned_.push_back(d_steps);
+    check(hipMalloc(&d_vn, vn4.size() * 4), "hipMalloc layer plan");
+    owned_.push_back(d_vn);
+    check(hipMemcpy(d_steps, steps.data(), steps.size() * 4, hipMemcpyHostToDevice), "upload layer plan");
+    check(hipMemcpy(d_vn, vn4.data(), vn4.size() * 4, hipMemcpyHostToDevice), "upload layer plan");
+    dev_layer_.steps = static_cast<const uint32_t *>(d_steps);
+    dev_layer_.vn4 = static_cast<const uint32_t *>(d_vn);
+    dev_layer_.n_steps = static_cast<uint32_t>(layer_plan_.steps.size());
+    dev_layer_.slots = layer_plan_.slots;
+    const size_t tot_bytes = 4 * ((nc + 3) & ~size_t(3));
+    dev_layer_.region_bytes = static_cast<uint32_t>((std::max(8 * nc, tot_bytes + 4 * size_t(layer_plan_.slots)) + 15) & ~size_t(15));
+    dev_layer_.region_bytes_half = static_cast<uint32_t>((std::max(8 * nc, tot_bytes + 2 * size_t(layer_plan_.slots)) + 15) & ~size_t(15));
+}
+
+void Engine::finish_batch(OutStage &st, const BatchOut &out, uint64_t n, const uint8_t *codeword, int noise_buffer, void *stream)
+{
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t nc = plan_.nc;
+    prof_mark(0, s);
+    if (noise_buffer >= 0)
+        noise_raw_release(noise_buffer, stream);
+    if (out.codeword)
+    {
+        if (codeword)
+            check(hipMemcpyAsync(out.codeword, codeword, n * nc,
+                                 is_device_ptr(out.codeword) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s),
+                  "codeword out");
+        else if (is_device_ptr(out.codeword))
+            check(hipMemsetAsync(out.codeword, 0, n * nc, s), "codeword out");
+        else
+            std::memset(out.codeword, 0, n * nc);
+    }
+    st.flush(s, &pin_out_);
 }
 
 void Engine::run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, uint64_t n, void *stream)
@@ -737,114 +794,53 @@ void Engine::run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, 
     a.llr_out = st.route(out.llr_out, stage_llr_out_, 8 * n * nc);
     a.llr_in_dump = st.route(out.llr_in, stage_llr_in_, 8 * n * nc);
     prof_mark(0, s);
-    if (fast_mode && !p.min_sum)
-    {
-        // the caller asked for a non-parity mode; never chosen by itself
-        if (fast_mode == 1)
+    // the caller asked for a non-parity mode (never chosen by itself): one launch, no ratio form
+    const bool fast = fast_mode && !p.min_sum;
+    bool fused_handover_used = false;
+    bool finished_in_one = false; // the launch was the totals-form register kernel's chain of all three forms (kernels_reg2_impl.hpp)
+    const auto launch = [&] {
+        if (fast && fast_mode == 1)
         {
             if (!fast_mode_supported(dev_, plan_.max_cn_degree) || plan_.has_isolated_vn)
                 throw std::runtime_error("fast mode: this code is outside what the binary32 kernel takes (check nodes up to degree 8, "
                                          "nc <= 8192, LDS-resident, no isolated variable node)");
             a.ws_hb = static_cast<uint8_t *>(ws_hb_.reserve(n * nc));
             check(launch_decode_fast(a, plan_.max_cn_degree, s), "decode (fast mode, binary32)");
+            return;
         }
-        else
+        if (fast)
         {
-            if (!layer_plan_.ok && layer_plan_.steps.empty())
-            {
-                layer_plan_ = build_layer_plan(*code_, plan_);
-                if (layer_plan_.ok)
-                {
-                    std::vector<uint32_t> st;
-                    for (const LayerStep &l : layer_plan_.steps)
-                        st.push_back(l.off), st.push_back(static_cast<uint32_t>(l.count) | static_cast<uint32_t>(l.degree) << 16);
-                    // the steps' neighbour tables as the kernel fetches them: four words per lane, two VN ranks per word
-                    std::vector<uint32_t> vn4(layer_plan_.steps.size() * 4 * kWaveSize, 0);
-                    for (size_t si = 0; si < layer_plan_.steps.size(); ++si)
-                        for (int j = 0; j < layer_plan_.steps[si].degree; ++j)
-                            for (int l = 0; l < kWaveSize; ++l)
-                                vn4[(si * 4 + j / 2) * kWaveSize + l] |=
-                                    static_cast<uint32_t>(layer_plan_.vn[layer_plan_.steps[si].off + static_cast<size_t>(j) * kWaveSize + l]) << (16 * (j & 1));
-                    void *d_steps = nullptr, *d_vn = nullptr;
-                    check(hipMalloc(&d_steps, st.size() * 4), "hipMalloc layer plan");
-                    owned_.push_back(d_steps);
-                    check(hipMalloc(&d_vn, vn4.size() * 4), "hipMalloc layer plan");
-                    owned_.push_back(d_vn);
-                    check(hipMemcpy(d_steps, st.data(), st.size() * 4, hipMemcpyHostToDevice), "upload layer plan");
-                    check(hipMemcpy(d_vn, vn4.data(), vn4.size() * 4, hipMemcpyHostToDevice), "upload layer plan");
-                    dev_layer_.steps = static_cast<const uint32_t *>(d_steps);
-                    dev_layer_.vn4 = static_cast<const uint32_t *>(d_vn);
-                    dev_layer_.n_steps = static_cast<uint32_t>(layer_plan_.steps.size());
-                    dev_layer_.slots = layer_plan_.slots;
-                    const size_t tot_bytes = 4 * ((nc + 3) & ~size_t(3));
-                    dev_layer_.region_bytes = static_cast<uint32_t>((std::max(8 * nc, tot_bytes + 4 * size_t(layer_plan_.slots)) + 15) & ~size_t(15));
-                    dev_layer_.region_bytes_half = static_cast<uint32_t>((std::max(8 * nc, tot_bytes + 2 * size_t(layer_plan_.slots)) + 15) & ~size_t(15));
-                }
-            }
+            ensure_layer_plan();
             const bool half = fast_mode == 3;
             if (!layer_plan_.ok || plan_.has_isolated_vn || (half ? dev_layer_.region_bytes_half : dev_layer_.region_bytes) > 160 * 1024)
                 throw std::runtime_error("layered mode: this code is outside what the layered kernel takes (check nodes of degree 2..8, at "
                                          "most 65535 columns, totals and messages of one frame within 160 KB of LDS, no isolated variable node)");
             check(launch_decode_layered(a, dev_layer_, half, s), half ? "decode (layered, binary16 messages)" : "decode (layered, binary32 messages)");
+            return;
         }
-        prof_mark(0, s);
-        if (a.mode == kModeAwgn && a.pairs_buffer >= 0 && ev_pairs_free_[a.pairs_buffer])
+        switch (residency_)
         {
-            check(hipEventRecord(static_cast<hipEvent_t>(ev_pairs_free_[a.pairs_buffer]), s), "event");
-            pairs_in_use_[a.pairs_buffer] = true;
-        }
-        if (out.codeword)
-        {
-            if (a.codeword)
-                check(hipMemcpyAsync(out.codeword, a.codeword, n * nc,
-                                     is_device_ptr(out.codeword) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s), "codeword out");
-            else if (is_device_ptr(out.codeword))
-                check(hipMemsetAsync(out.codeword, 0, n * nc, s), "codeword out");
+        case Residency::kLds:
+            // the first launch of sum-product with early termination, for codes the fused form takes (fused_rule.h)
+            if (fused_plan_.ok && !p.min_sum && p.early_term && a.redo_list && !a.redo_count_in && !a.ratio_separate)
+                check(launch_decode_fused(a, dev_fused_, s), "decode (fused form)");
+            else if (fused_plan_.ok && !p.min_sum && !p.early_term && a.redo_list && a.redo_iter && !a.redo_count_in)
+            {
+                // without early termination: the fused form with separately divided outputs until a frame's totals near the edge
+                // of the box, then the LLR-domain launch below continues it (the messages are handed over as LLRs)
+                check(launch_decode_fused_handover(a, dev_fused_, s), "decode (fused form, hand-over)");
+                fused_handover_used = true;
+            }
+            else if (fused_plan_.ok && p.min_sum && !p.early_term && p.iterations > 0 && !a.redo_list && !a.redo_count_in)
+                check(launch_decode_fused_minsum(a, dev_fused_, s), "decode (min-sum, fused plan)");
             else
-                std::memset(out.codeword, 0, n * nc);
-        }
-        st.flush(s, &pin_out_);
-        return;
-    }
-    bool fused_handover_used = false;
-    bool finished_in_one = false; // the launch was the totals-form register kernel's chain of all three forms (kernels_reg2_impl.hpp)
-    const auto launch = [&] {
-        // the first launch of sum-product with early termination, for codes the fused form takes (fused_rule.h)
-        if (fused_plan_.ok && !p.min_sum && p.early_term && a.redo_list && !a.redo_count_in && !a.ratio_separate)
-            check(launch_decode_fused(a, dev_fused_, s), "decode (fused form)");
-        else if (fused_plan_.ok && !p.min_sum && !p.early_term && a.redo_list && a.redo_iter && !a.redo_count_in && !std::getenv("LDPC_AMD_NO_FUSED_HO"))
-        {
-            // without early termination: the fused form with separately divided outputs until a frame's totals near the edge
-            // of the box, then the LLR-domain launch below continues it (the messages are handed over as LLRs)
-            check(launch_decode_fused_handover(a, dev_fused_, s), "decode (fused form, hand-over)");
-            fused_handover_used = true;
-        }
-        else if (fused_plan_.ok && p.min_sum && !p.early_term && p.iterations > 0 && !a.redo_list && !a.redo_count_in &&
-                 !std::getenv("LDPC_AMD_NO_FUSED_MS"))
-            check(launch_decode_fused_minsum(a, dev_fused_, s), "decode (min-sum, fused plan)");
-        else if (plan_.lds_ok)
-        {
-            // Input LLRs: in registers when that frees the LDS for one more resident frame per CU (n=1024 code:
-            // 40 KB -> 31 KB, five frames instead of four) and the plan allows it; in LDS otherwise.  Device memory
-            // (mode 1) also reaches five frames but pays for it in memory reads (measured: no net gain).
-            const size_t cu_lds = 160 * 1024, with_llr = plan_.lds_bytes, without = plan_.lds_bytes - 8 * nc;
-            int llr_mode = 0;
-            if (cu_lds / without > cu_lds / with_llr && plan_.vn_work_stride <= 8 && !plan_.has_isolated_vn &&
-                plan_.nc <= plan_.nnz && !plan_.vn_packed.empty())
-                llr_mode = 2;
-            if (const char *e = std::getenv("LDPC_AMD_LLR_MODE"))
-                llr_mode = std::atoi(e);
-            if (llr_mode == 1)
-                a.ws_llr = static_cast<double *>(ws_llr_.reserve(8 * n * nc));
-            if (const char *e = std::getenv("LDPC_AMD_LDS_PAD")) // occupancy experiments: extra dynamic LDS per frame
-                a.plan.lds_bytes = dev_.lds_bytes + (static_cast<uint32_t>(std::strtoul(e, nullptr, 10)) & ~15u);
-            check(launch_decode_lds(a, p.min_sum, plan_.max_cn_degree, llr_mode, s), "decode (LDS-resident)");
-        }
-        else if (reg_plan_.ok && !std::getenv("LDPC_AMD_NO_REG"))
-        {
+                check(launch_decode_lds(a, p.min_sum, plan_.max_cn_degree, lds_llr_mode_, s), "decode (LDS-resident)");
+            break;
+        case Residency::kRegTotals:
+        case Residency::kRegMessages:
             a.ws_llr = static_cast<double *>(ws_llr_.reserve(8 * n * nc));
             a.ws_hb = static_cast<uint8_t *>(ws_hb_.reserve(n * nc));
-            if (reg2_plan_.ok)
+            if (residency_ == Residency::kRegTotals)
             {
                 // channel terms of the variable nodes, one per (block slot, thread): kernels_reg2.hip
                 a.ws_scr = static_cast<double *>(ws_scr_.reserve(8 * n * static_cast<uint64_t>(reg2_plan_.nv0 + reg2_plan_.nv1) * reg2_plan_.nt));
@@ -853,36 +849,28 @@ void Engine::run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, 
             }
             else
                 check(launch_decode_reg(a, dev_reg_, p.min_sum, s), "decode (register-resident)");
-        }
-        else if (plan_.hbm_ok)
-        {
+            break;
+        case Residency::kMemory:
             a.ws_msg = static_cast<double *>(ws_msg_.reserve(8 * n * nnz));
             a.ws_llr = static_cast<double *>(ws_llr_.reserve(8 * n * nc));
             a.ws_hb = static_cast<uint8_t *>(ws_hb_.reserve(n * nnz));
             a.ws_scr = plan_.max_cn_degree > kMaxCnDegree ? static_cast<double *>(ws_scr_.reserve(16 * n * nnz)) : nullptr;
-            // resident frames per CU are bounded through a dummy LDS request so that the frames in flight
-            // (256 CUs x frames/CU x state bytes) stay inside the 256 MiB Infinity Cache
-            const uint64_t per_frame = 8ull * nnz + 8ull * nc + nnz;
-            uint64_t frames_per_cu = std::clamp<uint64_t>((224ull << 20) / (256 * per_frame), 1, 8);
-            if (const char *e = std::getenv("LDPC_AMD_FRAMES_PER_CU"))
-                frames_per_cu = std::clamp<uint64_t>(std::strtoull(e, nullptr, 10), 1, 8);
-            const uint32_t occ_lds = frames_per_cu >= 8 ? 0 : static_cast<uint32_t>((160 * 1024) / (frames_per_cu + 1) + 1024) & ~15u;
-            check(launch_decode_mem(a, p.min_sum, plan_.max_cn_degree, occ_lds, s), "decode (memory-resident)");
-        }
-        else
+            check(launch_decode_mem(a, p.min_sum, plan_.max_cn_degree, mem_occ_lds_, s), "decode (memory-resident)");
+            break;
+        case Residency::kNone:
             throw std::runtime_error("code not supported by any decoder instantiation");
+        }
     };
     // Sum-product with early termination runs in likelihood-ratio form (detmath.h: no exp/log inside the
     // iteration); the few frames whose values leave the box that form can represent come back in a list and are
     // decoded from scratch by the LLR-domain form.  Which form finishes a frame depends on that frame's data
-    // only, never on the batch it travels in.  (LDPC_AMD_NO_RATIO: experiments only — results change by ulps.)
+    // only, never on the batch it travels in.
     // (codes with a check node wider than kMaxCnDegree run the LLR-domain form only; the oracle applies the same rule)
     // Without early termination the LDS-resident decoder still starts every frame in the ratio form and hands it over
     // to the LLR-domain form at an iteration boundary when its totals near the edge of the box (detmath.h "Hand-over").
-    const bool handover = !p.early_term && plan_.lds_ok;
+    const bool handover = !p.early_term && residency_ == Residency::kLds;
     bool later_stages = true;
-    if (!p.min_sum && (p.early_term || handover) && p.iterations > 0 && plan_.max_cn_degree <= kMaxCnDegree &&
-        !std::getenv("LDPC_AMD_NO_RATIO"))
+    if (!fast && !p.min_sum && (p.early_term || handover) && p.iterations > 0 && plan_.max_cn_degree <= kMaxCnDegree)
     {
         uint32_t *redo = static_cast<uint32_t *>(redo_.reserve(4 * (2 * n + 1)));
         check(hipMemsetAsync(redo, 0, 4, s), "redo count");
@@ -894,7 +882,8 @@ void Engine::run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, 
         }
 #ifdef LDPC_AMD_PHASE_TRACE
         uint64_t *tr = nullptr;
-        if (std::getenv("LDPC_AMD_PHASE_TRACE")) // debug build: per-wave phase timers of the first 2048 frames -> file
+        const char *trace_file = std::getenv("LDPC_AMD_PHASE_TRACE"); // debug build: per-wave phase timers of the first 2048 frames
+        if (trace_file)
         {
             check(hipMalloc(&tr, 2048 * 32 * 8), "trace");
             check(hipMemset(tr, 0, 2048 * 32 * 8), "trace");
@@ -908,7 +897,7 @@ void Engine::run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, 
             std::vector<uint64_t> h(2048 * 32);
             check(hipDeviceSynchronize(), "sync");
             check(hipMemcpy(h.data(), tr, 2048 * 32 * 8, hipMemcpyDeviceToHost), "trace");
-            if (FILE *f = std::fopen(std::getenv("LDPC_AMD_PHASE_TRACE"), "wb"))
+            if (FILE *f = std::fopen(trace_file, "wb"))
             {
                 std::fwrite(h.data(), 8, h.size(), f);
                 std::fclose(f);
@@ -939,7 +928,7 @@ void Engine::run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, 
             a.redo_iter_in = redo + 1 + n;
             a.handover_llr = fused_handover_used ? 1 : 0;
         }
-        else if (plan_.lds_ok || shared6_)
+        else if (residency_ == Residency::kLds || shared6_)
         {
             // (codes the LDS-resident decoder does not take: the same three launches when the code has check nodes of degree 6,
             // which share reciprocals in the first launch of the register- and memory-resident decoders — detmath.h, dm_cn6_shared)
@@ -948,7 +937,7 @@ void Engine::run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, 
             // from scratch with every output divided separately — the ratio form still, a twentieth of a millisecond for a
             // few dozen frames — and only what leaves the box there goes on to the LLR domain.  (A lone frame takes 0.3 ms
             // in the LLR domain, and the launches of a batch run one after the other.)
-            if (plan_.lds_ok)
+            if (residency_ == Residency::kLds)
             {
                 // LDS-resident: ONE more launch, over the list — separately divided outputs and, for what leaves the box there,
                 // the LLR domain, frame by frame in the same workgroup (kernels.hip, decode_kernel_list)
@@ -973,27 +962,21 @@ void Engine::run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, 
     if (later_stages)
         launch();
     a.redo_count_in = nullptr, a.redo_list_in = nullptr, a.redo_iter_in = nullptr, a.ws_handover = nullptr, a.handover_llr = 0;
-    prof_mark(0, s);
-    if (a.mode == kModeAwgn && a.pairs_buffer >= 0 && ev_pairs_free_[a.pairs_buffer])
-    {
-        check(hipEventRecord(static_cast<hipEvent_t>(ev_pairs_free_[a.pairs_buffer]), s), "event");
-        pairs_in_use_[a.pairs_buffer] = true;
-    }
-    if (out.codeword)
-    {
-        if (a.codeword)
-            check(hipMemcpyAsync(out.codeword, a.codeword, n * nc,
-                                 is_device_ptr(out.codeword) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s),
-                  "codeword out");
-        else if (is_device_ptr(out.codeword))
-            check(hipMemsetAsync(out.codeword, 0, n * nc, s), "codeword out");
-        else
-            std::memset(out.codeword, 0, n * nc);
-    }
-    st.flush(s, &pin_out_);
+    finish_batch(st, out, n, a.codeword, a.mode == kModeAwgn ? a.pairs_buffer : -1, stream);
 }
 
-void Engine::run_bec(const DecParams &p, const BatchOut &out, uint64_t n, const uint8_t *codeword, void *stream)
+void Engine::run_bsc(DecodeArgs &a, const DecParams &p, const BatchOut &out, uint64_t n, uint64_t raw_first, void *stream)
+{
+    a.mode = kModeBsc;
+    int raw_buffer = 0;
+    a.raw = noise_raw_async(raw_first, n * static_cast<uint64_t>(plan_.nct), stream, raw_buffer);
+    a.eps = x_, a.delta = delta_;
+    a.shorten_llr = delta_; // channel.cpp:152
+    run_decode(a, p, out, n, stream);
+    noise_raw_release(raw_buffer, stream);
+}
+
+void Engine::run_bec(const DecParams &p, const BatchOut &out, uint64_t n, const uint8_t *codeword, uint64_t raw_first, void *stream)
 {
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t nc = plan_.nc;
@@ -1008,7 +991,7 @@ void Engine::run_bec(const DecParams &p, const BatchOut &out, uint64_t n, const 
     a.deg1_compat = bec_deg1_compat;
     a.n_frames = n;
     int raw_buffer = 0;
-    a.raw = noise_raw_async(raw_next_, n * nct, stream, raw_buffer);
+    a.raw = noise_raw_async(raw_first, n * nct, stream, raw_buffer);
     a.eps = x_;
     a.codeword = codeword;
     a.iters = st.route(out.iters, stage_iters_, 4 * n);
@@ -1018,20 +1001,27 @@ void Engine::run_bec(const DecParams &p, const BatchOut &out, uint64_t n, const 
     a.llr_in_dump = st.route(out.llr_in, stage_llr_in_, 8 * n * nc);
     prof_mark(0, s);
     check(launch_bec(a, s), "bec");
-    prof_mark(0, s);
-    noise_raw_release(raw_buffer, stream);
-    if (out.codeword)
+    finish_batch(st, out, n, codeword, raw_buffer, stream);
+}
+
+uint8_t *Engine::encoder_prologue(uint64_t frames_kept, bool sharded, void *stream)
+{
+    const int kc = code_->kc();
+    if (kc <= 0 || code_->G.rows > kc)
+        throw std::runtime_error("generator matrix does not match the code (rows > nc - mc)");
+    if (sharded && static_cast<size_t>((kc + 63) / 64) * 8 > Comm::kMaxBytes)
+        throw std::runtime_error("sharded encoding: more than 2048 information bits per frame do not fit the exchange");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t nc = plan_.nc;
+    uint8_t *prev = static_cast<uint8_t *>(cw_run_.reserve(nc));
+    if (!cw_run_valid_)
     {
-        if (codeword)
-            check(hipMemcpyAsync(out.codeword, codeword, n * nc,
-                                 is_device_ptr(out.codeword) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s),
-                  "codeword out");
-        else if (is_device_ptr(out.codeword))
-            check(hipMemsetAsync(out.codeword, 0, n * nc, s), "codeword out");
-        else
-            std::memset(out.codeword, 0, n * nc);
+        check(hipMemsetAsync(prev, 0, nc, s), "codeword reset");
+        cw_run_valid_ = true;
     }
-    st.flush(s, &pin_out_);
+    check(hipMemcpyAsync(cw_before_.reserve(nc), prev, nc, hipMemcpyDeviceToDevice, s), "codeword snapshot");
+    last_enc_n_ = frames_kept;
+    return prev;
 }
 
 // channel.cpp:44-60 for n consecutive frames (see EncodeArgs in kernels.hpp)
@@ -1042,16 +1032,7 @@ const uint8_t *Engine::encode_frames(uint64_t n, bool want_codewords, void *stre
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t nc = plan_.nc;
     const uint64_t kc = static_cast<uint64_t>(code_->kc());
-    if (code_->kc() <= 0 || code_->G.rows > code_->kc())
-        throw std::runtime_error("generator matrix does not match the code (rows > nc - mc)");
-    uint8_t *prev = static_cast<uint8_t *>(cw_run_.reserve(nc));
-    if (!cw_run_valid_)
-    {
-        check(hipMemsetAsync(prev, 0, nc, s), "codeword reset");
-        cw_run_valid_ = true;
-    }
-    check(hipMemcpyAsync(cw_before_.reserve(nc), prev, nc, hipMemcpyDeviceToDevice, s), "codeword snapshot");
-    last_enc_n_ = want_codewords ? n : 0;
+    uint8_t *prev = encoder_prologue(want_codewords ? n : 0, false, stream);
     EncodeArgs e{};
     e.nc = static_cast<int>(nc);
     e.kc = static_cast<int>(kc);
@@ -1079,19 +1060,8 @@ const uint8_t *Engine::encode_frames_sharded(Comm &comm, uint64_t before, uint64
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t nc = plan_.nc;
     const uint64_t kc = static_cast<uint64_t>(code_->kc());
-    if (code_->kc() <= 0 || code_->G.rows > code_->kc())
-        throw std::runtime_error("generator matrix does not match the code (rows > nc - mc)");
+    uint8_t *prev = encoder_prologue(n, true, stream);
     const int words = static_cast<int>((kc + 63) / 64);
-    if (static_cast<size_t>(words) * 8 > Comm::kMaxBytes)
-        throw std::runtime_error("sharded encoding: more than 2048 information bits per frame do not fit the exchange");
-    uint8_t *prev = static_cast<uint8_t *>(cw_run_.reserve(nc));
-    if (!cw_run_valid_)
-    {
-        check(hipMemsetAsync(prev, 0, nc, s), "codeword reset");
-        cw_run_valid_ = true;
-    }
-    check(hipMemcpyAsync(cw_before_.reserve(nc), prev, nc, hipMemcpyDeviceToDevice, s), "codeword snapshot");
-    last_enc_n_ = n;
     // this rank's frames: info words and their running XOR (the last entry is the XOR over the rank's range)
     uint64_t *base = static_cast<uint64_t *>(enc_base_.reserve(8 * 2 * static_cast<size_t>(words)));
     EncodeArgs e{};
@@ -1152,13 +1122,6 @@ void Engine::decode_llr(const DecParams &p, uint64_t n, const double *llr_in, co
     {
         const uint64_t m = std::min(sub, n - done);
         const size_t bytes = 8 * m * nc;
-        BatchOut o = out;
-        if (o.iters) o.iters += done;
-        if (o.bit_errors) o.bit_errors += done;
-        if (o.hard) o.hard += done * nc;
-        if (o.llr_out) o.llr_out += done * nc;
-        if (o.llr_in) o.llr_in += done * nc;
-        if (o.codeword) o.codeword += done * nc;
         DecodeArgs a{};
         a.mode = kModeLlr;
         const double *src = llr_in + done * nc;
@@ -1187,7 +1150,7 @@ void Engine::decode_llr(const DecParams &p, uint64_t n, const double *llr_in, co
                 check(hipEventRecord(static_cast<hipEvent_t>(pin_in_ev_), s), "event");
             a.llr_in = static_cast<const double *>(d);
         }
-        run_decode(a, p, o, m, stream);
+        run_decode(a, p, out.at(done, nc), m, stream);
     }
 }
 
@@ -1216,7 +1179,7 @@ void Engine::stream_begin(int channel, uint64_t seed, double x, bool fresh)
     chan_ = channel;
     // jump-ahead in four thread groups where its latency counts: the erasure channel (its bit-sliced decoder leaves the noise
     // chain on the critical path) and beside the register-resident decoders (rng_kernels.hip, mt_jump_kernel)
-    noise_.st.set_jump_groups(channel == kBec || reg_plan_.ok ? 4 : 1);
+    noise_.st.set_jump_groups(channel == kBec || register_resident() ? 4 : 1);
     x_ = x;
     frame_pos_ = 0;
     raw_next_ = 0;
@@ -1362,7 +1325,7 @@ void Engine::awgn_prepare(uint64_t n, DecodeArgs &a, void *stream, bool write_no
     // pairs that must exist from the start of chunk cur_chunk_ on / list index of the first pair the NEXT batch needs
     const uint64_t need = cur_k_ + (q1 - q0 + 1), target = cur_k_ + (qn - q0);
     if (write_normals && small_cache_.valid && small_cache_.chunk == cur_chunk_ && need <= small_cache_.np.res.total &&
-        target < small_cache_.np.res.total && !std::getenv("LDPC_AMD_NO_SMALL_CACHE"))
+        target < small_cache_.np.res.total)
     {
         // (the slab was complete when the pass that made it returned, and the decode launches that read it since are
         // ordered on the caller's stream by the events of run_decode as for any batch)
@@ -1391,7 +1354,6 @@ void Engine::awgn_prepare(uint64_t n, DecodeArgs &a, void *stream, bool write_no
     if (small)
         trials += 24.0 * static_cast<double>(nct / 2 + 1) * 1.2732395447351628;
     NoisePass np;
-    PhaseTrace tr;
     prof_mark(1, s);
     for (;;)
     {
@@ -1402,7 +1364,6 @@ void Engine::awgn_prepare(uint64_t n, DecodeArgs &a, void *stream, bool write_no
             ++full, last_blocks = 0;
         np = noise_pass(cur_chunk_, static_cast<uint32_t>(full), last_blocks, static_cast<uint32_t>(full + (last_blocks ? 1 : 0)), need, target,
                         buf, write_normals, false, 0);
-        tr.mark("noise pass");
         if (np.res.enough)
             break;
         trials += trials / 8 + 4096; // vanishingly rare: take a longer look at the same stream
@@ -1522,14 +1483,7 @@ void Engine::stream_decode(const DecParams &p, uint64_t n_frames, const BatchOut
     while (done < n_frames)
     {
         const uint64_t n = std::min<uint64_t>(n_frames - done, sub);
-        BatchOut o = out;
-        if (o.iters) o.iters += done;
-        if (o.bit_errors) o.bit_errors += done;
-        if (o.hard) o.hard += done * nc;
-        if (o.llr_out) o.llr_out += done * nc;
-        if (o.llr_in) o.llr_in += done * nc;
-        if (o.codeword) o.codeword += done * nc;
-        PhaseTrace tr;
+        const BatchOut o = out.at(done, nc);
         const uint8_t *cw = encode_frames(n, true, stream);
         DecodeArgs a{};
         a.codeword = cw;
@@ -1537,24 +1491,14 @@ void Engine::stream_decode(const DecParams &p, uint64_t n_frames, const BatchOut
         {
             a.mode = kModeAwgn;
             awgn_prepare(n, a, stream);
-            tr.mark("awgn_prepare");
             run_decode(a, p, o, n, stream);
-            tr.mark("run_decode(enq)");
-        }
-        else if (chan_ == kBsc)
-        {
-            a.mode = kModeBsc;
-            int raw_buffer = 0;
-            a.raw = noise_raw_async(raw_next_, n * nct, stream, raw_buffer);
-            a.eps = x_, a.delta = delta_;
-            a.shorten_llr = delta_; // channel.cpp:152
-            run_decode(a, p, o, n, stream);
-            noise_raw_release(raw_buffer, stream);
-            raw_next_ += n * nct;
         }
         else
         {
-            run_bec(p, o, n, cw, stream);
+            if (chan_ == kBsc)
+                run_bsc(a, p, o, n, raw_next_, stream);
+            else
+                run_bec(p, o, n, cw, raw_next_, stream);
             raw_next_ += n * nct;
         }
         frame_pos_ += n;
@@ -1734,22 +1678,11 @@ Engine::ShardStep Engine::stream_decode_sharded(Comm &comm, const DecParams &p, 
         }
         else if (chan_ == kBsc)
         {
-            a.mode = kModeBsc;
             a.codeword = cw;
-            int raw_buffer = 0;
-            a.raw = noise_raw_async(st.first * nct, st.n * nct, stream, raw_buffer);
-            a.eps = x_, a.delta = delta_;
-            a.shorten_llr = delta_; // channel.cpp:152
-            run_decode(a, p, out, st.n, stream);
-            noise_raw_release(raw_buffer, stream);
+            run_bsc(a, p, out, st.n, st.first * nct, stream);
         }
         else
-        {
-            const uint64_t keep_raw = raw_next_;
-            raw_next_ = st.first * nct; // run_bec reads the stream at raw_next_
-            run_bec(p, out, st.n, cw, stream);
-            raw_next_ = keep_raw;
-        }
+            run_bec(p, out, st.n, cw, st.first * nct, stream);
     }
     else if (chan_ == kAwgn && a.pairs_buffer >= 0)
         pairs_in_use_[a.pairs_buffer] = false;

@@ -44,7 +44,31 @@ struct BatchOut
     double *llr_out = nullptr;      // [n][nc] (BEC: symbol values widened to double)
     double *llr_in = nullptr;       // [n][nc]
     uint8_t *codeword = nullptr;    // [n][nc]
+    // the same outputs from frame `frame` of the batch on (a sub-batch)
+    BatchOut at(uint64_t frame, uint64_t nc) const
+    {
+        BatchOut o = *this;
+        if (o.iters) o.iters += frame;
+        if (o.bit_errors) o.bit_errors += frame;
+        if (o.hard) o.hard += frame * nc;
+        if (o.llr_out) o.llr_out += frame * nc;
+        if (o.llr_in) o.llr_in += frame * nc;
+        if (o.codeword) o.codeword += frame * nc;
+        return o;
+    }
 };
+
+// Where a frame's decoder state lives: fixed per code when the engine is built (Engine::residency)
+enum class Residency : int
+{
+    kNone,        // no decoder instantiation takes the code (the first decode throws)
+    kLds,         // LDS-resident (kernels.hip, kernels_fused.hip)
+    kRegTotals,   // register-resident, totals form (kernels_reg2.hip)
+    kRegMessages, // register-resident, messages form (kernels_reg.hip)
+    kMemory       // messages in device memory (kernels.hip)
+};
+
+struct OutStage; // engine.cpp: a batch's outputs, written directly or through staging buffers
 
 class DeviceBuffer
 {
@@ -112,7 +136,6 @@ class MtDevice
     // object's own stream (three tables: the generator of this step reads one while the others are written)
     void prefetch_strided();
     uint64_t jump_tasks() const { return jump_tasks_; } // jump-ahead tasks launched so far (tools/shard_probe.py)
-    void set_jump_pack(int tasks_per_workgroup) { jump_pack_ = tasks_per_workgroup; } // kernels.hpp launch_mt_jump
     void set_jump_groups(int groups) { jump_groups_ = groups; }
 
   private:
@@ -127,7 +150,6 @@ class MtDevice
     DeviceBuffer ring_buf_, strided_buf_;
     std::vector<std::pair<uint64_t, void *>> polys_; // (stride in chunks, device copy)
     uint64_t jump_tasks_ = 0;
-    int jump_pack_ = 1;
     int jump_groups_ = 1;
     bool ring_polys_ready_ = false;
     // look-ahead launches in flight on jump_stream_: the ring rows of chunks [hi_before, hi_after) are valid after `event`
@@ -177,6 +199,7 @@ class Engine
     const RegPlan &reg_plan() const { return reg_plan_; }
     const Reg2Plan &reg2_plan() const { return reg2_plan_; }
     const FusedPlan &fused_plan() const { return fused_plan_; }
+    Residency residency() const { return residency_; }
     int device() const { return device_; }
     bool bec_deg1_compat = false;
     // opt-in NON-PARITY modes, off (0) by default and never chosen by the library: 1 = flooding sum-product with binary32
@@ -239,8 +262,14 @@ class Engine
     const uint64_t *noise_raw_async(uint64_t first, uint64_t count, void *stream, int &buffer);
     void noise_raw_release(int buffer, void *stream);
     void upload_plan();
+    void ensure_layer_plan(); // the layered schedule of non-parity modes 2 / 3, built and uploaded at their first use
+    bool register_resident() const { return residency_ == Residency::kRegTotals || residency_ == Residency::kRegMessages; }
     void run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, uint64_t n, void *stream);
-    void run_bec(const DecParams &p, const BatchOut &out, uint64_t n, const uint8_t *codeword, void *stream);
+    // BSC / BEC: the batch reads the noise stream's raw draws from word `raw_first` on
+    void run_bsc(DecodeArgs &a, const DecParams &p, const BatchOut &out, uint64_t n, uint64_t raw_first, void *stream);
+    void run_bec(const DecParams &p, const BatchOut &out, uint64_t n, const uint8_t *codeword, uint64_t raw_first, void *stream);
+    // after a batch's last launch: the noise buffer it read released (-1: none), the codewords and the staged outputs delivered
+    void finish_batch(OutStage &st, const BatchOut &out, uint64_t n, const uint8_t *codeword, int noise_buffer, void *stream);
     // normals of frames [frame_pos_, frame_pos_ + n): generate, count, place (write_normals false: count only, stream_skip)
     void awgn_prepare(uint64_t n_frames, DecodeArgs &a, void *stream, bool write_normals = true);
     // one generator pass over chunks [chunk, chunk + full) (+ a prefix of `last_blocks` blocks of the next one) on the side stream
@@ -270,6 +299,9 @@ class Engine
     // draws the info words of ITS frames only, the ranks exchange the XOR of theirs (one all-gather of ceil(kc / 64) words),
     // and every rank ends with the codeword accumulated over the whole step.  Returns this rank's codewords [n][nc].
     const uint8_t *encode_frames_sharded(Comm &comm, uint64_t before, uint64_t n, uint64_t step_frames, void *stream);
+    // both: G checked against the code (and, sharded, against the exchange's size), the running codeword (zeroed when not
+    // valid) and its copy for stream_rewind_encoder; returns the running codeword
+    uint8_t *encoder_prologue(uint64_t frames_kept, bool sharded, void *stream);
 
     std::unique_ptr<LdpcCode> code_;
     Plan plan_;
@@ -277,6 +309,9 @@ class Engine
     Reg2Plan reg2_plan_;
     bool shared6_ = false; // not LDS-resident and a check node of degree 6: three launches with early termination (dm_cn6_shared)
     FusedPlan fused_plan_; // fused form of the first ratio launch (kernels_fused.hip); ok = the code qualifies (fused_rule.h)
+    Residency residency_ = Residency::kNone;
+    int lds_llr_mode_ = 0;     // LDS-resident: the input LLRs in LDS (0) or in registers (2), kernels.hpp launch_decode_lds
+    uint32_t mem_occ_lds_ = 0; // memory-resident: the dummy LDS request that bounds the resident frames per CU
     DevFusedPlan dev_fused_{};
     LayerPlan layer_plan_;
     DevLayerPlan dev_layer_{};

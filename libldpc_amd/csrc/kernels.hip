@@ -2320,20 +2320,14 @@ int launch_decode_lds(const DecodeArgs &a, bool min_sum, int max_cn_degree, int 
 {
     if (a.n_frames == 0)
         return hipSuccess;
-    if (llr_mode == kLlrMem && !a.ws_llr)
-        return hipErrorInvalidValue;
     if (llr_mode == kLlrRegs && (a.plan.vn_work_stride > kMaxVnBlocksInRegs || a.plan.nc > a.plan.nnz || !a.plan.vn_packed))
         return hipErrorInvalidValue;
-    uint32_t lds = a.plan.lds_bytes - (llr_mode != kLlrLds ? 8u * static_cast<uint32_t>(a.plan.nc) : 0u);
+    uint32_t lds = a.plan.lds_bytes - (llr_mode == kLlrRegs ? 8u * static_cast<uint32_t>(a.plan.nc) : 0u);
     if (a.redo_list) // ratio form: no hard-bit array (the last array of the frame in every layout)
         lds -= ((static_cast<uint32_t>(a.plan.nnz) + 15u) / 16u) * 16u;
-#define LDPC_PICK(D)                                                              \
-    switch (llr_mode)                                                             \
-    {                                                                             \
-    case kLlrMem: return launch_decode<true, D, kLlrMem>(a, min_sum, lds, stream);   \
-    case kLlrRegs: return launch_decode<true, D, kLlrRegs>(a, min_sum, lds, stream); \
-    default: return launch_decode<true, D, kLlrLds>(a, min_sum, lds, stream);        \
-    }
+#define LDPC_PICK(D)                                                                                                  \
+    return llr_mode == kLlrRegs ? launch_decode<true, D, kLlrRegs>(a, min_sum, lds, stream)                             \
+                                : launch_decode<true, D, kLlrLds>(a, min_sum, lds, stream);
     if (max_cn_degree <= 4)
     {
         LDPC_PICK(4)
@@ -2383,8 +2377,8 @@ int launch_bec(const BecArgs &a, void *stream)
 {
     if (a.n_frames == 0)
         return hipSuccess;
-    // codes whose bit-sliced state fits LDS: 64 frames per workgroup (kernels_bec.hip); LDPC_AMD_NO_BEC_SLICED: experiments
-    if (!a.ws && bec_sliced_fits(a.plan) && !std::getenv("LDPC_AMD_NO_BEC_SLICED"))
+    // codes whose bit-sliced state fits LDS: 64 frames per workgroup (kernels_bec.hip)
+    if (!a.ws && bec_sliced_fits(a.plan))
         return launch_bec_sliced(a, stream);
     const uint32_t lds = a.ws ? 16u : bec_state_bytes(a.plan.nnz, a.plan.nc);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(bec_kernel),

@@ -480,23 +480,17 @@ int launch_mt_generate(const uint64_t *ring, uint32_t ring_rows, uint32_t first_
 }
 
 int launch_mt_jump(uint64_t *ring, uint32_t ring_rows, uint32_t src_first, uint32_t dst_first, const uint64_t *poly,
-                   uint32_t n_tasks, int pack, int groups, void *stream)
+                   uint32_t n_tasks, int groups, void *stream)
 {
     if (n_tasks == 0)
         return hipSuccess;
     if (src_first >= ring_rows || dst_first >= ring_rows || n_tasks > ring_rows)
         return hipErrorInvalidValue;
     // groups = 4: one task per workgroup in four groups with branches (a short chain); else the one-group kernel with masked
-    // XORs, `pack` tasks to a workgroup (LDPC_AMD_JUMP_GROUPS: experiments)
-    static const int groups_env = std::getenv("LDPC_AMD_JUMP_GROUPS") ? std::atoi(std::getenv("LDPC_AMD_JUMP_GROUPS")) : 0;
-    if (groups_env)
-        groups = groups_env;
+    // XORs, one task to a workgroup
     if (groups >= 4)
         hipLaunchKernelGGL((mt_jump_kernel<1, 4, true>), dim3(n_tasks), dim3(kJumpThreads * 4), 0, static_cast<hipStream_t>(stream), ring, ring_rows,
                            src_first, dst_first, poly, n_tasks);
-    else if (pack >= 3)
-        hipLaunchKernelGGL((mt_jump_kernel<3, 1, false>), dim3((n_tasks + 2) / 3), dim3(kJumpThreads * 3), 0, static_cast<hipStream_t>(stream), ring,
-                           ring_rows, src_first, dst_first, poly, n_tasks);
     else
         hipLaunchKernelGGL((mt_jump_kernel<1, 1, false>), dim3(n_tasks), dim3(kJumpThreads), 0, static_cast<hipStream_t>(stream), ring, ring_rows,
                            src_first, dst_first, poly, n_tasks);
