@@ -123,6 +123,31 @@ void ldpc_hip_set_bec_compat(ldpc_hip_ctx *ctx, int compat);
    gpu/ldpc/ldpc.h, gpu/ldpc/ldpc.cpp:111-138: ideas only). */
 void ldpc_hip_set_fast_mode(ldpc_hip_ctx *ctx, int mode);
 
+/* Noise of the stream interface (ldpc_hip_stream_*, ldpc_hip_simulate*).  LDPC_HIP_NOISE_REFERENCE (the default) is the
+   reference's own stream, mt19937_64(seed): every frame can be held bit for bit against the reference.
+   LDPC_HIP_NOISE_COUNTER is NON-PARITY and not seed-comparable with the reference: a frame's noise is Philox4x32-10 of
+   (seed, frame index since ldpc_hip_stream_begin, bit index), computed inside the decode launch, and the same seed gives the
+   same frames on any number of GPUs and in any batch split.  Key (seed & 0xFFFFFFFF, seed >> 32), counter (block, frame low,
+   frame high, tag); tag 0 AWGN: transmitted bit i is normal i % 4 of block i / 4, two binary32 Box-Muller pairs per block,
+   u = (w0 + 0.5) / 2^32, angle w1 / 2^32 revolutions (so |n| <= sqrt(66 ln 2) = 6.764); tag 1 BSC / BEC: bit i flipped /
+   erased when (w[i % 4] of block i / 4 + 0.5) / 2^32 < eps; tag 2 encoder (a generator matrix loaded): info bit j is bit
+   j % 32 of word (j / 32) % 4 of block j / 128, and frame f's codeword is u_f G (no running sum over the frames).  Only error
+   rates (statistically) compare with the reference; ldpc_hip_stream_skip is O(1), ldpc_hip_stream_raw_draws fails, a
+   sharded step exchanges nothing.  Does not combine with ldpc_hip_set_fast_mode (ldpc_hip_stream_decode fails).  Part 1
+   (simulate(), decode(), ...) always uses the reference stream. */
+enum
+{
+    LDPC_HIP_NOISE_REFERENCE = 0,
+    LDPC_HIP_NOISE_COUNTER = 1
+};
+/* takes effect at the next ldpc_hip_stream_begin; touches no GPU.  0, or -1 (last_error set) for an unknown mode */
+int ldpc_hip_set_noise(ldpc_hip_ctx *ctx, int mode);
+/* the counter mode's raw generator words: out[4 i + k] = word k of Philox4x32-10 block first_block + i of `frame` under
+   `tag` and seed (n_blocks <= 2^32 - first_block); out is device or host memory.  For tests, as ldpc_hip_mt64 is for the
+   reference stream.  0 on success */
+int ldpc_hip_philox(ldpc_hip_ctx *ctx, uint64_t seed, uint32_t tag, uint64_t frame, uint32_t first_block, uint64_t n_blocks,
+                    uint32_t *out, void *hip_stream);
+
 /* decode n frames of given LLRs llr_in[n][nc] (column order, device or host). 0 on success. */
 int ldpc_hip_decode_batch(ldpc_hip_ctx *ctx, decoder_param dec, uint64_t n, const double *llr_in,
                           const ldpc_hip_out *out, void *hip_stream);

@@ -57,6 +57,10 @@ def load_library(path=LIB_PATH):
     L.ldpc_hip_code_info.argtypes = [vp, ct.POINTER(ct.c_int64)]
     L.ldpc_hip_set_bec_compat.argtypes = [vp, i32]
     L.ldpc_hip_set_fast_mode.argtypes = [vp, i32]
+    L.ldpc_hip_set_noise.restype = i32
+    L.ldpc_hip_set_noise.argtypes = [vp, i32]
+    L.ldpc_hip_philox.restype = i32
+    L.ldpc_hip_philox.argtypes = [vp, u64, ct.c_uint32, u64, ct.c_uint32, u64, vp, vp]
     L.ldpc_hip_decode_batch.restype = i32
     L.ldpc_hip_decode_batch.argtypes = [vp, decoder_param, u64, vp, ct.POINTER(ldpc_hip_out), vp]
     L.ldpc_hip_stream_begin.restype = i32
@@ -251,6 +255,24 @@ class HipDecoder:
     def set_fast_mode(self, on):
         """Opt-in NON-PARITY mode: sum-product with binary32 messages (include/ldpc_amd.h)."""
         self.lib.ldpc_hip_set_fast_mode(self.ctx, int(on))
+
+    NOISE_MODES = {"reference": 0, "counter": 1}
+
+    def set_noise(self, mode):
+        """Noise of the stream interface from the next stream_begin on: "reference" (the default: the reference's
+        mt19937_64 stream, parity) or "counter" (Philox4x32-10 of (seed, frame, bit): NON-PARITY, include/ldpc_amd.h)."""
+        m = self.NOISE_MODES.get(mode, mode) if isinstance(mode, str) else int(mode)
+        if isinstance(m, str):
+            m = -1
+        self._check(self.lib.ldpc_hip_set_noise(self.ctx, int(m)), f"ldpc_hip_set_noise({mode!r})")
+
+    def philox(self, seed, tag, frame, first_block, n_blocks):
+        """The counter mode's raw words, [n_blocks][4] uint32: blocks first_block.. of `frame` under `tag` (0 AWGN, 1 BSC /
+        BEC, 2 encoder info bits), from the device generator."""
+        out = np.zeros((int(n_blocks), 4), np.uint32)
+        self._check(self.lib.ldpc_hip_philox(self.ctx, int(seed), int(tag), int(frame), int(first_block), int(n_blocks),
+                                             _ptr(out), None), "ldpc_hip_philox")
+        return out
 
     def decode_batch(self, llr_in, early_term=True, iterations=50, decoding="BP",
                      want=("iters", "hard", "llr_out"), out=None, stream=None):

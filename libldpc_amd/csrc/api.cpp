@@ -32,6 +32,7 @@ struct ldpc_hip_ctx
     std::unique_ptr<Engine> eng;
     MtStream aux;
     DeviceBuffer aux_out;
+    DeviceBuffer philox_buf; // ldpc_hip_philox into host memory: the words pass through here
     std::string description;
 };
 
@@ -269,6 +270,50 @@ const char *ldpc_hip_describe(ldpc_hip_ctx *ctx)
 
 void ldpc_hip_set_bec_compat(ldpc_hip_ctx *ctx, int compat) { ctx->eng->bec_deg1_compat = compat != 0; }
 void ldpc_hip_set_fast_mode(ldpc_hip_ctx *ctx, int mode) { ctx->eng->fast_mode = mode < 0 || mode > 3 ? 0 : mode; }
+
+int ldpc_hip_set_noise(ldpc_hip_ctx *ctx, int mode)
+{
+    return guarded([&] {
+        if (mode != LDPC_HIP_NOISE_REFERENCE && mode != LDPC_HIP_NOISE_COUNTER)
+            throw std::runtime_error("ldpc_hip_set_noise: unknown noise mode " + std::to_string(mode) +
+                                     " (0 = reference stream, 1 = counter-based)");
+        ctx->eng->noise_mode = mode;
+    });
+}
+
+int ldpc_hip_philox(ldpc_hip_ctx *ctx, uint64_t seed, uint32_t tag, uint64_t frame, uint32_t first_block, uint64_t n_blocks,
+                    uint32_t *out, void *hip_stream)
+{
+    return guarded([&] {
+        if (n_blocks > (1ull << 32) - first_block)
+            throw std::runtime_error("ldpc_hip_philox: blocks beyond 2^32");
+        if (!out && n_blocks)
+            throw std::runtime_error("ldpc_hip_philox: null output");
+        if (ldpc_hip_device_count() <= ctx->eng->device())
+            throw std::runtime_error("no usable HIP device (MI355X required)");
+        if (hipSetDevice(ctx->eng->device()) != hipSuccess)
+            throw std::runtime_error("hipSetDevice failed");
+        hipStream_t s = static_cast<hipStream_t>(hip_stream);
+        hipPointerAttribute_t attr;
+        const bool dev = hipPointerGetAttributes(&attr, out) == hipSuccess && attr.type == hipMemoryTypeDevice;
+        if (!dev)
+            (void)hipGetLastError();
+        uint64_t done = 0;
+        while (done < n_blocks)
+        {
+            const uint64_t k = std::min<uint64_t>(n_blocks - done, 16ull << 20);
+            uint32_t *dst = out + 4 * done;
+            if (!dev)
+                dst = static_cast<uint32_t *>(ctx->philox_buf.reserve(16 * k));
+            if (launch_philox(seed, tag, frame, first_block + static_cast<uint32_t>(done), k, dst, s) != hipSuccess)
+                throw std::runtime_error("ldpc_hip_philox: launch failed");
+            if ((!dev && hipMemcpyAsync(out + 4 * done, dst, 16 * k, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+                hipStreamSynchronize(s) != hipSuccess)
+                throw std::runtime_error("copy of Philox words failed");
+            done += k;
+        }
+    });
+}
 
 int ldpc_hip_decode_batch(ldpc_hip_ctx *ctx, decoder_param dec, uint64_t n, const double *llr_in,
                           const ldpc_hip_out *out, void *hip_stream)

@@ -8,12 +8,13 @@
 #include <hip/hip_runtime.h>
 
 #include "device_math.hpp"
+#include "device_philox.hpp"
 #include "kernels.hpp"
 
 namespace ldpc_amd
 {
 
-template <int NT>
+template <int NT, int NK = kNoiseStream>
 __device__ __forceinline__ void channel_init(const DecodeArgs &a, uint64_t frame, double *llr, int tid)
 {
     const DevPlan &P = a.plan;
@@ -57,7 +58,40 @@ __device__ __forceinline__ void channel_init(const DecodeArgs &a, uint64_t frame
             for (int r8 = 8 * (tid + kThreads); r8 < nc; r8 += 8 * kThreads)
                 apply_kinds(r8, *reinterpret_cast<const uint64_t *>(P.rank_kind + r8));
         };
-        if (a.mode == kModeAwgn)
+        if (counter_mode<NK>(a)) // counter-based noise (device_philox.hpp): a thread takes the four transmitted bits of a Philox block
+        {
+            const bool awgn = a.mode == kModeAwgnCtr;
+            const uint64_t f = a.ctr_frame0 + frame;
+            for (int b = tid; 4 * b < nct; b += kThreads)
+            {
+                const uint4 w = philox_block(a.ctr_key[0], a.ctr_key[1], f, static_cast<uint32_t>(b), awgn ? kTagAwgn : kTagDraw);
+                float2 p0{0.f, 0.f}, p1{0.f, 0.f};
+                if (awgn)
+                    p0 = box_muller(w.x, w.y), p1 = box_muller(w.z, w.w);
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                {
+                    const int i = 4 * b + k;
+                    if (i >= nct)
+                        break;
+                    const int xb = cw ? static_cast<int>(cw[P.bit_pos[i]]) : 0;
+                    if (awgn)
+                    {
+                        const double noise = static_cast<double>(pick_normal(p0, p1, k)) * a.sigma + 0.0;
+                        const double xs = cw ? static_cast<double>(1 - 2 * xb) : 1.0;
+                        const double y = noise + xs;
+                        llr[P.tx_rank[i]] = 2 * y / a.sigma2;
+                    }
+                    else
+                    {
+                        const int y = xb ^ (counter_hit(word_of(w, k), a.eps) ? 1 : 0);
+                        llr[P.tx_rank[i]] = a.delta * static_cast<double>(1 - 2 * y);
+                    }
+                }
+            }
+            finish_kinds();
+        }
+        else if (a.mode == kModeAwgn)
         {
             // normal g of the stream is element (g & 1) of accepted polar pair g >> 1:
             // element 0 = y*mult, element 1 = x*mult (libstdc++ returns y first and saves x; channel.cpp:62-68)
@@ -182,7 +216,7 @@ __device__ __forceinline__ void channel_init(const DecodeArgs &a, uint64_t frame
 // index of the node's bit among the transmitted ones or a kVnSrc* code, rows 24.. = its column.  Same arithmetic, same
 // values as channel_init.  (The columns are fetched only where they are needed — given LLRs, a transmitted codeword — and
 // the indices only where they are: every word held across the loads is a register the headline kernel does not have.)
-template <int VNB>
+template <int VNB, int NK = kNoiseStream>
 __device__ __forceinline__ void channel_lanes(const DecodeArgs &a, uint64_t frame, const uint32_t *pk, double (&L)[VNB + 1])
 {
     const DevPlan &P = a.plan;
@@ -214,6 +248,36 @@ __device__ __forceinline__ void channel_lanes(const DecodeArgs &a, uint64_t fram
         xb[w] = 0;
         if (cw && src[w] < kVnSrcShortened)
             xb[w] = static_cast<int>(cw[pk[(24 + w) * kWaveSize]]); // (bit_pos[i] is the node's column)
+    }
+    if (counter_mode<NK>(a))
+    {
+        // counter-based noise (device_philox.hpp): the Philox block of each of the lane's transmitted bits
+        const bool awgn = a.mode == kModeAwgnCtr;
+        const uint64_t f = a.ctr_frame0 + frame;
+#pragma unroll 1
+        for (int w = 0; w < VNB; ++w)
+        {
+            if (src[w] == kVnSrcShortened)
+                L[w] = a.shorten_llr;
+            else if (src[w] != kVnSrcZero)
+            {
+                const uint4 blk = philox_block(a.ctr_key[0], a.ctr_key[1], f, src[w] >> 2, awgn ? kTagAwgn : kTagDraw);
+                const int k = static_cast<int>(src[w] & 3u);
+                if (awgn)
+                {
+                    const double noise = static_cast<double>(counter_normal(blk, k)) * a.sigma + 0.0;
+                    const double xs = cw ? static_cast<double>(1 - 2 * xb[w]) : 1.0;
+                    const double y = noise + xs;
+                    L[w] = 2 * y / a.sigma2;
+                }
+                else
+                {
+                    const int y = xb[w] ^ (counter_hit(word_of(blk, k), a.eps) ? 1 : 0);
+                    L[w] = a.delta * static_cast<double>(1 - 2 * y);
+                }
+            }
+        }
+        return;
     }
     if (a.mode == kModeAwgn)
     {

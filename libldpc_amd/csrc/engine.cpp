@@ -976,7 +976,8 @@ void Engine::run_bsc(DecodeArgs &a, const DecParams &p, const BatchOut &out, uin
     noise_raw_release(raw_buffer, stream);
 }
 
-void Engine::run_bec(const DecParams &p, const BatchOut &out, uint64_t n, const uint8_t *codeword, uint64_t raw_first, void *stream)
+void Engine::run_bec(const DecParams &p, const BatchOut &out, uint64_t n, const uint8_t *codeword, uint64_t raw_first, void *stream,
+                     const uint64_t *ctr_frame0)
 {
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t nc = plan_.nc;
@@ -990,8 +991,15 @@ void Engine::run_bec(const DecParams &p, const BatchOut &out, uint64_t n, const 
     a.early_term = p.early_term;
     a.deg1_compat = bec_deg1_compat;
     a.n_frames = n;
-    int raw_buffer = 0;
-    a.raw = noise_raw_async(raw_first, n * nct, stream, raw_buffer);
+    int raw_buffer = -1;
+    if (ctr_frame0)
+    {
+        a.counter = 1;
+        a.ctr_key[0] = static_cast<uint32_t>(ctr_seed_), a.ctr_key[1] = static_cast<uint32_t>(ctr_seed_ >> 32);
+        a.ctr_frame0 = *ctr_frame0;
+    }
+    else
+        a.raw = noise_raw_async(raw_first, n * nct, stream, raw_buffer);
     a.eps = x_;
     a.codeword = codeword;
     a.iters = st.route(out.iters, stage_iters_, 4 * n);
@@ -1111,6 +1119,65 @@ const uint8_t *Engine::encode_frames_sharded(Comm &comm, uint64_t before, uint64
     return cw;
 }
 
+const uint8_t *Engine::encode_frames_counter(uint64_t frame0, uint64_t n, void *stream)
+{
+    if (!code_->has_G() || n == 0)
+        return nullptr;
+    const int kc = code_->kc();
+    if (kc <= 0 || code_->G.rows > kc)
+        throw std::runtime_error("generator matrix does not match the code (rows > nc - mc)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t nc = plan_.nc;
+    EncodeArgs e{};
+    e.nc = static_cast<int>(nc);
+    e.kc = kc;
+    e.words = (kc + 63) / 64;
+    e.g_col_ptr = g_col_ptr_;
+    e.g_col_row = g_col_row_;
+    e.g_mask = g_mask_;
+    e.g_cols = code_->G.cols;
+    // the info words of the frames are the "prefixes" of the codeword launch, joined to an all-zero running codeword: u_f G
+    e.prefix = static_cast<uint64_t *>(enc_prefix_.reserve(8 * n * e.words));
+    check(launch_encode_info_counter(ctr_seed_, frame0, n, kc, e.words, e.prefix, s), "encode (counter info words)");
+    if (!cw_zero_.get() || cw_zero_.size() < nc)
+        check(hipMemsetAsync(cw_zero_.reserve(nc), 0, nc, s), "codeword zero");
+    e.cw_prev = static_cast<const uint8_t *>(cw_zero_.get());
+    e.codeword = static_cast<uint8_t *>(cw_frames_.reserve(n * nc));
+    e.cw_last = static_cast<uint8_t *>(cw_next_.reserve(nc));
+    e.n_frames = n;
+    check(launch_encode_codewords(e, s, false), "encode (counter codewords)");
+    return e.codeword;
+}
+
+void Engine::run_counter(const DecParams &p, const BatchOut &out, uint64_t frame0, uint64_t n, void *stream)
+{
+    if (fast_mode)
+        throw std::runtime_error("counter-based noise does not combine with the non-parity fast modes (set_fast_mode(0) first)");
+    const uint8_t *cw = encode_frames_counter(frame0, n, stream);
+    if (chan_ == kBec)
+    {
+        run_bec(p, out, n, cw, 0, stream, &frame0);
+        return;
+    }
+    DecodeArgs a{};
+    a.codeword = cw;
+    a.ctr_key[0] = static_cast<uint32_t>(ctr_seed_), a.ctr_key[1] = static_cast<uint32_t>(ctr_seed_ >> 32);
+    a.ctr_frame0 = frame0;
+    if (chan_ == kAwgn)
+    {
+        a.mode = kModeAwgnCtr;
+        a.sigma = sigma_, a.sigma2 = sigma2_, a.inv_sigma2 = 1.0 / sigma2_;
+        a.shorten_llr = 99999.9; // channel.cpp:83
+    }
+    else
+    {
+        a.mode = kModeBscCtr;
+        a.eps = x_, a.delta = delta_;
+        a.shorten_llr = delta_; // channel.cpp:152
+    }
+    run_decode(a, p, out, n, stream);
+}
+
 void Engine::decode_llr(const DecParams &p, uint64_t n, const double *llr_in, const BatchOut &out, void *stream)
 {
     if (n == 0)
@@ -1156,7 +1223,7 @@ void Engine::decode_llr(const DecParams &p, uint64_t n, const double *llr_in, co
 
 void Engine::stream_rewind_encoder(uint64_t frames_back, void *stream)
 {
-    if (!code_->has_G() || frames_back == 0)
+    if (!code_->has_G() || frames_back == 0 || counter_) // (counter-based noise: a codeword depends on its frame index alone)
         return;
     if (frames_back > last_enc_n_)
         throw std::runtime_error("stream_rewind_encoder: more frames than the last batch held");
@@ -1177,6 +1244,8 @@ void Engine::stream_begin(int channel, uint64_t seed, double x, bool fresh)
     if (channel != kAwgn && channel != kBsc && channel != kBec)
         throw std::runtime_error("No channel selected.");
     chan_ = channel;
+    counter_ = noise_mode == 1;
+    ctr_seed_ = seed;
     // jump-ahead in four thread groups where its latency counts: the erasure channel (its bit-sliced decoder leaves the noise
     // chain on the critical path) and beside the register-resident decoders (rng_kernels.hip, mt_jump_kernel)
     noise_.st.set_jump_groups(channel == kBec || register_resident() ? 4 : 1);
@@ -1392,6 +1461,8 @@ void Engine::awgn_prepare(uint64_t n, DecodeArgs &a, void *stream, bool write_no
 // raw 64-bit draws consumed from the noise stream since stream_begin (what orc_chan_raw_draws counts)
 uint64_t Engine::stream_raw_draws()
 {
+    if (counter_)
+        throw std::runtime_error("stream_raw_draws: counter-based noise draws from no stream (ldpc_hip_set_noise)");
     if (chan_ != kAwgn)
         return raw_next_;
     if (stream_mode_ == 2)
@@ -1449,6 +1520,11 @@ void Engine::stream_skip(uint64_t n_frames, void *stream)
     if (stream_mode_ == 2)
         throw std::runtime_error("stream_skip after stream_decode_sharded on the same stream: call stream_begin first");
     stream_mode_ = 1;
+    if (counter_) // (a frame's noise and codeword depend on its index alone)
+    {
+        frame_pos_ += n_frames;
+        return;
+    }
     upload_plan();
     const uint64_t nct = static_cast<uint64_t>(plan_.nct);
     while (n_frames)
@@ -1484,6 +1560,13 @@ void Engine::stream_decode(const DecParams &p, uint64_t n_frames, const BatchOut
     {
         const uint64_t n = std::min<uint64_t>(n_frames - done, sub);
         const BatchOut o = out.at(done, nc);
+        if (counter_)
+        {
+            run_counter(p, o, frame_pos_, n, stream);
+            frame_pos_ += n;
+            done += n;
+            continue;
+        }
         const uint8_t *cw = encode_frames(n, true, stream);
         DecodeArgs a{};
         a.codeword = cw;
@@ -1536,6 +1619,8 @@ uint64_t Engine::shard_capacity(uint64_t target_frames, int world) const
     world = std::max(world, 1);
     const uint64_t nct = static_cast<uint64_t>(plan_.nct);
     const uint64_t even = (std::max<uint64_t>(target_frames, 1) + world - 1) / world; // BSC / BEC: even split
+    if (counter_)
+        return even; // (counter-based noise: every channel splits evenly)
     // AWGN: a frame belongs to the rank whose piece holds its first pair; a piece of m chunks holds at most m * chunk_trials
     // pairs (every trial accepted), i.e. at most that many / (nct / 2) frame starts — a bound, not a statistical estimate
     const ShardGeometry g = shard_geometry(target_frames, world, nct, noise_.st.chunk_trials(), noise_.st.chunk_blocks());
@@ -1545,7 +1630,7 @@ uint64_t Engine::shard_capacity(uint64_t target_frames, int world) const
 
 void Engine::encoder_snapshot(void *stream)
 {
-    if (!code_->has_G())
+    if (!code_->has_G() || counter_)
         return;
     bind_device();
     const size_t nc = plan_.nc;
@@ -1558,7 +1643,7 @@ void Engine::encoder_snapshot(void *stream)
 
 void Engine::encoder_restore_and_skip(uint64_t frames, void *stream)
 {
-    if (!code_->has_G())
+    if (!code_->has_G() || counter_)
         return;
     bind_device();
     const size_t nc = plan_.nc;
@@ -1588,11 +1673,27 @@ Engine::ShardStep Engine::stream_decode_sharded(Comm &comm, const DecParams &p, 
     if (stream_mode_ == 1)
         throw std::runtime_error("stream_decode_sharded after stream_decode on the same stream: call stream_begin first");
     stream_mode_ = 2;
-    if (chan_ != kAwgn && !failed_before)
+    if ((chan_ != kAwgn || counter_) && !failed_before)
         upload_plan();
     ShardStep st;
     st.step_first = frame_pos_;
     DecodeArgs a{};
+    if (counter_)
+    {
+        // counter-based noise: an even split of the step, nothing exchanged (the encoder's codewords included)
+        if (failed_before)
+            throw std::runtime_error(*failed_before);
+        if (cap > max_sub_batch())
+            throw std::runtime_error("sharded step too large for one launch per rank");
+        st.step_frames = target_frames;
+        const uint64_t base = target_frames / R, extra = target_frames % R;
+        st.n = base + (static_cast<uint64_t>(r) < extra ? 1 : 0);
+        st.first = st.step_first + base * r + std::min<uint64_t>(r, extra);
+        if (st.n)
+            run_counter(p, out, st.first, st.n, stream);
+        frame_pos_ = st.step_first + st.step_frames;
+        return st;
+    }
     if (chan_ == kAwgn)
     {
         // The step: world * m whole chunks of the raw stream.  Rank r generates chunks [base + r m, base + (r+1) m) and the

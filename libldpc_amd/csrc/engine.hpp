@@ -205,6 +205,9 @@ class Engine
     // opt-in NON-PARITY modes, off (0) by default and never chosen by the library: 1 = flooding sum-product with binary32
     // messages (kernels_fast.hip); 2 / 3 = LAYERED sum-product with binary32 / binary16 messages (kernels_layered.hip)
     int fast_mode = 0;
+    // noise of the stream interface (include/ldpc_amd.h, LDPC_HIP_NOISE_*): 0 = the reference's mt19937_64 stream (parity),
+    // 1 = counter-based Philox4x32-10 of (seed, frame, bit), NON-PARITY (device_philox.hpp); stream_begin latches it
+    int noise_mode = 0;
 
     // ---- decode given LLRs (C-ABI decode(), shared.cpp:47-65, batched) ----
     void decode_llr(const DecParams &p, uint64_t n, const double *llr_in, const BatchOut &out, void *stream);
@@ -243,6 +246,7 @@ class Engine
     // frames a sharded step of about target_frames can put on one rank (the output buffers' size)
     uint64_t shard_capacity(uint64_t target_frames, int world) const;
     uint64_t noise_jump_tasks() const { return noise_.st.jump_tasks(); }
+    bool counter_noise() const { return counter_; }
 
     void synchronize(void *stream);
     uint64_t max_sub_batch() const; // frames one launch takes; larger requests are split
@@ -267,7 +271,9 @@ class Engine
     void run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, uint64_t n, void *stream);
     // BSC / BEC: the batch reads the noise stream's raw draws from word `raw_first` on
     void run_bsc(DecodeArgs &a, const DecParams &p, const BatchOut &out, uint64_t n, uint64_t raw_first, void *stream);
-    void run_bec(const DecParams &p, const BatchOut &out, uint64_t n, const uint8_t *codeword, uint64_t raw_first, void *stream);
+    // (ctr_frame0: counter-based noise, the stream index of the batch's frame 0; raw_first is then unused)
+    void run_bec(const DecParams &p, const BatchOut &out, uint64_t n, const uint8_t *codeword, uint64_t raw_first, void *stream,
+                 const uint64_t *ctr_frame0 = nullptr);
     // after a batch's last launch: the noise buffer it read released (-1: none), the codewords and the staged outputs delivered
     void finish_batch(OutStage &st, const BatchOut &out, uint64_t n, const uint8_t *codeword, int noise_buffer, void *stream);
     // normals of frames [frame_pos_, frame_pos_ + n): generate, count, place (write_normals false: count only, stream_skip)
@@ -302,6 +308,11 @@ class Engine
     // both: G checked against the code (and, sharded, against the exchange's size), the running codeword (zeroed when not
     // valid) and its copy for stream_rewind_encoder; returns the running codeword
     uint8_t *encoder_prologue(uint64_t frames_kept, bool sharded, void *stream);
+    // counter-based noise: the codewords u_f G of frames [frame0, frame0 + n) from their own info words (tag 2), no running
+    // state (nullptr when no G is loaded)
+    const uint8_t *encode_frames_counter(uint64_t frame0, uint64_t n, void *stream);
+    // counter-based noise: the channel of frames [frame0, frame0 + n) computed inside the decode launch (fast modes refused)
+    void run_counter(const DecParams &p, const BatchOut &out, uint64_t frame0, uint64_t n, void *stream);
 
     std::unique_ptr<LdpcCode> code_;
     Plan plan_;
@@ -326,6 +337,9 @@ class Engine
     int chan_ = 0;
     double x_ = 0, sigma2_ = 0, sigma_ = 0, delta_ = 0;
     uint64_t frame_pos_ = 0;
+    bool counter_ = false;    // counter-based noise latched by stream_begin (noise_mode == 1)
+    uint64_t ctr_seed_ = 0;   // ... and its Philox key (seed & 0xFFFFFFFF, seed >> 32)
+    DeviceBuffer cw_zero_;    // counter-mode encoder: an all-zero running codeword
     int stream_mode_ = 0; // 0 fresh, 1 stream_decode / stream_skip, 2 stream_decode_sharded (pair bookkeeping differs)
     uint64_t raw_next_ = 0;  // BSC / BEC: raw draws consumed so far
     // AWGN, one rank reading the stream front to back: the pair with stream index cur_pair_ (= first normal of the next

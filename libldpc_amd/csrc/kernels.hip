@@ -1121,7 +1121,7 @@ __device__ __forceinline__ bool decode_body(const DecodeArgs &a, const uint32_t 
     if constexpr (kLaneChannel)
     {
         const uint32_t *lane_pk = P.vn_packed + (static_cast<uint32_t>(wave) * kVnPackedRows) * kWaveSize + lane;
-        channel_lanes<VNB>(a, frame, lane_pk, my_llr);
+        channel_lanes<VNB, kNoiseAny>(a, frame, lane_pk, my_llr);
         // the slot indices now: their loads fly while the LLRs below become lambda (issued before the channel's loads they
         // would sit in fifteen registers across them, which the kernels at 96 do not have)
         pick_up_indices();
@@ -1135,7 +1135,7 @@ __device__ __forceinline__ bool decode_body(const DecodeArgs &a, const uint32_t 
         }
     }
     else
-        channel_init<kThreads>(a, frame, llr, tid);
+        channel_init<kThreads, kNoiseAny>(a, frame, llr, tid);
 #ifdef LDPC_AMD_PHASE_TRACE
     const uint64_t tr_chan0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -1814,7 +1814,7 @@ __global__ __launch_bounds__(kThreads) void bec_kernel(const BecArgs a)
     if (tid == 0)
         misc[0] = 0;
     // ---- channel: channel.cpp:199-229 ----
-    if (a.raw)
+    if (a.raw || a.counter)
     {
         for (int r = tid; r < nc; r += kThreads)
         {
@@ -1830,12 +1830,31 @@ __global__ __launch_bounds__(kThreads) void bec_kernel(const BecArgs a)
             else if (k == 3)
                 sym[r] = 0; // never written by the channel: the decoder's initial zero, a known 0 bit
         }
-        const uint64_t *raw = a.raw + frame * static_cast<uint64_t>(nct);
-        for (int i = tid; i < nct; i += kThreads)
+        if (a.counter) // counter-based noise (device_philox.hpp): a thread takes the four transmitted bits of a Philox block
         {
-            bool erased = canonical(raw[i]) < a.eps;
-            uint8_t xb = cw ? cw[P.bit_pos[i]] : 0;
-            sym[P.tx_rank[i]] = erased ? kErasure : xb;
+            for (int b = tid; 4 * b < nct; b += kThreads)
+            {
+                const uint4 w = philox_block(a.ctr_key[0], a.ctr_key[1], a.ctr_frame0 + frame, static_cast<uint32_t>(b), kTagDraw);
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                {
+                    const int i = 4 * b + k;
+                    if (i >= nct)
+                        break;
+                    const uint8_t xb = cw ? cw[P.bit_pos[i]] : 0;
+                    sym[P.tx_rank[i]] = counter_hit(word_of(w, k), a.eps) ? kErasure : xb;
+                }
+            }
+        }
+        else
+        {
+            const uint64_t *raw = a.raw + frame * static_cast<uint64_t>(nct);
+            for (int i = tid; i < nct; i += kThreads)
+            {
+                bool erased = canonical(raw[i]) < a.eps;
+                uint8_t xb = cw ? cw[P.bit_pos[i]] : 0;
+                sym[P.tx_rank[i]] = erased ? kErasure : xb;
+            }
         }
     }
     else

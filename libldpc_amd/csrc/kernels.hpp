@@ -38,6 +38,9 @@ enum ChannelMode : int
     kModeLlr = 0,  // LLRs given per frame (C-ABI decode, shared.cpp:47-65)
     kModeAwgn = 1, // fused channel_awgn::simulate + calculate_llrs (channel.cpp:62-93)
     kModeBsc = 2,  // fused channel_bsc (channel.cpp:129-162)
+    // opt-in NON-PARITY counter-based noise (device_philox.hpp): the frame's noise from (ctr_key, ctr_frame0 + frame, bit)
+    kModeAwgnCtr = 3, // AWGN normals
+    kModeBscCtr = 4,  // BSC draws
 };
 
 struct DecodeArgs
@@ -99,6 +102,9 @@ struct DecodeArgs
     double *ws_handover;
     int handover_llr; // ws_handover holds the c2v messages as LLRs already (the fused form's hand-over), not as lambda
     uint64_t *phase_trace; // debug builds with -DLDPC_AMD_PHASE_TRACE only: [2048 frames of mid-launch][4 waves][8 values]
+    // kModeAwgnCtr / kModeBscCtr: Philox key (seed & 0xFFFFFFFF, seed >> 32) and the stream index of the batch's frame 0
+    uint32_t ctr_key[2];
+    uint64_t ctr_frame0;
 };
 
 // device copy of RegPlan (register-resident decoder, kernels_reg.hip)
@@ -171,6 +177,10 @@ struct BecArgs
     double *llr_out;     // symbol values 0, 1, 'E' widened to double
     double *llr_in_dump;
     uint8_t *ws;         // per-frame state in device memory (codes whose nnz + 2 nc bytes exceed LDS), else nullptr
+    // counter-based noise (device_philox.hpp; raw == nullptr, symbols == nullptr): erasures from (ctr_key, ctr_frame0 + frame, bit)
+    int counter;
+    uint32_t ctr_key[2];
+    uint64_t ctr_frame0;
 };
 
 // erasure decoder, 64 frames per workgroup (kernels_bec.hip); launch_bec (kernels.hip) takes it when the code fits
@@ -299,6 +309,14 @@ int launch_encode(const EncodeArgs &a, void *stream);
 // codewords of the batch (only_last: just cw_last, from the batch's last prefix)
 int launch_encode_prefix(const EncodeArgs &a, void *stream);
 int launch_encode_codewords(const EncodeArgs &a, void *stream, bool only_last);
+
+// ---- counter-based noise (device_philox.hpp, counter_kernels.hip) ----
+// raw Philox4x32-10 words of blocks [first_block, first_block + n_blocks) of `frame` under `tag`: out[4 i + k] = word k of
+// block first_block + i (device pointer)
+int launch_philox(uint64_t seed, uint32_t tag, uint64_t frame, uint32_t first_block, uint64_t n_blocks, uint32_t *out, void *stream);
+// the info words of frames [frame0, frame0 + n) in counter mode, packed as EncodeArgs::prefix expects them: prefix[f][w] =
+// info bits 64 w .. 64 w + 63 of frame frame0 + f (bits from kc on zero)
+int launch_encode_info_counter(uint64_t seed, uint64_t frame0, uint64_t n, int kc, int words, uint64_t *prefix, void *stream);
 
 // {frames, frame errors, bit errors, iterations, early stops} of a batch (all device pointers), one launch
 int launch_batch_counters(const uint32_t *iters, const uint32_t *bit_errors, uint64_t n, uint32_t max_iters, int early_term,

@@ -29,6 +29,7 @@
 #include <utility>
 
 #include "device_math.hpp"
+#include "device_philox.hpp"
 #include "kernels.hpp"
 
 namespace ldpc_amd
@@ -66,8 +67,9 @@ __device__ __forceinline__ word_t slice(int nf, word_t valid, F bit_of_frame)
     return w & valid;
 }
 
-// (pinned at six waves per SIMD: three groups of eight waves per CU is what the LDS allows as well)
-__global__ __launch_bounds__(kBecThreads) __attribute__((amdgpu_waves_per_eu(6, 6))) void bec_sliced_kernel(const BecArgs a)
+// CTR: the counter-based noise mode's instantiation (device_philox.hpp; the parity kernel keeps exactly its own code)
+template <bool CTR>
+__device__ __forceinline__ void bec_sliced_body(const BecArgs &a)
 {
     extern __shared__ word_t ldsw[];
     __shared__ word_t still[2];
@@ -101,7 +103,7 @@ __global__ __launch_bounds__(kBecThreads) __attribute__((amdgpu_waves_per_eu(6, 
         X[r] = x;
         LE[r] = 0;
     }
-    if (a.raw)
+    if (a.raw || CTR)
     {
         for (int r = tid; r < nc; r += kBecThreads)
         {
@@ -123,19 +125,53 @@ __global__ __launch_bounds__(kBecThreads) __attribute__((amdgpu_waves_per_eu(6, 
             } // k == 3: never written by the channel: the decoder's initial zero, a known 0 bit
             SE[r] = se, LV[r] = sv;
         }
-        const uint64_t *raw = a.raw + f0 * static_cast<uint64_t>(nct);
-        for (int i = tid; i < nct; i += kBecThreads)
+        if constexpr (CTR)
         {
-            word_t xb = 0;
-            const double eps = a.eps;
-            const word_t se = slice(nf, valid, [&](int f) { return canonical(raw[static_cast<size_t>(f) * nct + i]) < eps; });
-            if (cw)
+            // counter-based noise (device_philox.hpp): a thread takes the four transmitted bits of a Philox block, for each of
+            // the group's frames one block
+            for (int b = tid; 4 * b < nct; b += kBecThreads)
             {
-                const uint8_t *c = cw + P.bit_pos[i];
-                xb = slice(nf, valid, [&](int f) { return c[static_cast<size_t>(f) * nc] != 0; });
+                word_t se[4] = {0, 0, 0, 0};
+                for (int f = 0; f < nf; ++f)
+                {
+                    const uint4 w = philox_block(a.ctr_key[0], a.ctr_key[1], a.ctr_frame0 + f0 + f, static_cast<uint32_t>(b), kTagDraw);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        se[k] |= static_cast<word_t>(counter_hit(word_of(w, k), a.eps) ? 1 : 0) << f;
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                {
+                    const int i = 4 * b + k;
+                    if (i >= nct)
+                        break;
+                    word_t xb = 0;
+                    if (cw)
+                    {
+                        const uint8_t *c = cw + P.bit_pos[i];
+                        xb = slice(nf, valid, [&](int f) { return c[static_cast<size_t>(f) * nc] != 0; });
+                    }
+                    const uint32_t r = P.tx_rank[i];
+                    SE[r] = se[k], LV[r] = xb & ~se[k];
+                }
             }
-            const uint32_t r = P.tx_rank[i];
-            SE[r] = se, LV[r] = xb & ~se;
+        }
+        else
+        {
+            const uint64_t *raw = a.raw + f0 * static_cast<uint64_t>(nct);
+            for (int i = tid; i < nct; i += kBecThreads)
+            {
+                word_t xb = 0;
+                const double eps = a.eps;
+                const word_t se = slice(nf, valid, [&](int f) { return canonical(raw[static_cast<size_t>(f) * nct + i]) < eps; });
+                if (cw)
+                {
+                    const uint8_t *c = cw + P.bit_pos[i];
+                    xb = slice(nf, valid, [&](int f) { return c[static_cast<size_t>(f) * nc] != 0; });
+                }
+                const uint32_t r = P.tx_rank[i];
+                SE[r] = se, LV[r] = xb & ~se;
+            }
         }
     }
     else
@@ -450,6 +486,17 @@ __global__ __launch_bounds__(kBecThreads) __attribute__((amdgpu_waves_per_eu(6, 
     }
 }
 
+// (pinned at six waves per SIMD: three groups of eight waves per CU is what the LDS allows as well)
+__global__ __launch_bounds__(kBecThreads) __attribute__((amdgpu_waves_per_eu(6, 6))) void bec_sliced_kernel(const BecArgs a)
+{
+    bec_sliced_body<false>(a);
+}
+
+__global__ __launch_bounds__(kBecThreads) __attribute__((amdgpu_waves_per_eu(6, 6))) void bec_sliced_ctr_kernel(const BecArgs a)
+{
+    bec_sliced_body<true>(a);
+}
+
 } // namespace
 
 uint32_t bec_sliced_lds_bytes(const DevPlan &p)
@@ -471,11 +518,11 @@ int launch_bec_sliced(const BecArgs &a, void *stream)
         return hipSuccess;
     static_assert(sizeof(CnBlock) == 8 && sizeof(VnBlock) == 12, "block descriptors are read as 2 / 3 scalar words");
     const uint32_t lds = bec_sliced_lds_bytes(a.plan);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(bec_sliced_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+    void (*k)(const BecArgs) = a.counter ? bec_sliced_ctr_kernel : bec_sliced_kernel;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
     if (e != hipSuccess)
         return e;
-    hipLaunchKernelGGL(bec_sliced_kernel, dim3(static_cast<unsigned>((a.n_frames + kBecFrames - 1) / kBecFrames)), dim3(kBecThreads), lds,
+    hipLaunchKernelGGL(k, dim3(static_cast<unsigned>((a.n_frames + kBecFrames - 1) / kBecFrames)), dim3(kBecThreads), lds,
                        static_cast<hipStream_t>(stream), a);
     return hipGetLastError();
 }

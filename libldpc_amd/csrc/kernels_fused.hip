@@ -27,6 +27,7 @@
 
 #include "device_cn.hpp"
 #include "device_math.hpp"
+#include "device_philox.hpp"
 #include "fused_rule.h"
 #include "kernels.hpp"
 
@@ -300,7 +301,7 @@ __device__ __forceinline__ AwgnFrame awgn_frame(const DecodeArgs &a, uint64_t fr
 // entry nct = the value of a shortened bit) or per column (given LLRs), spread evenly over the workgroup's threads;
 // put(entry, L) stages what the form keeps of it.  Returns false when the frame's normals cannot be addressed here
 // (awgn_frame).  channel.cpp:62-93 / 129-162, shared.cpp:50-55.
-template <typename Put>
+template <int NK, typename Put>
 __device__ __forceinline__ bool stage_channel(const DecodeArgs &a, const DevFusedPlan &F, uint64_t frame, int tid, Put &&put)
 {
     const DevPlan &P = a.plan;
@@ -323,6 +324,47 @@ __device__ __forceinline__ bool stage_channel(const DecodeArgs &a, const DevFuse
             if (dump)
                 dump[s] = L;
             put(s, L);
+        }
+    }
+    else if (counter_mode<NK>(a))
+    {
+        // counter-based noise (device_philox.hpp): a thread takes the four transmitted bits of a Philox block
+        const bool awgn = a.mode == kModeAwgnCtr;
+        const uint64_t f = a.ctr_frame0 + frame;
+        for (int b = tid; 4 * b < n_stage; b += kThreads)
+        {
+            const uint4 w = philox_block(a.ctr_key[0], a.ctr_key[1], f, static_cast<uint32_t>(b), awgn ? kTagAwgn : kTagDraw);
+            float2 p0{0.f, 0.f}, p1{0.f, 0.f};
+            if (awgn)
+                p0 = box_muller(w.x, w.y), p1 = box_muller(w.z, w.w);
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+            {
+                const int i = 4 * b + k;
+                if (i >= n_stage)
+                    break;
+                int xb = 0, col = 0;
+                if (cw || dump)
+                    col = P.bit_pos[i];
+                if (cw)
+                    xb = static_cast<int>(cw[col]);
+                double L;
+                if (awgn)
+                {
+                    const double noise = static_cast<double>(pick_normal(p0, p1, k)) * a.sigma + 0.0;
+                    const double xs = cw ? static_cast<double>(1 - 2 * xb) : 1.0;
+                    const double y = noise + xs;
+                    L = dm_div_by(2 * y, a.sigma2, a.inv_sigma2);
+                }
+                else
+                {
+                    const int y = xb ^ (counter_hit(word_of(w, k), a.eps) ? 1 : 0);
+                    L = a.delta * static_cast<double>(1 - 2 * y);
+                }
+                if (dump)
+                    dump[col] = L;
+                put(i, L);
+            }
         }
     }
     else if (a.mode == kModeAwgn)
@@ -374,7 +416,7 @@ __device__ __forceinline__ bool stage_channel(const DecodeArgs &a, const DevFuse
 }
 
 // =======================================================================================================================
-template <bool WANT_LLR, int VNB, int CNL, bool EXCL, bool HO = false>
+template <bool WANT_LLR, int VNB, int CNL, bool EXCL, bool HO = false, int NK = kNoiseStream>
 __device__ __forceinline__ void fused_body(const DecodeArgs &a, const DevFusedPlan &F)
 {
     extern __shared__ double lds[];
@@ -406,7 +448,7 @@ __device__ __forceinline__ void fused_body(const DecodeArgs &a, const DevFusedPl
                 t.hmax = 0xFFFFFFFFu; // the frame leaves the ratio form at once
             stage[s] = double2{need_lambda ? dm_exp_clamped(0.0 - L) : 1.0, dm_exp_clamped(L)};
         };
-        if (!stage_channel(a, F, frame, tid, put))
+        if (!stage_channel<NK>(a, F, frame, tid, put))
             t.hmax = 0xFFFFFFFFu;
         if (tid == kThreads - 1)
             stage[n_stage + 1] = double2{1.0, 1.0}; // L = 0: punctured, never written by the channel, no node
@@ -1007,7 +1049,7 @@ __device__ __forceinline__ double vnms_table(char *msg, const uint32_t *tbl, int
     return out;
 }
 
-template <bool WANT_LLR, int VNB, int CNL>
+template <bool WANT_LLR, int VNB, int CNL, int NK = kNoiseStream>
 __device__ __forceinline__ void fused_ms_body(const DecodeArgs &a, const DevFusedPlan &F)
 {
     extern __shared__ double lds[];
@@ -1028,7 +1070,7 @@ __device__ __forceinline__ void fused_ms_body(const DecodeArgs &a, const DevFuse
     const bool given = a.mode == kModeLlr;
     const int n_stage = given ? nc : nct;
     double2 *stage = reinterpret_cast<double2 *>(lds);
-    bool addressed = stage_channel(a, F, frame, tid, [&](int s, double L) { stage[s].x = L; });
+    bool addressed = stage_channel<NK>(a, F, frame, tid, [&](int s, double L) { stage[s].x = L; });
     if (tid == kThreads - 1)
         stage[n_stage + 1].x = 0.0; // punctured, never written by the channel, no node
     const uint32_t *tab = F.lane_tab + (static_cast<uint32_t>(wave) * kFusedLaneRows) * kWaveSize + lane;
@@ -1287,6 +1329,40 @@ __global__ __launch_bounds__(kThreads) void decode_fused_kernel(const DecodeArgs
     fused_body<WANT_LLR, VNB, CNL, false>(a, f);
 }
 
+// ---- the counter-based noise mode's instantiations (device_philox.hpp): the same forms, the prologue computing the
+// frame's noise from its index (the parity kernels above keep exactly their own code) ----
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(LDPC_AMD_FUSED_WAVES, LDPC_AMD_FUSED_WAVES))) void
+decode_ctr_fused_small(const DecodeArgs a, const DevFusedPlan f)
+{
+    fused_body<false, 4, 1, true, false, kNoiseCounter>(a, f);
+}
+
+template <bool WANT_LLR, int VNB, int CNL>
+__global__ __launch_bounds__(kThreads) void decode_ctr_fused_kernel(const DecodeArgs a, const DevFusedPlan f)
+{
+    fused_body<WANT_LLR, VNB, CNL, false, false, kNoiseCounter>(a, f);
+}
+
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(5, 5))) void
+decode_ctr_fused_ho_small(const DecodeArgs a, const DevFusedPlan f)
+{
+    fused_body<false, 4, 1, true, true, kNoiseCounter>(a, f);
+}
+
+template <bool WANT_LLR, int VNB, int CNL>
+__global__ __launch_bounds__(kThreads) void decode_ctr_fused_ho_kernel(const DecodeArgs a, const DevFusedPlan f)
+{
+    fused_body<WANT_LLR, VNB, CNL, false, true, kNoiseCounter>(a, f);
+}
+
+template <bool WANT_LLR, int VNB, int CNL>
+__global__ __launch_bounds__(kThreads) void decode_ctr_fused_ms_kernel(const DecodeArgs a, const DevFusedPlan f)
+{
+    fused_ms_body<WANT_LLR, VNB, CNL, kNoiseCounter>(a, f);
+}
+
+bool counter_args(const DecodeArgs &a) { return a.mode == kModeAwgnCtr || a.mode == kModeBscCtr; }
+
 } // namespace
 
 int launch_decode_fused(const DecodeArgs &a, const DevFusedPlan &f, void *stream)
@@ -1303,6 +1379,15 @@ int launch_decode_fused(const DecodeArgs &a, const DevFusedPlan &f, void *stream
         k = (want_llr || !f.wide_exclusive) ? (want_llr ? decode_fused_kernel<true, 4, 1> : decode_fused_kernel<false, 4, 1>) : decode_fused_small;
     else
         k = want_llr ? decode_fused_kernel<true, kFusedVnSlots, kFusedLeafCalls> : decode_fused_kernel<false, kFusedVnSlots, kFusedLeafCalls>;
+    if (counter_args(a))
+    {
+        if (f.vnb <= 4 && f.cnl <= 1)
+            k = (want_llr || !f.wide_exclusive) ? (want_llr ? decode_ctr_fused_kernel<true, 4, 1> : decode_ctr_fused_kernel<false, 4, 1>)
+                                                : decode_ctr_fused_small;
+        else
+            k = want_llr ? decode_ctr_fused_kernel<true, kFusedVnSlots, kFusedLeafCalls>
+                         : decode_ctr_fused_kernel<false, kFusedVnSlots, kFusedLeafCalls>;
+    }
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(f.lds_bytes));
     if (e != hipSuccess)
         return e;
@@ -1324,6 +1409,15 @@ int launch_decode_fused_handover(const DecodeArgs &a, const DevFusedPlan &f, voi
         k = (want_llr || !f.wide_exclusive) ? (want_llr ? decode_fused_ho_kernel<true, 4, 1> : decode_fused_ho_kernel<false, 4, 1>) : decode_fused_ho_small;
     else
         k = want_llr ? decode_fused_ho_kernel<true, kFusedVnSlots, kFusedLeafCalls> : decode_fused_ho_kernel<false, kFusedVnSlots, kFusedLeafCalls>;
+    if (counter_args(a))
+    {
+        if (f.vnb <= 4 && f.cnl <= 1)
+            k = (want_llr || !f.wide_exclusive) ? (want_llr ? decode_ctr_fused_ho_kernel<true, 4, 1> : decode_ctr_fused_ho_kernel<false, 4, 1>)
+                                                : decode_ctr_fused_ho_small;
+        else
+            k = want_llr ? decode_ctr_fused_ho_kernel<true, kFusedVnSlots, kFusedLeafCalls>
+                         : decode_ctr_fused_ho_kernel<false, kFusedVnSlots, kFusedLeafCalls>;
+    }
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(f.lds_bytes));
     if (e != hipSuccess)
         return e;
@@ -1345,6 +1439,14 @@ int launch_decode_fused_minsum(const DecodeArgs &a, const DevFusedPlan &f, void 
         k = want_llr ? decode_fused_ms_kernel<true, 4, 1> : decode_fused_ms_kernel<false, 4, 1>;
     else
         k = want_llr ? decode_fused_ms_kernel<true, kFusedVnSlots, kFusedLeafCalls> : decode_fused_ms_kernel<false, kFusedVnSlots, kFusedLeafCalls>;
+    if (counter_args(a))
+    {
+        if (f.vnb <= 4 && f.cnl <= 1)
+            k = want_llr ? decode_ctr_fused_ms_kernel<true, 4, 1> : decode_ctr_fused_ms_kernel<false, 4, 1>;
+        else
+            k = want_llr ? decode_ctr_fused_ms_kernel<true, kFusedVnSlots, kFusedLeafCalls>
+                         : decode_ctr_fused_ms_kernel<false, kFusedVnSlots, kFusedLeafCalls>;
+    }
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(f.lds_bytes));
     if (e != hipSuccess)
         return e;

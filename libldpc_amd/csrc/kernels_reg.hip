@@ -117,7 +117,7 @@ __global__ __launch_bounds__(NT) void decode_reg_kernel(const DecodeArgs a, cons
 
     if (tid == 0)
         misc[0] = 0;
-    channel_init<NT>(a, frame, llr, tid);
+    channel_init<NT, kNoiseAny>(a, frame, llr, tid);
     __syncthreads();
     if (a.llr_in_dump)
     {

@@ -121,7 +121,8 @@ __device__ __forceinline__ Reg2VnBlock load_vn_block(const Reg2VnBlock *table, u
 // degree 6 share reciprocals (detmath.h, dm_cn6_shared: the first of the three attempts a frame may need).  Returns true when
 // the frame left the range of the form — a value outside the box of the ratio form, or a product of denominators beyond its
 // limit — and has to be decoded again from scratch by the next form; nothing of it has been delivered then.
-template <bool MINSUM, bool WANT_LLR, int NT, int KC, int MAXD, int NV0, int NV1, bool RATIO, bool SH6, bool UCN, bool UVN>
+template <bool MINSUM, bool WANT_LLR, int NT, int KC, int MAXD, int NV0, int NV1, bool RATIO, bool SH6, bool UCN, bool UVN,
+          int NK = kNoiseStream>
 __device__ __forceinline__ bool reg2_frame(const DecodeArgs &a, const DevReg2Plan &R_arg, const uint64_t frame, const int wave)
 {
     static_assert(NV0 % 2 == 0 && NV1 % 2 == 0, "variable-node rounds go two blocks at a time");
@@ -145,7 +146,7 @@ __device__ __forceinline__ bool reg2_frame(const DecodeArgs &a, const DevReg2Pla
     uint8_t *hard = a.ws_hb + frame * nc;
     const uint8_t *cw = a.codeword ? a.codeword + frame * nc : nullptr;
 
-    channel_init<NT>(a, frame, llr, tid);
+    channel_init<NT, NK>(a, frame, llr, tid);
     if (tid == 0)
     {
         lds[R.neutral] = 1.0;
@@ -589,8 +590,8 @@ __device__ __forceinline__ bool reg2_frame(const DecodeArgs &a, const DevReg2Pla
 // by one workgroup on an otherwise idle chip — the frames that do not converge at the operating point of BASELINE config 4
 // leave the box of the ratio form after a few dozen iterations, a handful per batch, and cost 0.3 ms per batch that way —
 // while inside the first launch the repeat hides among the other frames.  Which form finishes a frame is the same either way.)
-template <bool MINSUM, bool WANT_LLR, int NT, int KC, int MAXD, int NV0, int NV1, bool CHAIN, bool U>
-__global__ __launch_bounds__(NT) void decode_reg2_kernel(const DecodeArgs a, const DevReg2Plan R)
+template <bool MINSUM, bool WANT_LLR, int NT, int KC, int MAXD, int NV0, int NV1, bool CHAIN, bool U, int NK>
+__device__ __forceinline__ void reg2_kernel_body(const DecodeArgs &a, const DevReg2Plan &R)
 {
     static_assert(!(CHAIN && MINSUM), "the chain is the sum-product decoder's");
     extern __shared__ double lds[];
@@ -601,14 +602,27 @@ __global__ __launch_bounds__(NT) void decode_reg2_kernel(const DecodeArgs a, con
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if constexpr (CHAIN)
     {
-        if (!reg2_frame<false, WANT_LLR, NT, KC, MAXD, NV0, NV1, true, true, U, U>(a, R, frame, wave))
+        if (!reg2_frame<false, WANT_LLR, NT, KC, MAXD, NV0, NV1, true, true, U, U, NK>(a, R, frame, wave))
             return;
         __syncthreads(); // the next attempt re-initialises LDS words this one may still be reading
-        if (!reg2_frame<false, WANT_LLR, NT, KC, MAXD, NV0, NV1, true, false, U, U>(a, R, frame, wave))
+        if (!reg2_frame<false, WANT_LLR, NT, KC, MAXD, NV0, NV1, true, false, U, U, NK>(a, R, frame, wave))
             return;
         __syncthreads();
     }
-    reg2_frame<MINSUM, WANT_LLR, NT, KC, MAXD, NV0, NV1, false, false, U, U>(a, R, frame, wave);
+    reg2_frame<MINSUM, WANT_LLR, NT, KC, MAXD, NV0, NV1, false, false, U, U, NK>(a, R, frame, wave);
+}
+
+template <bool MINSUM, bool WANT_LLR, int NT, int KC, int MAXD, int NV0, int NV1, bool CHAIN, bool U>
+__global__ __launch_bounds__(NT) void decode_reg2_kernel(const DecodeArgs a, const DevReg2Plan R)
+{
+    reg2_kernel_body<MINSUM, WANT_LLR, NT, KC, MAXD, NV0, NV1, CHAIN, U, kNoiseStream>(a, R);
+}
+
+// the counter-based noise mode's instantiation (device_philox.hpp): the same decoder, the frame's noise from its index
+template <bool MINSUM, bool WANT_LLR, int NT, int KC, int MAXD, int NV0, int NV1, bool CHAIN, bool U>
+__global__ __launch_bounds__(NT) void decode_reg2_ctr_kernel(const DecodeArgs a, const DevReg2Plan R)
+{
+    reg2_kernel_body<MINSUM, WANT_LLR, NT, KC, MAXD, NV0, NV1, CHAIN, U, kNoiseCounter>(a, R);
 }
 
 // U: the regular code's instantiation (no switch over check-node degrees, straight-line variable-node rounds), or the
@@ -634,6 +648,18 @@ int launch_reg2(const DecodeArgs &a, const DevReg2Plan &r, bool min_sum, void *s
     else
         k = want_llr ? decode_reg2_kernel<false, true, NT, KC, MAXD, NV0, NV1, false, U>
                      : decode_reg2_kernel<false, false, NT, KC, MAXD, NV0, NV1, false, U>;
+    if (a.mode == kModeAwgnCtr || a.mode == kModeBscCtr)
+    {
+        if (min_sum)
+            k = want_llr ? decode_reg2_ctr_kernel<true, true, NT, KC, MAXD, NV0, NV1, false, U>
+                         : decode_reg2_ctr_kernel<true, false, NT, KC, MAXD, NV0, NV1, false, U>;
+        else if (chain)
+            k = want_llr ? decode_reg2_ctr_kernel<false, true, NT, KC, MAXD, NV0, NV1, true, U>
+                         : decode_reg2_ctr_kernel<false, false, NT, KC, MAXD, NV0, NV1, true, U>;
+        else
+            k = want_llr ? decode_reg2_ctr_kernel<false, true, NT, KC, MAXD, NV0, NV1, false, U>
+                         : decode_reg2_ctr_kernel<false, false, NT, KC, MAXD, NV0, NV1, false, U>;
+    }
     const uint32_t lds = r.lds_entries * 8u + 16u;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        static_cast<int>(lds));

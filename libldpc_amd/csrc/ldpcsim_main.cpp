@@ -8,7 +8,8 @@
 // the batch replaces the OpenMP threads).  Extra flags: --device N (GPU index); --devices LIST (e.g. 0-7 or 0,2,4:
 // one process per listed GPU, forked before anything touches a GPU, the frames of every step shared out over them and
 // the counters exchanged over RCCL — results are those of the one-GPU run; --comm shm puts the exchange on host
-// shared memory instead, for rehearsals with a repeated device such as --devices 0,0); --bec-compat (reproduce the
+// shared memory instead, for rehearsals with a repeated device such as --devices 0,0); --noise counter (NON-PARITY
+// counter-based noise, include/ldpc_amd.h ldpc_hip_set_noise); --bec-compat (reproduce the
 // reference's out-of-bounds read for erased degree-1 variable nodes).
 #include <fcntl.h>
 #include <signal.h>
@@ -53,7 +54,10 @@ const char *kUsage =
     "--device            \tGPU index. (Default: 0)\n"
     "--devices           \tGPUs to share the frames over, one process each: \"0-7\", \"0,1,2\".\n"
     "--comm              \tExchange between those processes: \"rccl\" (default) or \"shm\".\n"
-    "--bec-compat        \tBEC: erased degree-1 variable nodes emit 0 as the reference build does.\n";
+    "--bec-compat        \tBEC: erased degree-1 variable nodes emit 0 as the reference build does.\n"
+    "--noise             \tNoise: \"reference\" (default: the reference's mt19937_64 stream, frame for frame) or\n"
+    "                    \t\"counter\" (counter-based Philox of seed, frame and bit; NON-PARITY: error rates compare\n"
+    "                    \twith the reference only statistically).\n";
 
 std::vector<int> parse_devices(const std::string &spec)
 {
@@ -95,6 +99,7 @@ int main(int argc, char *argv[])
     int device = 0;
     std::vector<int> devices;
     std::string comm_kind = "rccl";
+    std::string noise = "reference";
     try
     {
         for (int i = 1; i < argc; ++i)
@@ -136,6 +141,8 @@ int main(int argc, char *argv[])
                 comm_kind = value();
             else if (a == "--bec-compat")
                 bec_compat = true;
+            else if (a == "--noise")
+                noise = value();
             else if (a.size() > 1 && a[0] == '-' && !(std::isdigit(static_cast<unsigned char>(a[1])) || a[1] == '.'))
                 throw std::runtime_error("Unknown argument: " + a);
             else
@@ -145,6 +152,8 @@ int main(int argc, char *argv[])
             throw std::runtime_error("expected: codefile output-file MIN MAX STEP");
         if (comm_kind != "rccl" && comm_kind != "shm")
             throw std::runtime_error("--comm: rccl or shm");
+        if (noise != "reference" && noise != "counter")
+            throw std::runtime_error("--noise: reference or counter");
     }
     catch (const std::exception &e)
     {
@@ -277,6 +286,12 @@ int main(int argc, char *argv[])
         return reap(EXIT_FAILURE);
     }
     ldpc_hip_set_bec_compat(ctx, bec_compat);
+    if (noise == "counter" && ldpc_hip_set_noise(ctx, LDPC_HIP_NOISE_COUNTER) != 0)
+    {
+        std::cout << "Error: " << ldpc_hip_last_error() << std::endl;
+        ldpc_hip_destroy(ctx);
+        return reap(EXIT_FAILURE);
+    }
     int64_t info[10];
     ldpc_hip_code_info(ctx, info);
 
@@ -291,6 +306,8 @@ int main(int argc, char *argv[])
     std::cout << "== Channel Parameters\n";
     std::cout << " Type: " << channel << "\n Seed: " << seed << "\n Range: Min: " << range[0] << ", Max: " << range[1]
               << ", Step: " << range[2] << "\n";
+    if (noise == "counter")
+        std::cout << " Noise: counter-based (Philox4x32-10 of seed, frame, bit), NON-PARITY\n";
     std::cout << "== Simulation Parameters\n";
     std::cout << " Threads: " << threads << "\n FEC: " << fec << "\n Max Frames: " << max_frames
               << "\n Output File: " << pos[1] << "\n";
