@@ -148,6 +148,23 @@ int ldpc_hip_set_noise(ldpc_hip_ctx *ctx, int mode);
 int ldpc_hip_philox(ldpc_hip_ctx *ctx, uint64_t seed, uint32_t tag, uint64_t frame, uint32_t first_block, uint64_t n_blocks,
                     uint32_t *out, void *hip_stream);
 
+/* Corrected min-sum of "BP_MS" decoding: normalized (scale alpha < 1) and offset (offset beta > 0) min-sum.  NON-PARITY
+   unless (1, 0): the reference has plain min-sum only (decoder.h:17-20).  For check node c and its edge j:
+     m_j   = the smallest |v2c| over the node's other edges (what plain min-sum computes, exactly)
+     s_j   = XOR of the sign bits of the other edges' v2c (a zero carries its sign bit too)
+     t     = fl(alpha * m_j)                 (rounded; no fused multiply-add)
+     r     = fl(t - beta), and +0.0 where r is not greater than +0.0
+     c2v_j = r with sign bit s_j
+   Everything else is BP_MS as it is: v2c initialisation, the variable-node sum in column file order and v2c = out - c2v,
+   the hard decision out <= 0, the syndrome early stop, the iteration counts, bit errors over transmitted positions,
+   puncturing and shortening.  (1, 0) reproduces plain min-sum bit for bit and runs exactly today's kernels.
+   Applies to ldpc_hip_decode_batch, ldpc_hip_stream_decode(_sharded) and ldpc_hip_simulate(_sharded) whenever the call's
+   decoder_param.type is "BP_MS"; sum-product and the BEC ignore it; it combines with LDPC_HIP_NOISE_COUNTER.  Part 1
+   (simulate(), decode(), ...) is plain min-sum always.
+   Valid: 0 < scale <= 1 and 0 <= offset <= 1e6 (NaN and infinities fail).  Takes effect at the next decode call; touches no
+   GPU.  0, or -1 (last_error set; the setting unchanged) for invalid values */
+int ldpc_hip_set_min_sum_correction(ldpc_hip_ctx *ctx, double scale, double offset);
+
 /* decode n frames of given LLRs llr_in[n][nc] (column order, device or host). 0 on success. */
 int ldpc_hip_decode_batch(ldpc_hip_ctx *ctx, decoder_param dec, uint64_t n, const double *llr_in,
                           const ldpc_hip_out *out, void *hip_stream);

@@ -59,6 +59,8 @@ def load_library(path=LIB_PATH):
     L.ldpc_hip_set_fast_mode.argtypes = [vp, i32]
     L.ldpc_hip_set_noise.restype = i32
     L.ldpc_hip_set_noise.argtypes = [vp, i32]
+    L.ldpc_hip_set_min_sum_correction.restype = i32
+    L.ldpc_hip_set_min_sum_correction.argtypes = [vp, ct.c_double, ct.c_double]
     L.ldpc_hip_philox.restype = i32
     L.ldpc_hip_philox.argtypes = [vp, u64, ct.c_uint32, u64, ct.c_uint32, u64, vp, vp]
     L.ldpc_hip_decode_batch.restype = i32
@@ -265,6 +267,13 @@ class HipDecoder:
         if isinstance(m, str):
             m = -1
         self._check(self.lib.ldpc_hip_set_noise(self.ctx, int(m)), f"ldpc_hip_set_noise({mode!r})")
+
+    def set_min_sum_correction(self, scale=1.0, offset=0.0):
+        """Corrected min-sum for every "BP_MS" decode from the next call on: check-node output magnitudes
+        max(fl(fl(scale * m) - offset), +0.0), normalized (scale < 1) and offset (offset > 0) min-sum.  NON-PARITY unless
+        (1, 0), which switches it off (include/ldpc_amd.h).  0 < scale <= 1, 0 <= offset <= 1e6; touches no GPU."""
+        self._check(self.lib.ldpc_hip_set_min_sum_correction(self.ctx, float(scale), float(offset)),
+                    f"ldpc_hip_set_min_sum_correction({scale!r}, {offset!r})")
 
     def philox(self, seed, tag, frame, first_block, n_blocks):
         """The counter mode's raw words, [n_blocks][4] uint32: blocks first_block.. of `frame` under `tag` (0 AWGN, 1 BSC /

@@ -42,7 +42,7 @@ def _stale(target, deps):
 
 
 def _headers():
-    hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".h"))]
+    hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".h", ".inc"))]
     hs.append(os.path.join(os.path.dirname(PKG), "include", "ldpc_amd.h"))
     return hs
 

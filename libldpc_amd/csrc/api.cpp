@@ -281,6 +281,18 @@ int ldpc_hip_set_noise(ldpc_hip_ctx *ctx, int mode)
     });
 }
 
+int ldpc_hip_set_min_sum_correction(ldpc_hip_ctx *ctx, double scale, double offset)
+{
+    return guarded([&] {
+        // (the comparisons are false for NaN: a NaN fails them)
+        if (!(scale > 0.0 && scale <= 1.0) || !(offset >= 0.0 && offset <= 1e6))
+            throw std::runtime_error("ldpc_hip_set_min_sum_correction: need 0 < scale <= 1 and 0 <= offset <= 1e6, got (" +
+                                     std::to_string(scale) + ", " + std::to_string(offset) + ")");
+        ctx->eng->ms_scale = scale;
+        ctx->eng->ms_offset = offset;
+    });
+}
+
 int ldpc_hip_philox(ldpc_hip_ctx *ctx, uint64_t seed, uint32_t tag, uint64_t frame, uint32_t first_block, uint64_t n_blocks,
                     uint32_t *out, void *hip_stream)
 {

@@ -40,9 +40,45 @@ __device__ __forceinline__ void cn_saturated(double (&v)[D], double mu)
         v[j] = dm_sat_llr(sF[j - 1] ^ sB[j + 1], mu, F[j - 1] + B[j + 1]);
 }
 
-template <int D, bool MINSUM>
-__device__ __forceinline__ void cn_core(double (&v)[D])
+// Corrected min-sum (include/ldpc_amd.h, ldpc_hip_set_min_sum_correction; NON-PARITY): the magnitude m of a min-sum
+// output becomes max(fl(fl(scale * m) - offset), +0.0), its sign bit stays.  f(m) = max(fl(fl(scale * m) - offset), 0) is
+// monotone, so f(min over the other edges) == min over the other edges of f(|v|), bit for bit: the correction is applied
+// once to each INPUT of the node (sign bit kept, -0.0 included), and the exact min-sum recursion below does the rest.
+struct MsCorr
 {
+    double scale, offset;
+};
+
+__device__ __forceinline__ double ms_correct(double v, MsCorr c)
+{
+#pragma clang fp contract(off)
+    const double t = __builtin_fabs(v) * c.scale; // rounded: no fused multiply-add with the subtraction
+    double r = t - c.offset;
+    r = r > 0.0 ? r : 0.0;
+    return dm_from_bits(dm_bits(r) | (dm_bits(v) & 0x8000000000000000ull));
+}
+
+// a launch's correction (the kernel arguments' ms_scale / ms_offset) where CORR, else a constant nothing reads
+template <bool CORR, typename Args>
+__device__ __forceinline__ MsCorr ms_corr(const Args &a)
+{
+    if constexpr (CORR)
+        return MsCorr{a.ms_scale, a.ms_offset};
+    else
+        return MsCorr{1.0, 0.0};
+}
+
+// CORR: the corrected min-sum rule (MINSUM only), c its parameters
+template <int D, bool MINSUM, bool CORR = false>
+__device__ __forceinline__ void cn_core(double (&v)[D], MsCorr c = MsCorr{1.0, 0.0})
+{
+    static_assert(!CORR || MINSUM, "the correction is a min-sum rule");
+    if constexpr (CORR)
+    {
+#pragma unroll
+        for (int j = 0; j < D; ++j)
+            v[j] = ms_correct(v[j], c);
+    }
     if constexpr (!MINSUM && D > 2) // a degree-2 node only swaps its two inputs: the generic code below
     {
         // sum-product: saturated form when it applies; else the recursion is carried in E = e^-|L| (detmath.h,

@@ -793,6 +793,9 @@ void Engine::run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, 
     a.hard = st.route(out.hard, stage_hard_, n * nc);
     a.llr_out = st.route(out.llr_out, stage_llr_out_, 8 * n * nc);
     a.llr_in_dump = st.route(out.llr_in, stage_llr_in_, 8 * n * nc);
+    // (1, 0) is plain min-sum: the launches of today, not corrected instantiations that would compute the same
+    a.ms_correct = p.min_sum && !(ms_scale == 1.0 && ms_offset == 0.0);
+    a.ms_scale = ms_scale, a.ms_offset = ms_offset;
     prof_mark(0, s);
     // the caller asked for a non-parity mode (never chosen by itself): one launch, no ratio form
     const bool fast = fast_mode && !p.min_sum;

@@ -208,6 +208,9 @@ class Engine
     // noise of the stream interface (include/ldpc_amd.h, LDPC_HIP_NOISE_*): 0 = the reference's mt19937_64 stream (parity),
     // 1 = counter-based Philox4x32-10 of (seed, frame, bit), NON-PARITY (device_philox.hpp); stream_begin latches it
     int noise_mode = 0;
+    // corrected min-sum of BP_MS decoding (include/ldpc_amd.h, ldpc_hip_set_min_sum_correction), NON-PARITY unless (1, 0):
+    // check-node output magnitudes max(fl(fl(ms_scale * m) - ms_offset), +0.0) (device_cn.hpp, MsCorr); read at every decode
+    double ms_scale = 1.0, ms_offset = 0.0;
 
     // ---- decode given LLRs (C-ABI decode(), shared.cpp:47-65, batched) ----
     void decode_llr(const DecParams &p, uint64_t n, const double *llr_in, const BatchOut &out, void *stream);

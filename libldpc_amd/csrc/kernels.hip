@@ -64,14 +64,14 @@ constexpr int kThreads = kDecodeWaves * kWaveSize;
 constexpr uint8_t kErasure = 'E'; // functions.h:105
 
 // check-node update on the frame's message array: slot(j) = m[j*stride] (decoder.cpp:25-45, device_cn.hpp)
-template <int D, bool MINSUM>
-__device__ __forceinline__ void cn_update(double *m, int stride)
+template <int D, bool MINSUM, bool CORR = false>
+__device__ __forceinline__ void cn_update(double *m, int stride, MsCorr c = MsCorr{1.0, 0.0})
 {
     double v[D];
 #pragma unroll
     for (int j = 0; j < D; ++j)
         v[j] = m[j * stride];
-    cn_core<D, MINSUM>(v);
+    cn_core<D, MINSUM, CORR>(v, c);
 #pragma unroll
     for (int j = 0; j < D; ++j)
         m[j * stride] = v[j];
@@ -188,8 +188,31 @@ __device__ __noinline__ void cn_wide(double *m, double *scr, double *scr2, int s
     m[0] = bk;
 }
 
-template <bool MINSUM, int MAXD>
-__device__ __forceinline__ void cn_block(double *msg, const CnBlock b, int lane, double *scratch = nullptr, double *scratch2 = nullptr)
+// corrected min-sum on a wide node (device_cn.hpp, MsCorr): cn_wide's min-sum recursion with every input passed through
+// ms_correct as it is read (a function of its own: the plain one keeps its call signature)
+__device__ __noinline__ void cn_wide_msc(double *m, double *scr, int stride, int d, MsCorr c)
+{
+    double f = ms_correct(m[0], c);
+    scr[0] = f;
+    for (int j = 1; j <= d - 2; ++j)
+    {
+        f = box_minsum(f, ms_correct(m[j * stride], c));
+        scr[j * stride] = f;
+    }
+    double bk = ms_correct(m[(d - 1) * stride], c);
+    m[(d - 1) * stride] = f;
+    for (int j = d - 2; j >= 1; --j)
+    {
+        const double v = ms_correct(m[j * stride], c);
+        m[j * stride] = box_minsum(scr[(j - 1) * stride], bk);
+        bk = box_minsum(bk, v);
+    }
+    m[0] = bk;
+}
+
+template <bool MINSUM, int MAXD, bool CORR = false>
+__device__ __forceinline__ void cn_block(double *msg, const CnBlock b, int lane, double *scratch = nullptr, double *scratch2 = nullptr,
+                                         MsCorr c = MsCorr{1.0, 0.0})
 {
     if (lane >= b.count)
         return;
@@ -198,23 +221,26 @@ __device__ __forceinline__ void cn_block(double *msg, const CnBlock b, int lane,
     if constexpr (MAXD >= 16)
         if (b.degree > 16) // wave-uniform
         {
-            cn_wide<MINSUM>(m, scratch + b.off + lane, scratch2 + b.off + lane, s, b.degree);
+            if constexpr (CORR)
+                cn_wide_msc(m, scratch + b.off + lane, s, b.degree, c);
+            else
+                cn_wide<MINSUM>(m, scratch + b.off + lane, scratch2 + b.off + lane, s, b.degree);
             return;
         }
     switch (b.degree) // wave-uniform
     {
-    case 2: cn_update<2, MINSUM>(m, s); break;
-    case 3: cn_update<3, MINSUM>(m, s); break;
-    case 4: cn_update<4, MINSUM>(m, s); break;
+    case 2: cn_update<2, MINSUM, CORR>(m, s, c); break;
+    case 3: cn_update<3, MINSUM, CORR>(m, s, c); break;
+    case 4: cn_update<4, MINSUM, CORR>(m, s, c); break;
     default:
         if constexpr (MAXD > 4)
         {
             switch (b.degree)
             {
-            case 5: cn_update<5, MINSUM>(m, s); break;
-            case 6: cn_update<6, MINSUM>(m, s); break;
-            case 7: cn_update<7, MINSUM>(m, s); break;
-            case 8: cn_update<8, MINSUM>(m, s); break;
+            case 5: cn_update<5, MINSUM, CORR>(m, s, c); break;
+            case 6: cn_update<6, MINSUM, CORR>(m, s, c); break;
+            case 7: cn_update<7, MINSUM, CORR>(m, s, c); break;
+            case 8: cn_update<8, MINSUM, CORR>(m, s, c); break;
             default: break;
             }
         }
@@ -222,14 +248,14 @@ __device__ __forceinline__ void cn_block(double *msg, const CnBlock b, int lane,
         {
             switch (b.degree)
             {
-            case 9: cn_update<9, MINSUM>(m, s); break;
-            case 10: cn_update<10, MINSUM>(m, s); break;
-            case 11: cn_update<11, MINSUM>(m, s); break;
-            case 12: cn_update<12, MINSUM>(m, s); break;
-            case 13: cn_update<13, MINSUM>(m, s); break;
-            case 14: cn_update<14, MINSUM>(m, s); break;
-            case 15: cn_update<15, MINSUM>(m, s); break;
-            case 16: cn_update<16, MINSUM>(m, s); break;
+            case 9: cn_update<9, MINSUM, CORR>(m, s, c); break;
+            case 10: cn_update<10, MINSUM, CORR>(m, s, c); break;
+            case 11: cn_update<11, MINSUM, CORR>(m, s, c); break;
+            case 12: cn_update<12, MINSUM, CORR>(m, s, c); break;
+            case 13: cn_update<13, MINSUM, CORR>(m, s, c); break;
+            case 14: cn_update<14, MINSUM, CORR>(m, s, c); break;
+            case 15: cn_update<15, MINSUM, CORR>(m, s, c); break;
+            case 16: cn_update<16, MINSUM, CORR>(m, s, c); break;
             default: break;
             }
         }
@@ -238,8 +264,8 @@ __device__ __forceinline__ void cn_block(double *msg, const CnBlock b, int lane,
 }
 
 // two full blocks (64 nodes each) at once: one LDS round trip for both (min-sum is bound by exactly that latency)
-template <int D0, int D1, bool MINSUM>
-__device__ __forceinline__ void cn_update2(double *m0, double *m1)
+template <int D0, int D1, bool MINSUM, bool CORR = false>
+__device__ __forceinline__ void cn_update2(double *m0, double *m1, MsCorr c = MsCorr{1.0, 0.0})
 {
     double v0[D0], v1[D1];
 #pragma unroll
@@ -248,8 +274,8 @@ __device__ __forceinline__ void cn_update2(double *m0, double *m1)
 #pragma unroll
     for (int j = 0; j < D1; ++j)
         v1[j] = m1[j * kWaveSize];
-    cn_core<D0, MINSUM>(v0);
-    cn_core<D1, MINSUM>(v1);
+    cn_core<D0, MINSUM, CORR>(v0, c);
+    cn_core<D1, MINSUM, CORR>(v1, c);
 #pragma unroll
     for (int j = 0; j < D0; ++j)
         m0[j * kWaveSize] = v0[j];
@@ -259,37 +285,37 @@ __device__ __forceinline__ void cn_update2(double *m0, double *m1)
 }
 
 // returns false when the two degrees have no paired form (the caller then takes the blocks one after the other)
-template <bool MINSUM, int MAXD>
-__device__ __forceinline__ bool cn_pair(double *msg, uint32_t off0, uint32_t off1, int deg0, int deg1, int lane)
+template <bool MINSUM, int MAXD, bool CORR = false>
+__device__ __forceinline__ bool cn_pair(double *msg, uint32_t off0, uint32_t off1, int deg0, int deg1, int lane, MsCorr c = MsCorr{1.0, 0.0})
 {
     double *m0 = msg + off0 + lane, *m1 = msg + off1 + lane;
     if (deg0 == deg1)
     {
         switch (deg0) // wave-uniform
         {
-        case 2: cn_update2<2, 2, MINSUM>(m0, m1); return true;
-        case 3: cn_update2<3, 3, MINSUM>(m0, m1); return true;
-        case 4: cn_update2<4, 4, MINSUM>(m0, m1); return true;
+        case 2: cn_update2<2, 2, MINSUM, CORR>(m0, m1, c); return true;
+        case 3: cn_update2<3, 3, MINSUM, CORR>(m0, m1, c); return true;
+        case 4: cn_update2<4, 4, MINSUM, CORR>(m0, m1, c); return true;
         default: break;
         }
         if constexpr (MAXD > 4)
             switch (deg0)
             {
-            case 5: cn_update2<5, 5, MINSUM>(m0, m1); return true;
-            case 6: cn_update2<6, 6, MINSUM>(m0, m1); return true;
-            case 7: cn_update2<7, 7, MINSUM>(m0, m1); return true;
-            case 8: cn_update2<8, 8, MINSUM>(m0, m1); return true;
+            case 5: cn_update2<5, 5, MINSUM, CORR>(m0, m1, c); return true;
+            case 6: cn_update2<6, 6, MINSUM, CORR>(m0, m1, c); return true;
+            case 7: cn_update2<7, 7, MINSUM, CORR>(m0, m1, c); return true;
+            case 8: cn_update2<8, 8, MINSUM, CORR>(m0, m1, c); return true;
             default: break;
             }
     }
     else if (deg0 == 4 && deg1 == 3) // each wave's list is in descending degree order (plan.cpp)
     {
-        cn_update2<4, 3, MINSUM>(m0, m1);
+        cn_update2<4, 3, MINSUM, CORR>(m0, m1, c);
         return true;
     }
     else if (deg0 == 3 && deg1 == 2)
     {
-        cn_update2<3, 2, MINSUM>(m0, m1);
+        cn_update2<3, 2, MINSUM, CORR>(m0, m1, c);
         return true;
     }
     return false;
@@ -1007,7 +1033,7 @@ constexpr int kMaxVnBlocksInRegs = 8;
 // CHAIN (decode_kernel_list): the frame is entry `slot` of a.redo_list_in (the caller has checked the count); a frame that leaves
 // the ratio form's range is not appended to a list: the function returns true and the caller goes on to the next form.
 template <bool MINSUM, bool WANT_LLR, bool LDS_RESIDENT, int MAXD, int LLR_MODE, bool RATIO, bool HANDOVER = false, bool SEPARATE = false,
-          int VNB = kMaxVnBlocksInRegs, bool CHAIN = false>
+          int VNB = kMaxVnBlocksInRegs, bool CHAIN = false, bool CORR = false>
 __device__ __forceinline__ bool decode_body(const DecodeArgs &a, const uint32_t slot)
 {
     static_assert(VNB >= 1 && VNB <= kMaxVnBlocksInRegs, "register-held VN blocks");
@@ -1056,6 +1082,7 @@ __device__ __forceinline__ bool decode_body(const DecodeArgs &a, const uint32_t 
     }
     [[maybe_unused]] double *scratch = (!LDS_RESIDENT && a.ws_scr) ? a.ws_scr + frame * 2 * nnz : nullptr; // cn_wide
     [[maybe_unused]] double *scratch2 = scratch ? scratch + nnz : nullptr;
+    [[maybe_unused]] const MsCorr corr{a.ms_scale, a.ms_offset}; // CORR only
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -1511,12 +1538,12 @@ __device__ __forceinline__ bool decode_body(const DecodeArgs &a, const uint32_t 
                     if (b0.count == 0)
                         break;
                     if (b1.count == kWaveSize && b0.count == kWaveSize &&
-                        cn_pair<MINSUM, MAXD>(msg, b0.off, b1.off, b0.degree, b1.degree, lane))
+                        cn_pair<MINSUM, MAXD, CORR>(msg, b0.off, b1.off, b0.degree, b1.degree, lane, corr))
                         continue;
-                    cn_block<MINSUM, MAXD>(msg, b0, lane, scratch, scratch2);
+                    cn_block<MINSUM, MAXD, CORR>(msg, b0, lane, scratch, scratch2, corr);
                     if (b1.count == 0)
                         break;
-                    cn_block<MINSUM, MAXD>(msg, b1, lane, scratch, scratch2);
+                    cn_block<MINSUM, MAXD, CORR>(msg, b1, lane, scratch, scratch2, corr);
                 }
             }
             else
@@ -1776,6 +1803,20 @@ template <bool MINSUM, bool WANT_LLR, bool LDS_RESIDENT, int MAXD, int LLR_MODE,
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(5, 5))) void decode_kernel_w5(const DecodeArgs a)
 {
     decode_body<MINSUM, WANT_LLR, LDS_RESIDENT, MAXD, LLR_MODE, RATIO, false, false, kW5VnBlocks>(a, blockIdx.x);
+}
+
+// ---- corrected min-sum (device_cn.hpp, MsCorr; NON-PARITY): decode_kernel's and decode_kernel_w5's min-sum bodies with the
+// correction applied to every check node's inputs (the kernels above keep exactly their own code) ----
+template <bool WANT_LLR, bool LDS_RESIDENT, int MAXD, int LLR_MODE>
+__global__ __launch_bounds__(kThreads) void decode_msc_kernel(const DecodeArgs a)
+{
+    decode_body<true, WANT_LLR, LDS_RESIDENT, MAXD, LLR_MODE, false, false, false, kMaxVnBlocksInRegs, false, true>(a, blockIdx.x);
+}
+
+template <int MAXD, int LLR_MODE>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(5, 5))) void decode_msc_w5(const DecodeArgs a)
+{
+    decode_body<true, false, true, MAXD, LLR_MODE, false, false, false, kW5VnBlocks, false, true>(a, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2296,6 +2337,13 @@ int launch_decode_impl(const DecodeArgs &a, bool min_sum, uint32_t lds_bytes, vo
             else if (ratio)
                 k = decode_kernel_w5<false, false, LDS_RESIDENT, MAXD, LLR_MODE, true>;
         }
+    if (min_sum && a.ms_correct) // corrected min-sum: the same choice among its own instantiations
+    {
+        k = want_llr ? decode_msc_kernel<true, LDS_RESIDENT, MAXD, LLR_MODE> : decode_msc_kernel<false, LDS_RESIDENT, MAXD, LLR_MODE>;
+        if constexpr (LDS_RESIDENT && MAXD == 4 && LLR_MODE == kLlrRegs)
+            if (!want_llr && few_vn_blocks)
+                k = decode_msc_w5<MAXD, LLR_MODE>;
+    }
     if constexpr (LDS_RESIDENT)
     {
         if (handover)

@@ -105,6 +105,10 @@ struct DecodeArgs
     // kModeAwgnCtr / kModeBscCtr: Philox key (seed & 0xFFFFFFFF, seed >> 32) and the stream index of the batch's frame 0
     uint32_t ctr_key[2];
     uint64_t ctr_frame0;
+    // opt-in NON-PARITY corrected min-sum (device_cn.hpp, MsCorr): a min-sum launch with ms_correct set takes the corrected
+    // instantiations, whose check nodes output max(fl(fl(ms_scale * m) - ms_offset), +0.0) with the sign of plain min-sum
+    int ms_correct;
+    double ms_scale, ms_offset;
 };
 
 // device copy of RegPlan (register-resident decoder, kernels_reg.hip)

@@ -942,9 +942,10 @@ __device__ __forceinline__ void fused_body(const DecodeArgs &a, const DevFusedPl
 // decisions stay in registers, and the prologue is the balanced one.  Every operation is the reference's: sign * sign *
 // min (decoder.h:17-20: exact, so the order of a check node's inputs does not matter), the variable node's sum in column
 // file order, v2c = out - c2v.  LLR-out doubles == the reference's.
-template <int D, bool LEAF, bool TWO>
+// CORR: the corrected min-sum rule (device_cn.hpp, MsCorr), c its parameters
+template <int D, bool LEAF, bool TWO, bool CORR = false>
 __device__ __forceinline__ void cnms_call(char *msg, uint32_t off0, uint32_t off1, uint32_t cnt0, int lane, double &lv0, double &lv1,
-                                          double L0, double L1, double &out0, double &out1)
+                                          double L0, double L1, double &out0, double &out1, MsCorr c = MsCorr{1.0, 0.0})
 {
     constexpr int M = D - (LEAF ? 1 : 0);
     const uint32_t stride = TWO ? kWaveSize * 8u : cnt0 * 8u;
@@ -961,9 +962,9 @@ __device__ __forceinline__ void cnms_call(char *msg, uint32_t off0, uint32_t off
     }
     if constexpr (LEAF)
         v0[M] = lv0, v1[M] = lv1;
-    cn_core<D, true>(v0);
+    cn_core<D, true, CORR>(v0, c);
     if constexpr (TWO)
-        cn_core<D, true>(v1);
+        cn_core<D, true, CORR>(v1, c);
 #pragma unroll
     for (int k = 0; k < M; ++k)
         *at(p0, k * stride) = v0[k];
@@ -1049,9 +1050,10 @@ __device__ __forceinline__ double vnms_table(char *msg, const uint32_t *tbl, int
     return out;
 }
 
-template <bool WANT_LLR, int VNB, int CNL, int NK = kNoiseStream>
+template <bool WANT_LLR, int VNB, int CNL, int NK = kNoiseStream, bool CORR = false>
 __device__ __forceinline__ void fused_ms_body(const DecodeArgs &a, const DevFusedPlan &F)
 {
+    [[maybe_unused]] const MsCorr corr{a.ms_scale, a.ms_offset}; // CORR only
     extern __shared__ double lds[];
     __shared__ int misc[4];
     const DevPlan &P = a.plan;
@@ -1158,11 +1160,11 @@ __device__ __forceinline__ void fused_ms_body(const DecodeArgs &a, const DevFuse
 #define LDPC_MS_LEAF(D)                                                                                                                   \
     case D:                                                                                                                               \
         if (two)                                                                                                                          \
-            cnms_call<D, true, true>(msg, offs & 0xFFFFu, offs >> 16, cnt0, lane, leaf_v2c[2 * c], leaf_v2c[2 * c + 1], leaf_L[2 * c],    \
-                                     leaf_L[2 * c + 1], o0, o1);                                                                          \
+            cnms_call<D, true, true, CORR>(msg, offs & 0xFFFFu, offs >> 16, cnt0, lane, leaf_v2c[2 * c], leaf_v2c[2 * c + 1],          \
+                                           leaf_L[2 * c], leaf_L[2 * c + 1], o0, o1, corr);                                               \
         else if (lane < static_cast<int>(cnt0))                                                                                           \
-            cnms_call<D, true, false>(msg, offs & 0xFFFFu, 0, cnt0, lane, leaf_v2c[2 * c], leaf_v2c[2 * c + 1], leaf_L[2 * c],            \
-                                      leaf_L[2 * c + 1], o0, o1);                                                                         \
+            cnms_call<D, true, false, CORR>(msg, offs & 0xFFFFu, 0, cnt0, lane, leaf_v2c[2 * c], leaf_v2c[2 * c + 1], leaf_L[2 * c],      \
+                                            leaf_L[2 * c + 1], o0, o1, corr);                                                             \
         break;
             switch (cls & 7u) // wave-uniform (a min-sum node does not care where its outputs go: degree and leaf only)
             {
@@ -1193,9 +1195,9 @@ __device__ __forceinline__ void fused_ms_body(const DecodeArgs &a, const DevFuse
 #define LDPC_MS(D)                                                                                                        \
     case D:                                                                                                               \
         if (two)                                                                                                          \
-            cnms_call<D, false, true>(msg, offs & 0xFFFFu, offs >> 16, cnt0, lane, d0, d1, 0.0, 0.0, d2, d3);             \
+            cnms_call<D, false, true, CORR>(msg, offs & 0xFFFFu, offs >> 16, cnt0, lane, d0, d1, 0.0, 0.0, d2, d3, corr); \
         else if (lane < static_cast<int>(cnt0))                                                                           \
-            cnms_call<D, false, false>(msg, offs & 0xFFFFu, 0, cnt0, lane, d0, d1, 0.0, 0.0, d2, d3);                     \
+            cnms_call<D, false, false, CORR>(msg, offs & 0xFFFFu, 0, cnt0, lane, d0, d1, 0.0, 0.0, d2, d3, corr);         \
         break;
             switch (cls & 7u)
             {
@@ -1361,6 +1363,14 @@ __global__ __launch_bounds__(kThreads) void decode_ctr_fused_ms_kernel(const Dec
     fused_ms_body<WANT_LLR, VNB, CNL, kNoiseCounter>(a, f);
 }
 
+// ---- corrected min-sum (device_cn.hpp, MsCorr; NON-PARITY): fused_ms_body with the correction on every check node's inputs,
+// for the reference stream and the counter-based noise (NK) ----
+template <bool WANT_LLR, int VNB, int CNL, int NK>
+__global__ __launch_bounds__(kThreads) void decode_fused_msc_kernel(const DecodeArgs a, const DevFusedPlan f)
+{
+    fused_ms_body<WANT_LLR, VNB, CNL, NK, true>(a, f);
+}
+
 bool counter_args(const DecodeArgs &a) { return a.mode == kModeAwgnCtr || a.mode == kModeBscCtr; }
 
 } // namespace
@@ -1446,6 +1456,22 @@ int launch_decode_fused_minsum(const DecodeArgs &a, const DevFusedPlan &f, void 
         else
             k = want_llr ? decode_ctr_fused_ms_kernel<true, kFusedVnSlots, kFusedLeafCalls>
                          : decode_ctr_fused_ms_kernel<false, kFusedVnSlots, kFusedLeafCalls>;
+    }
+    if (a.ms_correct)
+    {
+#define LDPC_MSC(NK)                                                                                                                 \
+    k = (f.vnb <= 4 && f.cnl <= 1) ? (want_llr ? decode_fused_msc_kernel<true, 4, 1, NK> : decode_fused_msc_kernel<false, 4, 1, NK>) \
+                                   : (want_llr ? decode_fused_msc_kernel<true, kFusedVnSlots, kFusedLeafCalls, NK>                   \
+                                               : decode_fused_msc_kernel<false, kFusedVnSlots, kFusedLeafCalls, NK>);
+        if (counter_args(a))
+        {
+            LDPC_MSC(kNoiseCounter)
+        }
+        else
+        {
+            LDPC_MSC(kNoiseStream)
+        }
+#undef LDPC_MSC
     }
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(f.lds_bytes));
     if (e != hipSuccess)

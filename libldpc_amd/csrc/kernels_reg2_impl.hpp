@@ -44,8 +44,8 @@ namespace
 // SH6: the first of the three launches — check nodes of degree 6 share reciprocals (detmath.h, dm_cn6_shared); the range
 // check of their products joins `escaped`, which is voted on at the top of the NEXT pass: it counts once the frame has gone
 // on to the variable-node pass, as the rule says
-template <bool MINSUM, bool RATIO, int MAXD, bool SH6>
-__device__ __forceinline__ void cn_regs2(double (&m)[MAXD], int degree, uint32_t *escaped)
+template <bool MINSUM, bool RATIO, int MAXD, bool SH6, bool CORR = false>
+__device__ __forceinline__ void cn_regs2(double (&m)[MAXD], int degree, uint32_t *escaped, MsCorr c = MsCorr{1.0, 0.0})
 {
     // wave-uniform degree: one fully unrolled recursion per width
 #define LDPC_CASE(D)                                                \
@@ -56,7 +56,7 @@ __device__ __forceinline__ void cn_regs2(double (&m)[MAXD], int degree, uint32_t
         if constexpr (RATIO)                                        \
             cn_ratio<D, false, SH6>(v, nullptr, escaped);           \
         else                                                        \
-            cn_core<D, MINSUM>(v);                                  \
+            cn_core<D, MINSUM, CORR>(v, c);                         \
         _Pragma("unroll") for (int j = 0; j < D; ++j) m[j] = v[j];  \
         break;                                                      \
     }
@@ -122,9 +122,10 @@ __device__ __forceinline__ Reg2VnBlock load_vn_block(const Reg2VnBlock *table, u
 // the frame left the range of the form — a value outside the box of the ratio form, or a product of denominators beyond its
 // limit — and has to be decoded again from scratch by the next form; nothing of it has been delivered then.
 template <bool MINSUM, bool WANT_LLR, int NT, int KC, int MAXD, int NV0, int NV1, bool RATIO, bool SH6, bool UCN, bool UVN,
-          int NK = kNoiseStream>
+          int NK = kNoiseStream, bool CORR = false>
 __device__ __forceinline__ bool reg2_frame(const DecodeArgs &a, const DevReg2Plan &R_arg, const uint64_t frame, const int wave)
 {
+    [[maybe_unused]] const MsCorr corr{a.ms_scale, a.ms_offset}; // CORR (corrected min-sum, device_cn.hpp) only
     static_assert(NV0 % 2 == 0 && NV1 % 2 == 0, "variable-node rounds go two blocks at a time");
     static_assert(!(RATIO && MINSUM), "the ratio form is a sum-product form");
     static_assert(RATIO || !SH6, "shared reciprocals belong to the ratio form");
@@ -316,12 +317,12 @@ __device__ __forceinline__ bool reg2_frame(const DecodeArgs &a, const DevReg2Pla
                  if constexpr (!UCN)
                  {
                      if (deg[Ks] >= 2)
-                         cn_regs2<MINSUM, RATIO, MAXD, SH6>(m[Ks], deg[Ks], &escaped);
+                         cn_regs2<MINSUM, RATIO, MAXD, SH6, CORR>(m[Ks], deg[Ks], &escaped, corr);
                  }
                  else if constexpr (RATIO)
                      cn_ratio<MAXD, false, SH6>(m[Ks], nullptr, &escaped);
                  else
-                     cn_core<MAXD, MINSUM>(m[Ks]);
+                     cn_core<MAXD, MINSUM, CORR>(m[Ks], corr);
                  // one node after the other: the next one's inputs exist when this one's outputs do (left to itself the compiler
                  // works on all KC nodes at once and spills: 204 bytes per lane with the shared reciprocals)
                  if constexpr (UCN && MAXD == 6 && Ks + 1 < KC)
@@ -590,7 +591,7 @@ __device__ __forceinline__ bool reg2_frame(const DecodeArgs &a, const DevReg2Pla
 // by one workgroup on an otherwise idle chip — the frames that do not converge at the operating point of BASELINE config 4
 // leave the box of the ratio form after a few dozen iterations, a handful per batch, and cost 0.3 ms per batch that way —
 // while inside the first launch the repeat hides among the other frames.  Which form finishes a frame is the same either way.)
-template <bool MINSUM, bool WANT_LLR, int NT, int KC, int MAXD, int NV0, int NV1, bool CHAIN, bool U, int NK>
+template <bool MINSUM, bool WANT_LLR, int NT, int KC, int MAXD, int NV0, int NV1, bool CHAIN, bool U, int NK, bool CORR = false>
 __device__ __forceinline__ void reg2_kernel_body(const DecodeArgs &a, const DevReg2Plan &R)
 {
     static_assert(!(CHAIN && MINSUM), "the chain is the sum-product decoder's");
@@ -609,7 +610,7 @@ __device__ __forceinline__ void reg2_kernel_body(const DecodeArgs &a, const DevR
             return;
         __syncthreads();
     }
-    reg2_frame<MINSUM, WANT_LLR, NT, KC, MAXD, NV0, NV1, false, false, U, U, NK>(a, R, frame, wave);
+    reg2_frame<MINSUM, WANT_LLR, NT, KC, MAXD, NV0, NV1, false, false, U, U, NK, CORR>(a, R, frame, wave);
 }
 
 template <bool MINSUM, bool WANT_LLR, int NT, int KC, int MAXD, int NV0, int NV1, bool CHAIN, bool U>
@@ -623,6 +624,14 @@ template <bool MINSUM, bool WANT_LLR, int NT, int KC, int MAXD, int NV0, int NV1
 __global__ __launch_bounds__(NT) void decode_reg2_ctr_kernel(const DecodeArgs a, const DevReg2Plan R)
 {
     reg2_kernel_body<MINSUM, WANT_LLR, NT, KC, MAXD, NV0, NV1, CHAIN, U, kNoiseCounter>(a, R);
+}
+
+// corrected min-sum (device_cn.hpp, MsCorr; NON-PARITY): the min-sum decoder with the correction on every check node's inputs,
+// for the reference stream and the counter-based noise (NK)
+template <bool WANT_LLR, int NT, int KC, int MAXD, int NV0, int NV1, bool U, int NK>
+__global__ __launch_bounds__(NT) void decode_reg2_msc_kernel(const DecodeArgs a, const DevReg2Plan R)
+{
+    reg2_kernel_body<true, WANT_LLR, NT, KC, MAXD, NV0, NV1, false, U, NK, true>(a, R);
 }
 
 // U: the regular code's instantiation (no switch over check-node degrees, straight-line variable-node rounds), or the
@@ -659,6 +668,15 @@ int launch_reg2(const DecodeArgs &a, const DevReg2Plan &r, bool min_sum, void *s
         else
             k = want_llr ? decode_reg2_ctr_kernel<false, true, NT, KC, MAXD, NV0, NV1, false, U>
                          : decode_reg2_ctr_kernel<false, false, NT, KC, MAXD, NV0, NV1, false, U>;
+    }
+    if (min_sum && a.ms_correct)
+    {
+        if (a.mode == kModeAwgnCtr || a.mode == kModeBscCtr)
+            k = want_llr ? decode_reg2_msc_kernel<true, NT, KC, MAXD, NV0, NV1, U, kNoiseCounter>
+                         : decode_reg2_msc_kernel<false, NT, KC, MAXD, NV0, NV1, U, kNoiseCounter>;
+        else
+            k = want_llr ? decode_reg2_msc_kernel<true, NT, KC, MAXD, NV0, NV1, U, kNoiseStream>
+                         : decode_reg2_msc_kernel<false, NT, KC, MAXD, NV0, NV1, U, kNoiseStream>;
     }
     const uint32_t lds = r.lds_entries * 8u + 16u;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,

@@ -9,8 +9,9 @@
 // one process per listed GPU, forked before anything touches a GPU, the frames of every step shared out over them and
 // the counters exchanged over RCCL — results are those of the one-GPU run; --comm shm puts the exchange on host
 // shared memory instead, for rehearsals with a repeated device such as --devices 0,0); --noise counter (NON-PARITY
-// counter-based noise, include/ldpc_amd.h ldpc_hip_set_noise); --bec-compat (reproduce the
-// reference's out-of-bounds read for erased degree-1 variable nodes).
+// counter-based noise, include/ldpc_amd.h ldpc_hip_set_noise); --ms-scale A / --ms-offset B with --decoding BP_MS
+// (NON-PARITY normalized / offset min-sum, include/ldpc_amd.h ldpc_hip_set_min_sum_correction); --bec-compat (reproduce
+// the reference's out-of-bounds read for erased degree-1 variable nodes).
 #include <fcntl.h>
 #include <signal.h>
 #include <sys/prctl.h>
@@ -57,7 +58,10 @@ const char *kUsage =
     "--bec-compat        \tBEC: erased degree-1 variable nodes emit 0 as the reference build does.\n"
     "--noise             \tNoise: \"reference\" (default: the reference's mt19937_64 stream, frame for frame) or\n"
     "                    \t\"counter\" (counter-based Philox of seed, frame and bit; NON-PARITY: error rates compare\n"
-    "                    \twith the reference only statistically).\n";
+    "                    \twith the reference only statistically).\n"
+    "--ms-scale          \tBP_MS only: normalized min-sum, check-node magnitudes times A, 0 < A <= 1 (NON-PARITY).\n"
+    "--ms-offset         \tBP_MS only: offset min-sum, B subtracted from check-node magnitudes, 0 <= B <= 1e6,\n"
+    "                    \tclamped at zero (NON-PARITY; with --ms-scale: the offset after the scale).\n";
 
 std::vector<int> parse_devices(const std::string &spec)
 {
@@ -100,6 +104,8 @@ int main(int argc, char *argv[])
     std::vector<int> devices;
     std::string comm_kind = "rccl";
     std::string noise = "reference";
+    std::string ms_scale_arg, ms_offset_arg; // corrected min-sum: the values as given (empty: not given)
+    double ms_scale = 1.0, ms_offset = 0.0;
     try
     {
         for (int i = 1; i < argc; ++i)
@@ -143,6 +149,10 @@ int main(int argc, char *argv[])
                 bec_compat = true;
             else if (a == "--noise")
                 noise = value();
+            else if (a == "--ms-scale")
+                ms_scale = std::stod(ms_scale_arg = value());
+            else if (a == "--ms-offset")
+                ms_offset = std::stod(ms_offset_arg = value());
             else if (a.size() > 1 && a[0] == '-' && !(std::isdigit(static_cast<unsigned char>(a[1])) || a[1] == '.'))
                 throw std::runtime_error("Unknown argument: " + a);
             else
@@ -154,6 +164,16 @@ int main(int argc, char *argv[])
             throw std::runtime_error("--comm: rccl or shm");
         if (noise != "reference" && noise != "counter")
             throw std::runtime_error("--noise: reference or counter");
+        if (!ms_scale_arg.empty() || !ms_offset_arg.empty())
+        {
+            if (decoding != "BP_MS")
+                throw std::runtime_error("--ms-scale / --ms-offset: min-sum corrections, for --decoding BP_MS only");
+            // (include/ldpc_amd.h, ldpc_hip_set_min_sum_correction; the comparisons are false for NaN)
+            if (!(ms_scale > 0.0 && ms_scale <= 1.0))
+                throw std::runtime_error("--ms-scale: need 0 < A <= 1");
+            if (!(ms_offset >= 0.0 && ms_offset <= 1e6))
+                throw std::runtime_error("--ms-offset: need 0 <= B <= 1e6");
+        }
     }
     catch (const std::exception &e)
     {
@@ -292,6 +312,12 @@ int main(int argc, char *argv[])
         ldpc_hip_destroy(ctx);
         return reap(EXIT_FAILURE);
     }
+    if ((!ms_scale_arg.empty() || !ms_offset_arg.empty()) && ldpc_hip_set_min_sum_correction(ctx, ms_scale, ms_offset) != 0)
+    {
+        std::cout << "Error: " << ldpc_hip_last_error() << std::endl;
+        ldpc_hip_destroy(ctx);
+        return reap(EXIT_FAILURE);
+    }
     int64_t info[10];
     ldpc_hip_code_info(ctx, info);
 
@@ -303,6 +329,10 @@ int main(int argc, char *argv[])
     std::cout << bar << std::endl;
     std::cout << "== Decoder Parameters\n";
     std::cout << " Type: " << decoding << "\n Iterations: " << iterations << "\n Early Termination: " << !no_early << "\n";
+    if (!ms_scale_arg.empty() || !ms_offset_arg.empty())
+        std::cout << " Min-Sum Correction: scale " << (ms_scale_arg.empty() ? "1" : ms_scale_arg) << ", offset "
+                  << (ms_offset_arg.empty() ? "0" : ms_offset_arg)
+                  << " (c2v magnitude max(scale * min - offset, 0)), NON-PARITY\n";
     std::cout << "== Channel Parameters\n";
     std::cout << " Type: " << channel << "\n Seed: " << seed << "\n Range: Min: " << range[0] << ", Max: " << range[1]
               << ", Step: " << range[2] << "\n";
