@@ -261,6 +261,10 @@ int ldpc_hip_comm_allgather(ldpc_hip_comm *comm, const void *send, void *recv, u
    take it): info = {the code qualifies, message slots, variable-node blocks per wave, leaf calls per wave, the small
    instantiation applies, check-node calls per wave + 1, the code has shortened bits, entries of the slot table} */
 void ldpc_hip_fused_plan_info(const ldpc_hip_ctx *ctx, int64_t info[8]);
+/* the launches a batch decoded with `dec` takes on this context, in order (host only; honours ldpc_hip_set_fast_mode;
+   DESIGN.md section 4): stages[i] = 0 whole, 1 ratio-first, 2 ratio-separate, 3 list-chain, 4 llr-redo, 5 handover-first,
+   6 handover-resume; returns their number, 1 to 3 */
+int ldpc_hip_decode_stages(const ldpc_hip_ctx *ctx, decoder_param dec, int32_t stages[3]);
 /* the steps of the layered schedule of the non-parity modes 2 / 3 (host only): step_of_row[mc] = the step each check node
    is processed in; returns the number of steps, -1 when the schedule does not take the code */
 int ldpc_hip_selftest_layer_plan(ldpc_hip_ctx *ctx, int32_t *step_of_row);

@@ -99,6 +99,8 @@ def load_library(path=LIB_PATH):
     L.ldpc_hip_comm_allgather.argtypes = [vp, vp, vp, u64]
     L.ldpc_hip_fused_plan_info.restype = None
     L.ldpc_hip_fused_plan_info.argtypes = [vp, vp]
+    L.ldpc_hip_decode_stages.restype = i32
+    L.ldpc_hip_decode_stages.argtypes = [vp, decoder_param, vp]
     L.ldpc_hip_selftest_layer_plan.restype = i32
     L.ldpc_hip_selftest_layer_plan.argtypes = [vp, vp]
     L.ldpc_hip_selftest_place.restype = i32
@@ -253,6 +255,15 @@ class HipDecoder:
         info = (ct.c_int64 * 8)()
         self.lib.ldpc_hip_fused_plan_info(self.ctx, info)
         return dict(zip(("ok", "n_slots", "vnb", "cnl", "small", "calls_stride", "has_shortened", "table_entries"), [int(v) for v in info]))
+
+    STAGES = ("whole", "ratio-first", "ratio-separate", "list-chain", "llr-redo", "handover-first", "handover-resume")
+
+    def decode_stages(self, early_term=True, iterations=50, decoding="BP"):
+        """The launches a batch with these parameters takes, in order (include/ldpc_amd.h, ldpc_hip_decode_stages; honours
+        set_fast_mode; touches no GPU)."""
+        stages = (ct.c_int32 * 3)()
+        n = self.lib.ldpc_hip_decode_stages(self.ctx, _dec(early_term, iterations, decoding), stages)
+        return [self.STAGES[stages[i]] for i in range(n)]
 
     def set_fast_mode(self, on):
         """Opt-in NON-PARITY mode: sum-product with binary32 messages (include/ldpc_amd.h)."""

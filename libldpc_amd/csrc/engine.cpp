@@ -779,6 +779,16 @@ void Engine::finish_batch(OutStage &st, const BatchOut &out, uint64_t n, const u
     st.flush(s, &pin_out_);
 }
 
+// the list pointers a stage reads (`in`) and writes (`out`): buffers of [count][n frames][n resume iterations]
+static void set_stage_lists(DecodeArgs &a, Stage st, uint32_t *in, uint32_t *out, uint64_t n)
+{
+    const bool reads = stage_reads_list(st), writes = stage_writes_list(st);
+    a.redo_count_in = reads ? in : nullptr, a.redo_list_in = reads ? in + 1 : nullptr;
+    a.redo_iter_in = st == Stage::kHandoverResume ? in + 1 + n : nullptr;
+    a.redo_count = writes ? out : nullptr, a.redo_list = writes ? out + 1 : nullptr;
+    a.redo_iter = st == Stage::kHandoverFirst ? out + 1 + n : nullptr;
+}
+
 void Engine::run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, uint64_t n, void *stream)
 {
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -799,9 +809,7 @@ void Engine::run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, 
     prof_mark(0, s);
     // the caller asked for a non-parity mode (never chosen by itself): one launch, no ratio form
     const bool fast = fast_mode && !p.min_sum;
-    bool fused_handover_used = false;
-    bool finished_in_one = false; // the launch was the totals-form register kernel's chain of all three forms (kernels_reg2_impl.hpp)
-    const auto launch = [&] {
+    const auto launch = [&](Stage stage) {
         if (fast && fast_mode == 1)
         {
             if (!fast_mode_supported(dev_, plan_.max_cn_degree) || plan_.has_isolated_vn)
@@ -824,20 +832,16 @@ void Engine::run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, 
         switch (residency_)
         {
         case Residency::kLds:
-            // the first launch of sum-product with early termination, for codes the fused form takes (fused_rule.h)
-            if (fused_plan_.ok && !p.min_sum && p.early_term && a.redo_list && !a.redo_count_in && !a.ratio_separate)
-                check(launch_decode_fused(a, dev_fused_, s), "decode (fused form)");
-            else if (fused_plan_.ok && !p.min_sum && !p.early_term && a.redo_list && a.redo_iter && !a.redo_count_in)
-            {
-                // without early termination: the fused form with separately divided outputs until a frame's totals near the edge
-                // of the box, then the LLR-domain launch below continues it (the messages are handed over as LLRs)
-                check(launch_decode_fused_handover(a, dev_fused_, s), "decode (fused form, hand-over)");
-                fused_handover_used = true;
-            }
-            else if (fused_plan_.ok && p.min_sum && !p.early_term && p.iterations > 0 && !a.redo_list && !a.redo_count_in)
-                check(launch_decode_fused_minsum(a, dev_fused_, s), "decode (min-sum, fused plan)");
+            // codes the fused form takes (fused_rule.h): the first launch of sum-product — without early termination with
+            // separately divided outputs, its messages handed over as LLRs — and min-sum without early termination
+            if (fused_plan_.ok && stage == Stage::kRatioFirst)
+                check(launch_decode_fused(a, dev_fused_, stage, s), "decode (fused form)");
+            else if (fused_plan_.ok && stage == Stage::kHandoverFirst)
+                check(launch_decode_fused(a, dev_fused_, stage, s), "decode (fused form, hand-over)");
+            else if (fused_plan_.ok && stage == Stage::kWhole && p.min_sum && !p.early_term && p.iterations > 0)
+                check(launch_decode_fused(a, dev_fused_, stage, s), "decode (min-sum, fused plan)");
             else
-                check(launch_decode_lds(a, p.min_sum, plan_.max_cn_degree, lds_llr_mode_, s), "decode (LDS-resident)");
+                check(launch_decode_lds(a, stage, p.min_sum, plan_.max_cn_degree, lds_llr_mode_, s), "decode (LDS-resident)");
             break;
         case Residency::kRegTotals:
         case Residency::kRegMessages:
@@ -847,45 +851,42 @@ void Engine::run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, 
             {
                 // channel terms of the variable nodes, one per (block slot, thread): kernels_reg2.hip
                 a.ws_scr = static_cast<double *>(ws_scr_.reserve(8 * n * static_cast<uint64_t>(reg2_plan_.nv0 + reg2_plan_.nv1) * reg2_plan_.nt));
-                check(launch_decode_reg2(a, dev_reg2_, p.min_sum, s), "decode (register-resident, totals form)");
-                finished_in_one = a.redo_list != nullptr;
+                check(launch_decode_reg2(a, dev_reg2_, stage, p.min_sum, s), "decode (register-resident, totals form)");
             }
             else
-                check(launch_decode_reg(a, dev_reg_, p.min_sum, s), "decode (register-resident)");
+                check(launch_decode_reg(a, dev_reg_, stage, p.min_sum, s), "decode (register-resident)");
             break;
         case Residency::kMemory:
             a.ws_msg = static_cast<double *>(ws_msg_.reserve(8 * n * nnz));
             a.ws_llr = static_cast<double *>(ws_llr_.reserve(8 * n * nc));
             a.ws_hb = static_cast<uint8_t *>(ws_hb_.reserve(n * nnz));
             a.ws_scr = plan_.max_cn_degree > kMaxCnDegree ? static_cast<double *>(ws_scr_.reserve(16 * n * nnz)) : nullptr;
-            check(launch_decode_mem(a, p.min_sum, plan_.max_cn_degree, mem_occ_lds_, s), "decode (memory-resident)");
+            check(launch_decode_mem(a, stage, p.min_sum, plan_.max_cn_degree, mem_occ_lds_, s), "decode (memory-resident)");
             break;
         case Residency::kNone:
             throw std::runtime_error("code not supported by any decoder instantiation");
         }
     };
-    // Sum-product with early termination runs in likelihood-ratio form (detmath.h: no exp/log inside the
-    // iteration); the few frames whose values leave the box that form can represent come back in a list and are
-    // decoded from scratch by the LLR-domain form.  Which form finishes a frame depends on that frame's data
-    // only, never on the batch it travels in.
-    // (codes with a check node wider than kMaxCnDegree run the LLR-domain form only; the oracle applies the same rule)
-    // Without early termination the LDS-resident decoder still starts every frame in the ratio form and hands it over
-    // to the LLR-domain form at an iteration boundary when its totals near the edge of the box (detmath.h "Hand-over").
-    const bool handover = !p.early_term && residency_ == Residency::kLds;
-    bool later_stages = true;
-    if (!fast && !p.min_sum && (p.early_term || handover) && p.iterations > 0 && plan_.max_cn_degree <= kMaxCnDegree)
+    const StageSeq seq = stages(p);
+    uint32_t *list_in = nullptr; // what the stage before handed on
+    for (int i = 0; i < seq.n; ++i)
     {
-        uint32_t *redo = static_cast<uint32_t *>(redo_.reserve(4 * (2 * n + 1)));
-        check(hipMemsetAsync(redo, 0, 4, s), "redo count");
-        a.redo_count = redo, a.redo_list = redo + 1;
-        if (handover)
+        const Stage stage = seq.s[i];
+        uint32_t *list_out = nullptr;
+        if (stage_writes_list(stage))
         {
-            a.redo_iter = redo + 1 + n;
-            a.ws_handover = static_cast<double *>(ws_msg_.reserve(8 * n * nnz));
+            list_out = static_cast<uint32_t *>(i == 0 ? redo_.reserve(4 * (2 * n + 1)) : redo2_.reserve(4 * (n + 1)));
+            check(hipMemsetAsync(list_out, 0, 4, s), "redo count");
         }
+        set_stage_lists(a, stage, list_in, list_out, n);
+        if (stage == Stage::kHandoverFirst)
+            a.ws_handover = static_cast<double *>(ws_msg_.reserve(8 * n * nnz));
+        if (stage == Stage::kHandoverResume) // (the fused form hands its messages over as LLRs)
+            a.handover_llr = fused_plan_.ok ? 1 : 0;
 #ifdef LDPC_AMD_PHASE_TRACE
         uint64_t *tr = nullptr;
-        const char *trace_file = std::getenv("LDPC_AMD_PHASE_TRACE"); // debug build: per-wave phase timers of the first 2048 frames
+        // debug build: per-wave phase timers of the first 2048 frames
+        const char *trace_file = i == 0 && stage != Stage::kWhole ? std::getenv("LDPC_AMD_PHASE_TRACE") : nullptr;
         if (trace_file)
         {
             check(hipMalloc(&tr, 2048 * 32 * 8), "trace");
@@ -893,7 +894,7 @@ void Engine::run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, 
             a.phase_trace = tr;
         }
 #endif
-        launch();
+        launch(stage);
 #ifdef LDPC_AMD_PHASE_TRACE
         if (tr)
         {
@@ -909,62 +910,21 @@ void Engine::run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, 
             a.phase_trace = nullptr;
         }
 #endif
-        a.redo_count = nullptr, a.redo_list = nullptr, a.redo_iter = nullptr;
-        a.redo_count_in = redo, a.redo_list_in = redo + 1;
         // A handful of frames for a caller who waits for host results anyway (the reference's decode(): one frame per call):
         // the results of the first launch and the number of frames it handed back travel to the host together; the later
         // launches — two more dispatches and a memset, a fifth of such a call's latency, for lists that are almost always
         // empty — are issued only when that number is not zero, and the results delivered again.
         const size_t pinned = st.pinned_bytes();
-        if (n <= 16 && pinned && pinned <= OutStage::kPinnedLimit && !handover && a.mode == kModeLlr &&
-            st.flush(s, &pin_out_, redo) == 0)
+        if (i == 0 && stage == Stage::kRatioFirst && n <= 16 && pinned && pinned <= OutStage::kPinnedLimit && a.mode == kModeLlr &&
+            st.flush(s, &pin_out_, list_out) == 0)
         {
-            later_stages = false;
             st.items.clear(); // (delivered)
+            break;
         }
-        if (finished_in_one)
-            later_stages = false; // (nothing has been delivered yet: the outputs are flushed below as after any last launch)
-        if (!later_stages)
-            ;
-        else if (handover)
-        {
-            a.redo_iter_in = redo + 1 + n;
-            a.handover_llr = fused_handover_used ? 1 : 0;
-        }
-        else if (residency_ == Residency::kLds || shared6_)
-        {
-            // (codes the LDS-resident decoder does not take: the same three launches when the code has check nodes of degree 6,
-            // which share reciprocals in the first launch of the register- and memory-resident decoders — detmath.h, dm_cn6_shared)
-            // The first launch ran the shared-reciprocal check nodes (detmath.h), whose denominator products leave their
-            // range in a few frames per ten thousand at the waterfall (strongly converged frames): those are decoded again
-            // from scratch with every output divided separately — the ratio form still, a twentieth of a millisecond for a
-            // few dozen frames — and only what leaves the box there goes on to the LLR domain.  (A lone frame takes 0.3 ms
-            // in the LLR domain, and the launches of a batch run one after the other.)
-            if (residency_ == Residency::kLds)
-            {
-                // LDS-resident: ONE more launch, over the list — separately divided outputs and, for what leaves the box there,
-                // the LLR domain, frame by frame in the same workgroup (kernels.hip, decode_kernel_list)
-                a.ratio_separate = 1;
-                launch();
-                a.ratio_separate = 0;
-                later_stages = false;
-            }
-            else
-            {
-                uint32_t *redo2 = static_cast<uint32_t *>(redo2_.reserve(4 * (n + 1)));
-                check(hipMemsetAsync(redo2, 0, 4, s), "redo count");
-                a.redo_count = redo2, a.redo_list = redo2 + 1;
-                a.ratio_separate = 1;
-                launch();
-                a.ratio_separate = 0;
-                a.redo_count = nullptr, a.redo_list = nullptr;
-                a.redo_count_in = redo2, a.redo_list_in = redo2 + 1;
-            }
-        }
+        list_in = list_out;
     }
-    if (later_stages)
-        launch();
-    a.redo_count_in = nullptr, a.redo_list_in = nullptr, a.redo_iter_in = nullptr, a.ws_handover = nullptr, a.handover_llr = 0;
+    set_stage_lists(a, Stage::kWhole, nullptr, nullptr, n);
+    a.ws_handover = nullptr, a.handover_llr = 0;
     finish_batch(st, out, n, a.codeword, a.mode == kModeAwgn ? a.pairs_buffer : -1, stream);
 }
 

@@ -68,6 +68,39 @@ enum class Residency : int
     kMemory       // messages in device memory (kernels.hip)
 };
 
+// The launches of one batch, in order (kernels.hpp, Stage).  Pure host arithmetic, no HIP: run_decode walks
+// the sequence, the CPU tests read it through ldpc_hip_decode_stages.
+struct StageSeq
+{
+    int n = 0;
+    Stage s[3] = {};
+};
+// shared6: not LDS-resident and a check node of degree 6; ratio_width: no check node wider than kMaxCnDegree (wider ones
+// run the LLR-domain form only; the oracle applies the same rule); fast: a non-parity fast / layered mode applies
+inline StageSeq decode_stages(Residency r, bool shared6, bool ratio_width, bool min_sum, bool early_term, bool iterations, bool fast)
+{
+    // Sum-product runs in likelihood-ratio form (detmath.h: no exp/log inside the iteration); the few frames whose values
+    // leave the box that form can represent come back in a list and go on to the next stage.  Which form finishes a frame
+    // depends on that frame's data only, never on the batch it travels in.
+    if (fast || min_sum || !iterations || !ratio_width || r == Residency::kNone)
+        return {1, {Stage::kWhole}};
+    // LDS-resident: ONE more launch over the first one's list (kernels.hip, decode_kernel_list); without early termination
+    // every frame still starts in the ratio form and is handed over to the LLR-domain form at an iteration boundary when
+    // its totals near the edge of the box (detmath.h "Hand-over")
+    if (r == Residency::kLds)
+        return early_term ? StageSeq{2, {Stage::kRatioFirst, Stage::kListChain}}
+                          : StageSeq{2, {Stage::kHandoverFirst, Stage::kHandoverResume}};
+    if (!early_term)
+        return {1, {Stage::kWhole}};
+    if (r == Residency::kRegTotals) // the kernel chains all three forms in its workgroup: no frame is handed back
+        return {1, {Stage::kRatioFirst}};
+    // The first launch of a code with check nodes of degree 6 runs them with shared reciprocals (detmath.h, dm_cn6_shared),
+    // whose denominator products leave their range in a few frames per ten thousand at the waterfall: those are decoded
+    // again with every output divided separately, and only what leaves the box there goes on to the LLR domain.
+    return shared6 ? StageSeq{3, {Stage::kRatioFirst, Stage::kRatioSeparate, Stage::kLlrRedo}}
+                   : StageSeq{2, {Stage::kRatioFirst, Stage::kLlrRedo}};
+}
+
 struct OutStage; // engine.cpp: a batch's outputs, written directly or through staging buffers
 
 class DeviceBuffer
@@ -200,6 +233,12 @@ class Engine
     const Reg2Plan &reg2_plan() const { return reg2_plan_; }
     const FusedPlan &fused_plan() const { return fused_plan_; }
     Residency residency() const { return residency_; }
+    // the launches a batch with these parameters takes (honours fast_mode; needs no device)
+    StageSeq stages(const DecParams &p) const
+    {
+        return decode_stages(residency_, shared6_, plan_.max_cn_degree <= kMaxCnDegree, p.min_sum, p.early_term, p.iterations > 0,
+                             fast_mode && !p.min_sum);
+    }
     int device() const { return device_; }
     bool bec_deg1_compat = false;
     // opt-in NON-PARITY modes, off (0) by default and never chosen by the library: 1 = flooding sum-product with binary32
@@ -321,7 +360,7 @@ class Engine
     Plan plan_;
     RegPlan reg_plan_;
     Reg2Plan reg2_plan_;
-    bool shared6_ = false; // not LDS-resident and a check node of degree 6: three launches with early termination (dm_cn6_shared)
+    bool shared6_ = false; // not LDS-resident and a check node of degree 6 (decode_stages: dm_cn6_shared, then kRatioSeparate)
     FusedPlan fused_plan_; // fused form of the first ratio launch (kernels_fused.hip); ok = the code qualifies (fused_rule.h)
     Residency residency_ = Residency::kNone;
     int lds_llr_mode_ = 0;     // LDS-resident: the input LLRs in LDS (0) or in registers (2), kernels.hpp launch_decode_lds

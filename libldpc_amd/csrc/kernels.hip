@@ -2294,107 +2294,105 @@ __global__ __launch_bounds__(256) void division_selftest_kernel(uint64_t n, uint
         atomicAdd(mismatches, bad);
 }
 
-template <bool LDS_RESIDENT, int MAXD, int LLR_MODE>
-int launch_decode_impl(const DecodeArgs &a, bool min_sum, uint32_t lds_bytes, void *stream)
+using DecodeKernel = void (*)(const DecodeArgs);
+
+// The kernel of a stage, or null where this decoder has none.  w5: the instantiations for small codes (at most kW5VnBlocks VN
+// blocks per wave, message byte offsets within 16 bits), which only the narrow LDS-resident shape has.
+template <bool WANT_LLR, bool LDS_RESIDENT, int MAXD, int LLR_MODE>
+DecodeKernel decode_kernel_of(Stage stage, bool min_sum, bool ms_correct, [[maybe_unused]] bool w5)
 {
-    const bool want_llr = a.llr_out != nullptr;
-    // LDS-resident: the launch over the first launch's list (ratio_separate, a list coming in, none going out) is the chain
-    // kernel decode_kernel_list; memory-resident: a separately dividing ratio launch with lists on both sides
-    const bool list_chain = LDS_RESIDENT && a.ratio_separate && a.redo_count_in && !a.redo_list;
-    if (list_chain && (min_sum || !a.early_term || a.iterations == 0 || !a.redo_list_in || a.redo_iter_in))
-        return hipErrorInvalidValue;
-    const bool ratio = a.redo_list != nullptr;
-    // without early termination the ratio form runs with the hand-over to the LLR-domain form (detmath.h "Hand-over")
-    const bool handover = ratio && !a.early_term;
-    if (ratio && (min_sum || a.iterations == 0 || !a.redo_count || (a.redo_count_in && !a.ratio_separate) ||
-                  (handover && (!a.redo_iter || !a.ws_handover))))
-        return hipErrorInvalidValue;
-    if (a.ratio_separate && !list_chain && (!ratio || handover || LDS_RESIDENT || MAXD < 6))
-        return hipErrorInvalidValue;
-    if (a.redo_iter_in && !a.ws_handover)
-        return hipErrorInvalidValue;
-    void (*k)(const DecodeArgs) = nullptr;
-    if (min_sum)
-        k = want_llr ? decode_kernel<true, true, LDS_RESIDENT, MAXD, LLR_MODE, false>
-                     : decode_kernel<true, false, LDS_RESIDENT, MAXD, LLR_MODE, false>;
-    else if (ratio)
+    constexpr bool kHasW5 = LDS_RESIDENT && MAXD == 4 && LLR_MODE == kLlrRegs;
+    switch (stage)
     {
-        k = want_llr ? decode_kernel<false, true, LDS_RESIDENT, MAXD, LLR_MODE, true>
-                     : decode_kernel<false, false, LDS_RESIDENT, MAXD, LLR_MODE, true>;
-    }
-    else
-    {
-        k = want_llr ? decode_kernel<false, true, LDS_RESIDENT, MAXD, LLR_MODE, false>
-                     : decode_kernel<false, false, LDS_RESIDENT, MAXD, LLR_MODE, false>;
-    }
-    // the instantiations for small codes: at most kW5VnBlocks VN blocks per wave, message byte offsets within 16 bits
-    [[maybe_unused]] const bool few_vn_blocks = a.plan.vn_work_stride <= kW5VnBlocks && 8 * a.plan.nnz < 65536;
-    if constexpr (LDS_RESIDENT && MAXD == 4 && LLR_MODE == kLlrRegs)
-        if (!want_llr && few_vn_blocks)
+    case Stage::kWhole:
+        if (min_sum && ms_correct) // corrected min-sum: the same choice among its own instantiations
         {
-            if (min_sum)
-                k = decode_kernel_w5<true, false, LDS_RESIDENT, MAXD, LLR_MODE, false>;
-            else if (ratio)
-                k = decode_kernel_w5<false, false, LDS_RESIDENT, MAXD, LLR_MODE, true>;
+            if constexpr (kHasW5 && !WANT_LLR)
+                if (w5)
+                    return decode_msc_w5<MAXD, LLR_MODE>;
+            return decode_msc_kernel<WANT_LLR, LDS_RESIDENT, MAXD, LLR_MODE>;
         }
-    if (min_sum && a.ms_correct) // corrected min-sum: the same choice among its own instantiations
-    {
-        k = want_llr ? decode_msc_kernel<true, LDS_RESIDENT, MAXD, LLR_MODE> : decode_msc_kernel<false, LDS_RESIDENT, MAXD, LLR_MODE>;
-        if constexpr (LDS_RESIDENT && MAXD == 4 && LLR_MODE == kLlrRegs)
-            if (!want_llr && few_vn_blocks)
-                k = decode_msc_w5<MAXD, LLR_MODE>;
-    }
-    if constexpr (LDS_RESIDENT)
-    {
-        if (handover)
+        if (min_sum)
         {
-            k = want_llr ? decode_kernel_handover<true, MAXD, LLR_MODE> : decode_kernel_handover<false, MAXD, LLR_MODE>;
-            if constexpr (MAXD == 4 && LLR_MODE == kLlrRegs)
-                if (few_vn_blocks)
-                    k = want_llr ? decode_kernel_handover<true, MAXD, LLR_MODE, kW5VnBlocks> : decode_kernel_handover<false, MAXD, LLR_MODE, kW5VnBlocks>;
+            if constexpr (kHasW5 && !WANT_LLR)
+                if (w5)
+                    return decode_kernel_w5<true, false, LDS_RESIDENT, MAXD, LLR_MODE, false>;
+            return decode_kernel<true, WANT_LLR, LDS_RESIDENT, MAXD, LLR_MODE, false>;
         }
-        else if (list_chain)
-            k = want_llr ? decode_kernel_list<true, MAXD, LLR_MODE> : decode_kernel_list<false, MAXD, LLR_MODE>;
+        [[fallthrough]];
+    case Stage::kLlrRedo:
+    case Stage::kHandoverResume: // the LLR-domain form: over the batch, or over the list that came in (the kernel looks)
+        return decode_kernel<false, WANT_LLR, LDS_RESIDENT, MAXD, LLR_MODE, false>;
+    case Stage::kRatioFirst:
+        if constexpr (kHasW5 && !WANT_LLR)
+            if (w5)
+                return decode_kernel_w5<false, false, LDS_RESIDENT, MAXD, LLR_MODE, true>;
+        return decode_kernel<false, WANT_LLR, LDS_RESIDENT, MAXD, LLR_MODE, true>;
+    case Stage::kRatioSeparate: // (only check nodes of degree 6 share reciprocals in the first launch)
+        if constexpr (!LDS_RESIDENT && MAXD >= 6)
+            return decode_kernel<false, WANT_LLR, false, MAXD, LLR_MODE, true, true>;
+        break;
+    case Stage::kListChain:
+        if constexpr (LDS_RESIDENT)
+            return decode_kernel_list<WANT_LLR, MAXD, LLR_MODE>;
+        break;
+    case Stage::kHandoverFirst: // (the memory-resident decoder runs the LLR-domain form when early termination is off)
+        if constexpr (kHasW5)
+            if (w5)
+                return decode_kernel_handover<WANT_LLR, MAXD, LLR_MODE, kW5VnBlocks>;
+        if constexpr (LDS_RESIDENT)
+            return decode_kernel_handover<WANT_LLR, MAXD, LLR_MODE>;
+        break;
     }
-    if constexpr (!LDS_RESIDENT && MAXD >= 6)
-        if (ratio && a.ratio_separate)
-            k = want_llr ? decode_kernel<false, true, false, MAXD, LLR_MODE, true, true> : decode_kernel<false, false, false, MAXD, LLR_MODE, true, true>;
-    if (handover && !LDS_RESIDENT)
-        return hipErrorInvalidValue; // (the memory-resident decoder runs the LLR-domain form when early termination is off)
+    return nullptr;
+}
+
+template <bool LDS_RESIDENT, int MAXD, int LLR_MODE>
+int launch_decode_impl(const DecodeArgs &a, Stage stage, bool min_sum, uint32_t lds_bytes, void *stream)
+{
+    if (!stage_args_ok(a, stage) || (min_sum && stage != Stage::kWhole))
+        return hipErrorInvalidValue;
+    const bool w5 = a.plan.vn_work_stride <= kW5VnBlocks && 8 * a.plan.nnz < 65536;
+    const DecodeKernel k = a.llr_out ? decode_kernel_of<true, LDS_RESIDENT, MAXD, LLR_MODE>(stage, min_sum, a.ms_correct, w5)
+                                     : decode_kernel_of<false, LDS_RESIDENT, MAXD, LLR_MODE>(stage, min_sum, a.ms_correct, w5);
+    if (!k)
+        return hipErrorInvalidValue;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        static_cast<int>(lds_bytes));
     if (e != hipSuccess)
         return e;
-    const unsigned grid = list_chain ? static_cast<unsigned>(std::min<uint64_t>(a.n_frames, 1024)) : static_cast<unsigned>(a.n_frames);
+    // (the chain kernel's small grid walks the list)
+    const unsigned grid = static_cast<unsigned>(stage == Stage::kListChain ? std::min<uint64_t>(a.n_frames, 1024) : a.n_frames);
     hipLaunchKernelGGL(k, dim3(grid), dim3(kThreads), lds_bytes, static_cast<hipStream_t>(stream), a);
     return hipGetLastError();
 }
 
 template <bool LDS_RESIDENT, int MAXD, int LLR_MODE>
-int launch_decode(const DecodeArgs &a, bool min_sum, uint32_t lds_bytes, void *stream)
+int launch_decode(const DecodeArgs &a, Stage stage, bool min_sum, uint32_t lds_bytes, void *stream)
 {
 #ifdef LDPC_AMD_HEADLINE_SHAPE_ONLY // register-allocation experiments: one code shape, a fraction of the build time
     if constexpr (!(LDS_RESIDENT && MAXD == 4 && LLR_MODE == kLlrRegs))
         return hipErrorInvalidValue;
     else
 #endif
-        return launch_decode_impl<LDS_RESIDENT, MAXD, LLR_MODE>(a, min_sum, lds_bytes, stream);
+        return launch_decode_impl<LDS_RESIDENT, MAXD, LLR_MODE>(a, stage, min_sum, lds_bytes, stream);
 }
 
 } // namespace
 
-int launch_decode_lds(const DecodeArgs &a, bool min_sum, int max_cn_degree, int llr_mode, void *stream)
+int launch_decode_lds(const DecodeArgs &a, Stage stage, bool min_sum, int max_cn_degree, int llr_mode, void *stream)
 {
     if (a.n_frames == 0)
         return hipSuccess;
     if (llr_mode == kLlrRegs && (a.plan.vn_work_stride > kMaxVnBlocksInRegs || a.plan.nc > a.plan.nnz || !a.plan.vn_packed))
         return hipErrorInvalidValue;
     uint32_t lds = a.plan.lds_bytes - (llr_mode == kLlrRegs ? 8u * static_cast<uint32_t>(a.plan.nc) : 0u);
-    if (a.redo_list) // ratio form: no hard-bit array (the last array of the frame in every layout)
+    // ratio form over the batch: no hard-bit array (the last array of the frame in every layout)
+    if (stage == Stage::kRatioFirst || stage == Stage::kHandoverFirst)
         lds -= ((static_cast<uint32_t>(a.plan.nnz) + 15u) / 16u) * 16u;
 #define LDPC_PICK(D)                                                                                                  \
-    return llr_mode == kLlrRegs ? launch_decode<true, D, kLlrRegs>(a, min_sum, lds, stream)                             \
-                                : launch_decode<true, D, kLlrLds>(a, min_sum, lds, stream);
+    return llr_mode == kLlrRegs ? launch_decode<true, D, kLlrRegs>(a, stage, min_sum, lds, stream)                      \
+                                : launch_decode<true, D, kLlrLds>(a, stage, min_sum, lds, stream);
     if (max_cn_degree <= 4)
     {
         LDPC_PICK(4)
@@ -2407,19 +2405,19 @@ int launch_decode_lds(const DecodeArgs &a, bool min_sum, int max_cn_degree, int 
     return hipErrorInvalidValue;
 }
 
-int launch_decode_mem(const DecodeArgs &a, bool min_sum, int max_cn_degree, uint32_t occupancy_lds, void *stream)
+int launch_decode_mem(const DecodeArgs &a, Stage stage, bool min_sum, int max_cn_degree, uint32_t occupancy_lds, void *stream)
 {
     if (a.n_frames == 0)
         return hipSuccess;
     if (!a.ws_msg || !a.ws_llr || !a.ws_hb)
         return hipErrorInvalidValue;
     if (max_cn_degree <= 4)
-        return launch_decode<false, 4, kLlrMem>(a, min_sum, occupancy_lds, stream);
+        return launch_decode<false, 4, kLlrMem>(a, stage, min_sum, occupancy_lds, stream);
     if (max_cn_degree <= 8)
-        return launch_decode<false, 8, kLlrMem>(a, min_sum, occupancy_lds, stream);
-    if (max_cn_degree > 16 && (!a.ws_scr || a.redo_list)) // wide nodes: scratch needed, no likelihood-ratio form
+        return launch_decode<false, 8, kLlrMem>(a, stage, min_sum, occupancy_lds, stream);
+    if (max_cn_degree > 16 && (!a.ws_scr || stage != Stage::kWhole)) // wide nodes: scratch needed, no likelihood-ratio form
         return hipErrorInvalidValue;
-    return launch_decode<false, 16, kLlrMem>(a, min_sum, occupancy_lds, stream);
+    return launch_decode<false, 16, kLlrMem>(a, stage, min_sum, occupancy_lds, stream);
 }
 
 int launch_batch_counters(const uint32_t *iters, const uint32_t *bit_errors, uint64_t n, uint32_t max_iters, int early_term,

@@ -1,6 +1,7 @@
 // kernels.hpp — host-visible launch interface of the HIP kernels (kernels.hip).
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 
 #include "plan.hpp"
@@ -86,15 +87,17 @@ struct DecodeArgs
     uint8_t *ws_hb;  // [n_frames][nnz]
     double *ws_scr;  // [n_frames][2 nnz] scratch of check nodes wider than 16 (nullptr when the code has none);
                      // totals-form register kernel: [n_frames][(nv0 + nv1) * nt] channel terms of the variable nodes
-    // sum-product in likelihood-ratio form (detmath.h): when redo_list is set the launch runs that form and
-    // appends the frames it could not finish to redo_list[atomicAdd(redo_count)]; a launch with redo_list_in /
-    // redo_count_in set decodes exactly those frames (block b takes frame redo_list_in[b], b < *redo_count_in)
+    // sum-product in likelihood-ratio form (detmath.h), the lists of a launch's Stage (below): a stage that hands frames on
+    // appends the frames it could not finish to redo_list[atomicAdd(redo_count)]; a stage that reads a list decodes exactly
+    // those frames (block b takes frame redo_list_in[b], b < *redo_count_in; kListChain: a small grid walks the list)
     uint32_t *redo_list;
     uint32_t *redo_count;
-    int ratio_separate; // ratio form with every check-node output divided separately (the middle launch of three, LDS-resident)
+    // unused, kept in place: moving or removing a host-only member of this struct changed the compiler's register allocation
+    // and scratch use of dozens of kernel instantiations that take it by value (the static_asserts below hold the layout)
+    int ratio_separate;
     const uint32_t *redo_list_in;
     const uint32_t *redo_count_in;
-    // hand-over (sum-product without early termination, detmath.h "Hand-over"): redo_iter[pos] = iteration the frame
+    // hand-over (kHandoverFirst -> kHandoverResume; detmath.h "Hand-over"): redo_iter[pos] = iteration the frame
     // redo_list[pos] resumes at in the LLR domain (0xFFFFFFFF: decode it from scratch), ws_handover[pos][nnz] = its c2v
     // messages as the ratio form left them (lambda, a decision in the sign bit), in message-slot order
     uint32_t *redo_iter;
@@ -110,6 +113,43 @@ struct DecodeArgs
     int ms_correct;
     double ms_scale, ms_offset;
 };
+// the kernels take DecodeArgs by value and their register allocation follows its layout: no member moves
+static_assert(sizeof(DecodeArgs) == 512 && offsetof(DecodeArgs, plan) == 0 && offsetof(DecodeArgs, iterations) == 168 &&
+                  offsetof(DecodeArgs, redo_list) == 392 && offsetof(DecodeArgs, ratio_separate) == 408 &&
+                  offsetof(DecodeArgs, redo_list_in) == 416 && offsetof(DecodeArgs, ms_correct) == 488 &&
+                  offsetof(DecodeArgs, ms_offset) == 504,
+              "DecodeArgs: layout changed");
+
+// What one decode launch is for.  A batch takes one to three launches (engine.hpp, decode_stages); the
+// stage says which form runs and which lists the launch reads and writes.
+enum class Stage : int
+{
+    kWhole,          // no list: min-sum, the LLR-domain sum-product from scratch, the fast / layered modes
+    kRatioFirst,     // list out: ratio form over the batch, early termination on
+    kRatioSeparate,  // lists in and out: ratio form again, every check-node output divided separately (not LDS-resident)
+    kListChain,      // list in: separately divided ratio form, then the LLR domain, frame by frame (LDS-resident)
+    kLlrRedo,        // list in: the listed frames from scratch in the LLR domain
+    kHandoverFirst,  // list out + redo_iter, ws_handover: ratio form without early termination (LDS-resident)
+    kHandoverResume, // list in + redo_iter_in, ws_handover, handover_llr: the LLR domain resuming those frames
+};
+constexpr bool stage_writes_list(Stage s) { return s == Stage::kRatioFirst || s == Stage::kRatioSeparate || s == Stage::kHandoverFirst; }
+constexpr bool stage_reads_list(Stage s)
+{
+    return s == Stage::kRatioSeparate || s == Stage::kListChain || s == Stage::kLlrRedo || s == Stage::kHandoverResume;
+}
+constexpr bool stage_is_handover(Stage s) { return s == Stage::kHandoverFirst || s == Stage::kHandoverResume; }
+// every launcher's one check of the arguments: the pointers the stage needs are there, and the stages of the ratio form
+// (iterations to run; early termination on, or the hand-over without it) are what the arguments describe
+inline bool stage_args_ok(const DecodeArgs &a, Stage s)
+{
+    if (stage_writes_list(s) && (!a.redo_list || !a.redo_count))
+        return false;
+    if (stage_reads_list(s) && (!a.redo_list_in || !a.redo_count_in))
+        return false;
+    if (stage_is_handover(s) && (!a.ws_handover || !(s == Stage::kHandoverFirst ? a.redo_iter : a.redo_iter_in)))
+        return false;
+    return s == Stage::kWhole || (a.iterations > 0 && stage_is_handover(s) == !a.early_term);
+}
 
 // device copy of RegPlan (register-resident decoder, kernels_reg.hip)
 struct DevRegPlan
@@ -155,13 +195,9 @@ struct DevFusedPlan
     const uint32_t *lane_tab;    // [kDecodeWaves][kFusedLaneRows][64]
     const uint32_t *ho_map;      // [n_slots] (plan.hpp, FusedPlan::ho_map)
 };
-// first launch of sum-product with early termination (a.redo_list / a.redo_count set, a.early_term, no a.redo_count_in)
-int launch_decode_fused(const DecodeArgs &a, const DevFusedPlan &f, void *stream);
-// the same form WITHOUT early termination: separately divided outputs, hand-over to the LLR-domain form (a.redo_iter,
-// a.ws_handover as for the general kernel; the messages arrive there as LLRs: set handover_llr for the resuming launch)
-int launch_decode_fused_handover(const DecodeArgs &a, const DevFusedPlan &f, void *stream);
-// min-sum without early termination on the same plan (no redo lists)
-int launch_decode_fused_minsum(const DecodeArgs &a, const DevFusedPlan &f, void *stream);
+// the fused family on the LDS-resident decoder's plan: kRatioFirst, kHandoverFirst (separately divided outputs; the messages
+// are handed over as LLRs: handover_llr for the resuming launch) and kWhole = min-sum without early termination
+int launch_decode_fused(const DecodeArgs &a, const DevFusedPlan &f, Stage stage, void *stream);
 
 // BEC (u8 erasure alphabet, decoder.cpp:91-192 + channel.cpp:199-229)
 struct BecArgs
@@ -194,14 +230,14 @@ int launch_bec_sliced(const BecArgs &a, void *stream);
 // All launchers enqueue on `stream` (hipStream_t passed as void*) and return a hipError_t as int.
 // LDS-resident decoder; llr_mode: 0 input LLRs in LDS, 2 in registers (needs plan.vn_work_stride <= 8 and no isolated
 // variable node)
-int launch_decode_lds(const DecodeArgs &a, bool min_sum, int max_cn_degree, int llr_mode, void *stream);
+int launch_decode_lds(const DecodeArgs &a, Stage stage, bool min_sum, int max_cn_degree, int llr_mode, void *stream);
 // memory-resident variant for codes whose messages do not fit LDS (a.ws_* must be set); occupancy_lds
 // bytes of dynamic LDS are requested only to bound the number of resident frames per CU
-int launch_decode_mem(const DecodeArgs &a, bool min_sum, int max_cn_degree, uint32_t occupancy_lds, void *stream);
+int launch_decode_mem(const DecodeArgs &a, Stage stage, bool min_sum, int max_cn_degree, uint32_t occupancy_lds, void *stream);
 // register-resident decoder: a.ws_llr [n][nc] doubles and a.ws_hb [n][nc] bytes must be set
-int launch_decode_reg(const DecodeArgs &a, const DevRegPlan &r, bool min_sum, void *stream);
+int launch_decode_reg(const DecodeArgs &a, const DevRegPlan &r, Stage stage, bool min_sum, void *stream);
 // register-resident decoder, second form (same workspace requirements)
-int launch_decode_reg2(const DecodeArgs &a, const DevReg2Plan &r, bool min_sum, void *stream);
+int launch_decode_reg2(const DecodeArgs &a, const DevReg2Plan &r, Stage stage, bool min_sum, void *stream);
 // opt-in non-parity fast mode (kernels_fast.hip): sum-product with binary32 messages; a.ws_hb [n][nc] must be set
 bool fast_mode_supported(const DevPlan &p, int max_cn_degree);
 int launch_decode_fast(const DecodeArgs &a, int max_cn_degree, void *stream);

@@ -1371,108 +1371,56 @@ __global__ __launch_bounds__(kThreads) void decode_fused_msc_kernel(const Decode
     fused_ms_body<WANT_LLR, VNB, CNL, NK, true>(a, f);
 }
 
-bool counter_args(const DecodeArgs &a) { return a.mode == kModeAwgnCtr || a.mode == kModeBscCtr; }
+using FusedKernel = void (*)(const DecodeArgs, const DevFusedPlan);
+
+// The kernel of a stage (null: the fused family has none).  exclusive: the plan's wide_exclusive, which together with no LLR
+// output and the <4, 1> shape selects the small instantiations; counter: the counter-based noise mode
+template <bool WANT_LLR, int VNB, int CNL>
+FusedKernel fused_kernel_of(Stage stage, bool counter, bool ms_correct, [[maybe_unused]] bool exclusive)
+{
+    constexpr bool kHasSmall = !WANT_LLR && VNB == 4 && CNL == 1;
+    switch (stage)
+    {
+    case Stage::kRatioFirst:
+        if constexpr (kHasSmall)
+            if (exclusive)
+                return counter ? decode_ctr_fused_small : decode_fused_small;
+        return counter ? decode_ctr_fused_kernel<WANT_LLR, VNB, CNL> : decode_fused_kernel<WANT_LLR, VNB, CNL>;
+    case Stage::kHandoverFirst:
+        if constexpr (kHasSmall)
+            if (exclusive)
+                return counter ? decode_ctr_fused_ho_small : decode_fused_ho_small;
+        return counter ? decode_ctr_fused_ho_kernel<WANT_LLR, VNB, CNL> : decode_fused_ho_kernel<WANT_LLR, VNB, CNL>;
+    case Stage::kWhole: // min-sum
+        if (ms_correct)
+            return counter ? decode_fused_msc_kernel<WANT_LLR, VNB, CNL, kNoiseCounter> : decode_fused_msc_kernel<WANT_LLR, VNB, CNL, kNoiseStream>;
+        return counter ? decode_ctr_fused_ms_kernel<WANT_LLR, VNB, CNL> : decode_fused_ms_kernel<WANT_LLR, VNB, CNL>;
+    default:
+        return nullptr;
+    }
+}
 
 } // namespace
 
-int launch_decode_fused(const DecodeArgs &a, const DevFusedPlan &f, void *stream)
+int launch_decode_fused(const DecodeArgs &a, const DevFusedPlan &f, Stage stage, void *stream)
 {
     if (a.n_frames == 0)
         return hipSuccess;
-    if (!a.redo_list || !a.redo_count || a.redo_count_in || !a.early_term || a.iterations == 0 || a.ratio_separate)
+    // (min-sum on this plan: without early termination only)
+    if (!stage_args_ok(a, stage) || (stage == Stage::kWhole && (a.early_term || a.iterations == 0)))
         return hipErrorInvalidValue;
     if (f.vnb > kFusedVnSlots || f.cnl > kFusedLeafCalls)
         return hipErrorInvalidValue;
-    const bool want_llr = a.llr_out != nullptr;
-    void (*k)(const DecodeArgs, const DevFusedPlan) = nullptr;
+    const bool counter = a.mode == kModeAwgnCtr || a.mode == kModeBscCtr, exclusive = f.wide_exclusive != 0;
+    FusedKernel k = nullptr;
     if (f.vnb <= 4 && f.cnl <= 1)
-        k = (want_llr || !f.wide_exclusive) ? (want_llr ? decode_fused_kernel<true, 4, 1> : decode_fused_kernel<false, 4, 1>) : decode_fused_small;
+        k = a.llr_out ? fused_kernel_of<true, 4, 1>(stage, counter, a.ms_correct, exclusive)
+                      : fused_kernel_of<false, 4, 1>(stage, counter, a.ms_correct, exclusive);
     else
-        k = want_llr ? decode_fused_kernel<true, kFusedVnSlots, kFusedLeafCalls> : decode_fused_kernel<false, kFusedVnSlots, kFusedLeafCalls>;
-    if (counter_args(a))
-    {
-        if (f.vnb <= 4 && f.cnl <= 1)
-            k = (want_llr || !f.wide_exclusive) ? (want_llr ? decode_ctr_fused_kernel<true, 4, 1> : decode_ctr_fused_kernel<false, 4, 1>)
-                                                : decode_ctr_fused_small;
-        else
-            k = want_llr ? decode_ctr_fused_kernel<true, kFusedVnSlots, kFusedLeafCalls>
-                         : decode_ctr_fused_kernel<false, kFusedVnSlots, kFusedLeafCalls>;
-    }
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(f.lds_bytes));
-    if (e != hipSuccess)
-        return e;
-    hipLaunchKernelGGL(k, dim3(static_cast<unsigned>(a.n_frames)), dim3(kThreads), f.lds_bytes, static_cast<hipStream_t>(stream), a, f);
-    return hipGetLastError();
-}
-
-int launch_decode_fused_handover(const DecodeArgs &a, const DevFusedPlan &f, void *stream)
-{
-    if (a.n_frames == 0)
-        return hipSuccess;
-    if (!a.redo_list || !a.redo_count || !a.redo_iter || !a.ws_handover || a.redo_count_in || a.early_term || a.iterations == 0)
+        k = a.llr_out ? fused_kernel_of<true, kFusedVnSlots, kFusedLeafCalls>(stage, counter, a.ms_correct, exclusive)
+                      : fused_kernel_of<false, kFusedVnSlots, kFusedLeafCalls>(stage, counter, a.ms_correct, exclusive);
+    if (!k)
         return hipErrorInvalidValue;
-    if (f.vnb > kFusedVnSlots || f.cnl > kFusedLeafCalls)
-        return hipErrorInvalidValue;
-    const bool want_llr = a.llr_out != nullptr;
-    void (*k)(const DecodeArgs, const DevFusedPlan) = nullptr;
-    if (f.vnb <= 4 && f.cnl <= 1)
-        k = (want_llr || !f.wide_exclusive) ? (want_llr ? decode_fused_ho_kernel<true, 4, 1> : decode_fused_ho_kernel<false, 4, 1>) : decode_fused_ho_small;
-    else
-        k = want_llr ? decode_fused_ho_kernel<true, kFusedVnSlots, kFusedLeafCalls> : decode_fused_ho_kernel<false, kFusedVnSlots, kFusedLeafCalls>;
-    if (counter_args(a))
-    {
-        if (f.vnb <= 4 && f.cnl <= 1)
-            k = (want_llr || !f.wide_exclusive) ? (want_llr ? decode_ctr_fused_ho_kernel<true, 4, 1> : decode_ctr_fused_ho_kernel<false, 4, 1>)
-                                                : decode_ctr_fused_ho_small;
-        else
-            k = want_llr ? decode_ctr_fused_ho_kernel<true, kFusedVnSlots, kFusedLeafCalls>
-                         : decode_ctr_fused_ho_kernel<false, kFusedVnSlots, kFusedLeafCalls>;
-    }
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(f.lds_bytes));
-    if (e != hipSuccess)
-        return e;
-    hipLaunchKernelGGL(k, dim3(static_cast<unsigned>(a.n_frames)), dim3(kThreads), f.lds_bytes, static_cast<hipStream_t>(stream), a, f);
-    return hipGetLastError();
-}
-
-int launch_decode_fused_minsum(const DecodeArgs &a, const DevFusedPlan &f, void *stream)
-{
-    if (a.n_frames == 0)
-        return hipSuccess;
-    if (a.early_term || a.iterations == 0 || a.redo_list || a.redo_count_in)
-        return hipErrorInvalidValue;
-    if (f.vnb > kFusedVnSlots || f.cnl > kFusedLeafCalls)
-        return hipErrorInvalidValue;
-    const bool want_llr = a.llr_out != nullptr;
-    void (*k)(const DecodeArgs, const DevFusedPlan) = nullptr;
-    if (f.vnb <= 4 && f.cnl <= 1)
-        k = want_llr ? decode_fused_ms_kernel<true, 4, 1> : decode_fused_ms_kernel<false, 4, 1>;
-    else
-        k = want_llr ? decode_fused_ms_kernel<true, kFusedVnSlots, kFusedLeafCalls> : decode_fused_ms_kernel<false, kFusedVnSlots, kFusedLeafCalls>;
-    if (counter_args(a))
-    {
-        if (f.vnb <= 4 && f.cnl <= 1)
-            k = want_llr ? decode_ctr_fused_ms_kernel<true, 4, 1> : decode_ctr_fused_ms_kernel<false, 4, 1>;
-        else
-            k = want_llr ? decode_ctr_fused_ms_kernel<true, kFusedVnSlots, kFusedLeafCalls>
-                         : decode_ctr_fused_ms_kernel<false, kFusedVnSlots, kFusedLeafCalls>;
-    }
-    if (a.ms_correct)
-    {
-#define LDPC_MSC(NK)                                                                                                                 \
-    k = (f.vnb <= 4 && f.cnl <= 1) ? (want_llr ? decode_fused_msc_kernel<true, 4, 1, NK> : decode_fused_msc_kernel<false, 4, 1, NK>) \
-                                   : (want_llr ? decode_fused_msc_kernel<true, kFusedVnSlots, kFusedLeafCalls, NK>                   \
-                                               : decode_fused_msc_kernel<false, kFusedVnSlots, kFusedLeafCalls, NK>);
-        if (counter_args(a))
-        {
-            LDPC_MSC(kNoiseCounter)
-        }
-        else
-        {
-            LDPC_MSC(kNoiseStream)
-        }
-#undef LDPC_MSC
-    }
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(f.lds_bytes));
     if (e != hipSuccess)
         return e;

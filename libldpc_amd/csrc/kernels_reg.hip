@@ -106,24 +106,39 @@ __global__ __launch_bounds__(NT) void decode_reg_msc_kernel(const DecodeArgs a, 
 #include "kernels_reg_body.inc"
 }
 
-template <int NT, int KC, int MAXD>
-int launch_reg(const DecodeArgs &a, const DevRegPlan &r, bool min_sum, void *stream)
+using RegKernel = void (*)(const DecodeArgs, const DevRegPlan);
+
+// the kernel of a stage (null: none here).  The first ratio launch shares the reciprocals of degree-6 check nodes (SH6); the
+// second, over its list, divides every output separately.
+template <bool WANT_LLR, int NT, int KC, int MAXD>
+RegKernel reg_kernel_of(Stage stage, bool min_sum, bool ms_correct)
 {
-    const bool want_llr = a.llr_out != nullptr;
-    const bool ratio = a.redo_list != nullptr; // (with a list coming in as well: the second launch, outputs divided separately)
-    if (ratio && (min_sum || !a.early_term || a.iterations == 0 || !a.redo_count))
+    switch (stage)
+    {
+    case Stage::kWhole:
+        if (min_sum)
+            return ms_correct ? decode_reg_msc_kernel<WANT_LLR, NT, KC, MAXD> : decode_reg_kernel<true, WANT_LLR, NT, KC, MAXD, false>;
+        [[fallthrough]];
+    case Stage::kLlrRedo:
+        return decode_reg_kernel<false, WANT_LLR, NT, KC, MAXD, false>;
+    case Stage::kRatioFirst:
+        return decode_reg_kernel<false, WANT_LLR, NT, KC, MAXD, true, MAXD >= 6>;
+    case Stage::kRatioSeparate:
+        return decode_reg_kernel<false, WANT_LLR, NT, KC, MAXD, true>;
+    default:
+        return nullptr;
+    }
+}
+
+template <int NT, int KC, int MAXD>
+int launch_reg(const DecodeArgs &a, const DevRegPlan &r, Stage stage, bool min_sum, void *stream)
+{
+    if (!stage_args_ok(a, stage) || (min_sum && stage != Stage::kWhole))
         return hipErrorInvalidValue;
-    void (*k)(const DecodeArgs, const DevRegPlan) = nullptr;
-    if (min_sum)
-        k = want_llr ? decode_reg_kernel<true, true, NT, KC, MAXD, false> : decode_reg_kernel<true, false, NT, KC, MAXD, false>;
-    else if (ratio && !a.redo_count_in && MAXD >= 6)
-        k = want_llr ? decode_reg_kernel<false, true, NT, KC, MAXD, true, MAXD >= 6> : decode_reg_kernel<false, false, NT, KC, MAXD, true, MAXD >= 6>;
-    else if (ratio)
-        k = want_llr ? decode_reg_kernel<false, true, NT, KC, MAXD, true> : decode_reg_kernel<false, false, NT, KC, MAXD, true>;
-    else
-        k = want_llr ? decode_reg_kernel<false, true, NT, KC, MAXD, false> : decode_reg_kernel<false, false, NT, KC, MAXD, false>;
-    if (min_sum && a.ms_correct)
-        k = want_llr ? decode_reg_msc_kernel<true, NT, KC, MAXD> : decode_reg_msc_kernel<false, NT, KC, MAXD>;
+    const RegKernel k = a.llr_out ? reg_kernel_of<true, NT, KC, MAXD>(stage, min_sum, a.ms_correct)
+                                  : reg_kernel_of<false, NT, KC, MAXD>(stage, min_sum, a.ms_correct);
+    if (!k)
+        return hipErrorInvalidValue;
     const uint32_t lds = r.mb_doubles * 9u;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        static_cast<int>(lds));
@@ -135,7 +150,7 @@ int launch_reg(const DecodeArgs &a, const DevRegPlan &r, bool min_sum, void *str
 
 } // namespace
 
-int launch_decode_reg(const DecodeArgs &a, const DevRegPlan &r, bool min_sum, void *stream)
+int launch_decode_reg(const DecodeArgs &a, const DevRegPlan &r, Stage stage, bool min_sum, void *stream)
 {
     if (a.n_frames == 0)
         return hipSuccess;
@@ -143,7 +158,7 @@ int launch_decode_reg(const DecodeArgs &a, const DevRegPlan &r, bool min_sum, vo
         return hipErrorInvalidValue;
 #define LDPC_TILE(N, K, D)                      \
     if (r.nt == N && r.kc == K && r.maxd == D)  \
-        return launch_reg<N, K, D>(a, r, min_sum, stream);
+        return launch_reg<N, K, D>(a, r, stage, min_sum, stream);
     LDPC_TILE(512, 8, 6)
     LDPC_TILE(512, 16, 4)
     LDPC_TILE(512, 4, 8)

@@ -634,50 +634,44 @@ __global__ __launch_bounds__(NT) void decode_reg2_msc_kernel(const DecodeArgs a,
     reg2_kernel_body<true, WANT_LLR, NT, KC, MAXD, NV0, NV1, false, U, NK, true>(a, R);
 }
 
+using Reg2Kernel = void (*)(const DecodeArgs, const DevReg2Plan);
+
+// the kernel of a stage (null: none here): the chain of all three forms for the first launch of sum-product with early
+// termination — it hands nothing back, so the decoder has no stage over a list.  counter: the counter-based noise mode
+template <bool WANT_LLR, int NT, int KC, int MAXD, int NV0, int NV1, bool U>
+Reg2Kernel reg2_kernel_of(Stage stage, bool min_sum, bool ms_correct, bool counter)
+{
+    switch (stage)
+    {
+    case Stage::kWhole:
+        if (min_sum && ms_correct)
+            return counter ? decode_reg2_msc_kernel<WANT_LLR, NT, KC, MAXD, NV0, NV1, U, kNoiseCounter>
+                           : decode_reg2_msc_kernel<WANT_LLR, NT, KC, MAXD, NV0, NV1, U, kNoiseStream>;
+        if (min_sum)
+            return counter ? decode_reg2_ctr_kernel<true, WANT_LLR, NT, KC, MAXD, NV0, NV1, false, U>
+                           : decode_reg2_kernel<true, WANT_LLR, NT, KC, MAXD, NV0, NV1, false, U>;
+        return counter ? decode_reg2_ctr_kernel<false, WANT_LLR, NT, KC, MAXD, NV0, NV1, false, U>
+                       : decode_reg2_kernel<false, WANT_LLR, NT, KC, MAXD, NV0, NV1, false, U>;
+    case Stage::kRatioFirst:
+        return counter ? decode_reg2_ctr_kernel<false, WANT_LLR, NT, KC, MAXD, NV0, NV1, true, U>
+                       : decode_reg2_kernel<false, WANT_LLR, NT, KC, MAXD, NV0, NV1, true, U>;
+    default:
+        return nullptr;
+    }
+}
+
 // U: the regular code's instantiation (no switch over check-node degrees, straight-line variable-node rounds), or the
 // generic one
 template <int NT, int KC, int MAXD, int NV0, int NV1, bool U>
-int launch_reg2(const DecodeArgs &a, const DevReg2Plan &r, bool min_sum, void *stream)
+int launch_reg2(const DecodeArgs &a, const DevReg2Plan &r, Stage stage, bool min_sum, void *stream)
 {
-    const bool want_llr = a.llr_out != nullptr;
-    // the caller's first launch of sum-product with early termination (a list to hand frames back in): the chain kernel,
-    // which hands nothing back; its later launches over those lists have nothing to do
-    const bool chain = a.redo_list != nullptr;
-    if (chain && (min_sum || !a.early_term || a.iterations == 0))
+    if (!stage_args_ok(a, stage) || (min_sum && stage != Stage::kWhole))
         return hipErrorInvalidValue;
-    if (a.redo_count_in)
-        return min_sum ? hipErrorInvalidValue : hipSuccess;
-    void (*k)(const DecodeArgs, const DevReg2Plan) = nullptr;
-    if (min_sum)
-        k = want_llr ? decode_reg2_kernel<true, true, NT, KC, MAXD, NV0, NV1, false, U>
-                     : decode_reg2_kernel<true, false, NT, KC, MAXD, NV0, NV1, false, U>;
-    else if (chain)
-        k = want_llr ? decode_reg2_kernel<false, true, NT, KC, MAXD, NV0, NV1, true, U>
-                     : decode_reg2_kernel<false, false, NT, KC, MAXD, NV0, NV1, true, U>;
-    else
-        k = want_llr ? decode_reg2_kernel<false, true, NT, KC, MAXD, NV0, NV1, false, U>
-                     : decode_reg2_kernel<false, false, NT, KC, MAXD, NV0, NV1, false, U>;
-    if (a.mode == kModeAwgnCtr || a.mode == kModeBscCtr)
-    {
-        if (min_sum)
-            k = want_llr ? decode_reg2_ctr_kernel<true, true, NT, KC, MAXD, NV0, NV1, false, U>
-                         : decode_reg2_ctr_kernel<true, false, NT, KC, MAXD, NV0, NV1, false, U>;
-        else if (chain)
-            k = want_llr ? decode_reg2_ctr_kernel<false, true, NT, KC, MAXD, NV0, NV1, true, U>
-                         : decode_reg2_ctr_kernel<false, false, NT, KC, MAXD, NV0, NV1, true, U>;
-        else
-            k = want_llr ? decode_reg2_ctr_kernel<false, true, NT, KC, MAXD, NV0, NV1, false, U>
-                         : decode_reg2_ctr_kernel<false, false, NT, KC, MAXD, NV0, NV1, false, U>;
-    }
-    if (min_sum && a.ms_correct)
-    {
-        if (a.mode == kModeAwgnCtr || a.mode == kModeBscCtr)
-            k = want_llr ? decode_reg2_msc_kernel<true, NT, KC, MAXD, NV0, NV1, U, kNoiseCounter>
-                         : decode_reg2_msc_kernel<false, NT, KC, MAXD, NV0, NV1, U, kNoiseCounter>;
-        else
-            k = want_llr ? decode_reg2_msc_kernel<true, NT, KC, MAXD, NV0, NV1, U, kNoiseStream>
-                         : decode_reg2_msc_kernel<false, NT, KC, MAXD, NV0, NV1, U, kNoiseStream>;
-    }
+    const bool counter = a.mode == kModeAwgnCtr || a.mode == kModeBscCtr;
+    const Reg2Kernel k = a.llr_out ? reg2_kernel_of<true, NT, KC, MAXD, NV0, NV1, U>(stage, min_sum, a.ms_correct, counter)
+                                   : reg2_kernel_of<false, NT, KC, MAXD, NV0, NV1, U>(stage, min_sum, a.ms_correct, counter);
+    if (!k)
+        return hipErrorInvalidValue;
     const uint32_t lds = r.lds_entries * 8u + 16u;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        static_cast<int>(lds));

@@ -5,9 +5,9 @@
 namespace ldpc_amd
 {
 
-int launch_decode_reg2_regular(const DecodeArgs &a, const DevReg2Plan &r, bool min_sum, void *stream)
+int launch_decode_reg2_regular(const DecodeArgs &a, const DevReg2Plan &r, Stage stage, bool min_sum, void *stream)
 {
-    return launch_reg2<1024, 4, 6, 4, 4, true>(a, r, min_sum, stream);
+    return launch_reg2<1024, 4, 6, 4, 4, true>(a, r, stage, min_sum, stream);
 }
 
 } // namespace ldpc_amd

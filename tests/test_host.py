@@ -235,6 +235,50 @@ def test_fused_plan_of_the_test_code(lib, h8k_file):
     assert libldpc_amd.HipDecoder(h8k_file).fused_plan()["ok"] == 0
 
 
+def test_decode_stage_sequences(lib, h8k_file, tmp_path):
+    """The launches of a batch (DESIGN.md §4 "Launch stages"; engine.hpp, decode_stages) as ldpc_hip_decode_stages reports
+    them, on real codes of every residency: the sequence follows from the residency, degree-6 check nodes off the LDS path,
+    the widest check node and the decoder parameters alone."""
+    import zlib
+    import libldpc_amd
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from test_gpu_random_codes import CASES, make_code, make_code_by_degrees
+    whole = ["whole"]
+    # h.txt: LDS-resident, the fused plan takes it
+    d = libldpc_amd.HipDecoder(orc.H_TXT)
+    assert d.residency == "lds" and d.fused_plan()["ok"] == 1
+    assert d.decode_stages() == d.decode_stages(True, 50, "BP") == ["ratio-first", "list-chain"]
+    assert d.decode_stages(early_term=False) == ["handover-first", "handover-resume"]
+    assert d.decode_stages(decoding="BP_MS") == d.decode_stages(early_term=False, decoding="BP_MS") == whole
+    assert d.decode_stages(iterations=0) == d.decode_stages(early_term=False, iterations=0) == whole
+    for mode in (1, 2, 3):
+        d.set_fast_mode(mode)
+        assert d.decode_stages() == d.decode_stages(early_term=False) == whole, mode
+    d.set_fast_mode(0)
+    assert d.decode_stages() == ["ratio-first", "list-chain"]
+    # the (3,6) n=8192 code: registers, totals form — the chain kernel finishes every frame in the first launch
+    d = libldpc_amd.HipDecoder(h8k_file)
+    assert d.residency == "registers" and d.register_form == "totals"
+    assert d.decode_stages() == ["ratio-first"]
+    assert d.decode_stages(early_term=False) == d.decode_stages(decoding="BP_MS") == d.decode_stages(iterations=0) == whole
+    # a check node of degree 6 off the LDS path, messages form and memory (test_degree6_shared_reciprocals_three_launches)
+    for name, vn, cn, residency, form in (("registers_messages", [1] * 600 + [3] * 7200, [6] * 3700, "registers", "messages"),
+                                          ("memory", [3] * 16384, [6] * 8192, "memory", None)):
+        path = make_code_by_degrees(str(tmp_path / f"{name}.txt"), vn, cn, np.random.default_rng(zlib.crc32(name.encode())))
+        d = libldpc_amd.HipDecoder(path)
+        assert d.residency == residency and d.register_form == form, (name, d.residency, d.register_form)
+        assert d.decode_stages() == ["ratio-first", "ratio-separate", "llr-redo"], name
+        assert d.decode_stages(early_term=False) == d.decode_stages(decoding="BP_MS") == d.decode_stages(iterations=0) == whole, name
+    # off the LDS path without a check node of degree 6: two stages; a check node of degree 20: the LLR domain only
+    for name, stages in (("reg_tile_8x4", ["ratio-first", "llr-redo"]), ("mem_cn12", ["ratio-first", "llr-redo"]), ("mem_cn20", whole)):
+        _, nc, mc, pool, punct, short, skip, residency = [c for c in CASES if c[0] == name][0]
+        rng = np.random.default_rng(zlib.crc32(name.encode()))
+        d = libldpc_amd.HipDecoder(make_code(str(tmp_path / f"{name}.txt"), nc, mc, rng.choice(pool, size=mc), rng, punct, short, skip))
+        assert d.residency == residency and (name != "reg_tile_8x4" or d.register_form == "messages"), (name, d.residency, d.register_form)
+        assert d.decode_stages() == stages, name
+        assert d.decode_stages(early_term=False) == d.decode_stages(decoding="BP_MS") == whole, name
+
+
 def test_layer_plan_matches_its_restatement(lib):
     """The steps of the layered schedule (non-parity modes 2 / 3): the product's plan (plan.cpp, build_layer_plan) and the
     oracle's independent restatement put every check node of h.txt into the same step — the mirror the GPU test of the
