@@ -265,6 +265,14 @@ void ldpc_hip_fused_plan_info(const ldpc_hip_ctx *ctx, int64_t info[8]);
    DESIGN.md section 4): stages[i] = 0 whole, 1 ratio-first, 2 ratio-separate, 3 list-chain, 4 llr-redo, 5 handover-first,
    6 handover-resume; returns their number, 1 to 3 */
 int ldpc_hip_decode_stages(const ldpc_hip_ctx *ctx, decoder_param dec, int32_t stages[3]);
+/* Host arithmetic only. The simulation loop's counters over given per-frame results. Frames [0, n) are presented as
+   consecutive ranges; ends[k] is the end of range k (ascending, <= n; ranges may be empty); `world` consecutive ranges form
+   one step (world == 1: the ranges are the batches of the one-rank loop, world > 1: the ranks' ranges of a sharded step).
+   out[0..3] = frames, fec, bec, iters (the `totals` of ldpc_hip_simulate); out[4], out[5] = frames and iterations at the
+   last published report (0, 0: none); out[6] = 1 if the stop rule fired; out[7] = frames of the last step that counted
+   (what the encoder is advanced by). Returns the number of steps walked, -1 on bad arguments. */
+int ldpc_hip_selftest_sim_fold(const uint32_t *iters, const uint32_t *bit_errors, uint64_t n, const uint64_t *ends,
+                               uint64_t n_ranges, int world, uint64_t min_fec, uint64_t max_frames, uint64_t out[8]);
 /* the steps of the layered schedule of the non-parity modes 2 / 3 (host only): step_of_row[mc] = the step each check node
    is processed in; returns the number of steps, -1 when the schedule does not take the code */
 int ldpc_hip_selftest_layer_plan(ldpc_hip_ctx *ctx, int32_t *step_of_row);

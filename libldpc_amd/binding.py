@@ -101,6 +101,8 @@ def load_library(path=LIB_PATH):
     L.ldpc_hip_fused_plan_info.argtypes = [vp, vp]
     L.ldpc_hip_decode_stages.restype = i32
     L.ldpc_hip_decode_stages.argtypes = [vp, decoder_param, vp]
+    L.ldpc_hip_selftest_sim_fold.restype = i32
+    L.ldpc_hip_selftest_sim_fold.argtypes = [vp, vp, u64, vp, u64, i32, u64, u64, vp]
     L.ldpc_hip_selftest_layer_plan.restype = i32
     L.ldpc_hip_selftest_layer_plan.argtypes = [vp, vp]
     L.ldpc_hip_selftest_place.restype = i32
@@ -147,6 +149,17 @@ def _ptr(buf):
 
 def _dec(early_term, iterations, decoding):
     return decoder_param(bool(early_term), int(iterations), decoding.encode())
+
+
+def sim_fold(iters, bit_errors, ends, world=1, min_fec=50, max_frames=10**10, lib=LIB_PATH):
+    """The simulation loop's counters over given per-frame results, cut into ranges ending at `ends`, `world` ranges to a
+    step (include/ldpc_amd.h, ldpc_hip_selftest_sim_fold; no GPU): (steps walked, the eight output words)."""
+    it, be = np.ascontiguousarray(iters, np.uint32), np.ascontiguousarray(bit_errors, np.uint32)
+    e = np.ascontiguousarray(ends, np.uint64)
+    out = np.zeros(8, np.uint64)
+    steps = load_library(lib).ldpc_hip_selftest_sim_fold(_ptr(it), _ptr(be), min(it.size, be.size), _ptr(e), e.size, int(world),
+                                                         int(min_fec), int(max_frames), _ptr(out))
+    return steps, [int(v) for v in out]
 
 
 class Comm:

@@ -7,6 +7,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -18,6 +19,7 @@
 #include "engine.hpp"
 #include "shard_place.hpp"
 #include "sim.hpp"
+#include "sim_fold.hpp"
 
 using namespace ldpc_amd;
 
@@ -61,6 +63,21 @@ int channel_from(const char *type)
     if (type && !std::strcmp(type, "BEC"))
         return kBec;
     return 0;
+}
+
+SimRequest to_request(const decoder_param &dec, const channel_param &ch, const simulation_param &sim, bool cli_output)
+{
+    SimRequest rq;
+    rq.dec = to_params(dec);
+    rq.channel = channel_from(ch.type); // 0: none selected, which the entry points turn away
+    rq.seed = ch.seed;
+    for (int i = 0; i < 3; ++i)
+        rq.x_range[i] = ch.xRange[i];
+    rq.max_frames = sim.maxFrames;
+    rq.min_fec = sim.fec;
+    rq.result_file = sim.resultFile ? sim.resultFile : "";
+    rq.cli_output = cli_output;
+    return rq;
 }
 
 [[noreturn]] void die(const char *where, const std::exception &e)
@@ -131,16 +148,8 @@ void ldpc_setup(const char *pcFile, const char *genFile, int *n, int *m, int *nc
 void simulate(decoder_param decoderParams, channel_param channelParam, simulation_param simParam,
               sim_results_t *results, bool *stopFlag)
 {
-    SimRequest rq;
-    rq.dec = to_params(decoderParams);
-    rq.channel = channel_from(channelParam.type);
-    rq.seed = channelParam.seed;
-    for (int i = 0; i < 3; ++i)
-        rq.x_range[i] = channelParam.xRange[i];
-    rq.max_frames = simParam.maxFrames;
-    rq.min_fec = simParam.fec;
-    rq.result_file = simParam.resultFile ? simParam.resultFile : "";
-    rq.cli_output = false; // the reference library is built with LIB_SHARED (CMakeLists.txt:22)
+    // no console line, no result file: the reference library is built with LIB_SHARED (CMakeLists.txt:22)
+    const SimRequest rq = to_request(decoderParams, channelParam, simParam, false);
     try
     {
         if (!g_engine)
@@ -699,18 +708,9 @@ int ldpc_hip_simulate_sharded(ldpc_hip_ctx *ctx, ldpc_hip_comm *comm, decoder_pa
 {
     int n = -1;
     int rc = guarded([&] {
-        SimRequest rq;
-        rq.dec = to_params(dec);
-        rq.channel = channel_from(ch.type);
+        const SimRequest rq = to_request(dec, ch, sim, cli_output != 0);
         if (!rq.channel)
             throw std::runtime_error("No channel selected.");
-        rq.seed = ch.seed;
-        for (int i = 0; i < 3; ++i)
-            rq.x_range[i] = ch.xRange[i];
-        rq.max_frames = sim.maxFrames;
-        rq.min_fec = sim.fec;
-        rq.result_file = sim.resultFile ? sim.resultFile : "";
-        rq.cli_output = cli_output != 0;
         n = run_simulation(*ctx->eng, rq, results, totals, stopFlag, comm ? comm->comm.get() : nullptr);
     });
     return rc == 0 ? n : -1;
@@ -719,23 +719,49 @@ int ldpc_hip_simulate_sharded(ldpc_hip_ctx *ctx, ldpc_hip_comm *comm, decoder_pa
 int ldpc_hip_simulate(ldpc_hip_ctx *ctx, decoder_param dec, channel_param ch, simulation_param sim,
                       sim_results_t *results, uint64_t *totals, bool *stopFlag, int cli_output)
 {
-    int n = -1;
-    int rc = guarded([&] {
-        SimRequest rq;
-        rq.dec = to_params(dec);
-        rq.channel = channel_from(ch.type);
-        if (!rq.channel)
-            throw std::runtime_error("No channel selected.");
-        rq.seed = ch.seed;
-        for (int i = 0; i < 3; ++i)
-            rq.x_range[i] = ch.xRange[i];
-        rq.max_frames = sim.maxFrames;
-        rq.min_fec = sim.fec;
-        rq.result_file = sim.resultFile ? sim.resultFile : "";
-        rq.cli_output = cli_output != 0;
-        n = run_simulation(*ctx->eng, rq, results, totals, stopFlag);
-    });
-    return rc == 0 ? n : -1;
+    return ldpc_hip_simulate_sharded(ctx, nullptr, dec, ch, sim, results, totals, stopFlag, cli_output);
+}
+
+int ldpc_hip_selftest_sim_fold(const uint32_t *iters, const uint32_t *bit_errors, uint64_t n, const uint64_t *ends,
+                               uint64_t n_ranges, int world, uint64_t min_fec, uint64_t max_frames, uint64_t out[8])
+{
+    if (world < 1 || n_ranges % static_cast<uint64_t>(world) != 0)
+        return -1;
+    for (uint64_t k = 0; k < n_ranges; ++k)
+        if (ends[k] > n || (k > 0 && ends[k] < ends[k - 1]))
+            return -1;
+    PointCounters pc, published; // published: what the driver last handed to its report
+    uint64_t used = 0;
+    bool stop = false;
+    int steps = 0;
+    const auto begin = [&](uint64_t r) { return r ? ends[r - 1] : 0; };
+    const auto fold = [&](uint64_t r, uint64_t frames0, uint64_t fec0, uint64_t fec_limit, uint64_t frame_limit, auto &&on_error) {
+        return fold_range(iters + begin(r), bit_errors + begin(r), ends[r] - begin(r), frames0, fec0, fec_limit, frame_limit, on_error);
+    };
+    std::vector<Fold> rows(static_cast<size_t>(world));
+    for (uint64_t k = 0; k < n_ranges && !stop; k += static_cast<uint64_t>(world), ++steps)
+    {
+        used = 0;
+        if (world == 1) // a batch of the one-rank loop (sim.cpp, run_point)
+        {
+            const Fold f = fold(k, pc.frames, pc.fec, min_fec, max_frames, [&](const Fold &g) { published = pc.plus(g, min_fec); });
+            pc = pc.plus(f, min_fec);
+            used = f.n, stop = f.stop != 0;
+            continue;
+        }
+        const uint64_t rep_before = pc.rep_frames; // a sharded step (sim.cpp, run_point_sharded)
+        for (int q = 0; q < world; ++q)
+            rows[static_cast<size_t>(q)] = fold(k + q, 0, 0, kNoLimit, kNoLimit, NoReport{});
+        const int q_stop = reduce_ranks(rows.data(), world, pc, min_fec, max_frames, &used);
+        if (q_stop >= 0)
+            apply_cut(fold(k + q_stop, pc.frames, pc.fec, min_fec, max_frames, NoReport{}), pc, min_fec, &used);
+        stop = q_stop >= 0;
+        if (pc.rep_frames != rep_before)
+            published = pc;
+    }
+    const uint64_t res[8] = {pc.frames, pc.fec, pc.bec, pc.iters, published.rep_frames, published.rep_iters, stop ? 1u : 0u, used};
+    std::copy(res, res + 8, out);
+    return steps;
 }
 
 } // extern "C"
