@@ -165,6 +165,49 @@ int ldpc_hip_philox(ldpc_hip_ctx *ctx, uint64_t seed, uint32_t tag, uint64_t fra
    GPU.  0, or -1 (last_error set; the setting unchanged) for invalid values */
 int ldpc_hip_set_min_sum_correction(ldpc_hip_ctx *ctx, double scale, double offset);
 
+/* Schedule of "BP_MS" decoding.  LDPC_HIP_MS_SCHEDULE_FLOODING (the default) is the reference's.
+   LDPC_HIP_MS_SCHEDULE_LAYERED is the layered (row-serial) schedule: NON-PARITY (the reference's schedule is flooding,
+   decoder.cpp:22-76), off by default and never chosen by the library itself.
+   Where it applies: whenever a call's decoder_param.type is "BP_MS" in ldpc_hip_decode_batch,
+   ldpc_hip_stream_decode(_sharded) and ldpc_hip_simulate(_sharded).  Sum-product, the BEC decoder and Part 1 (simulate(),
+   decode(), ...) never see it.  It combines with ldpc_hip_set_min_sum_correction and with both noise modes
+   (ldpc_hip_set_noise).  ldpc_hip_decode_stages reports one `whole` launch for "BP_MS" while it is set and unchanged stages
+   for "BP".
+   Which codes it takes: every check node of degree 2..8, at most 65 535 columns, no isolated variable node, and the frame's
+   LDS — 8 nc bytes of totals plus 20 bytes per check node (each step of the schedule rounded up to an even number of check
+   nodes), ldpc_hip_layered_min_sum_lds_bytes — within 160 KB.  For any other code, and for an unknown `schedule` value, the
+   setter returns -1 with ldpc_hip_last_error set and the setting unchanged.  The check is host-only; the setting takes
+   effect at the next decode call and touches no GPU.
+   Arithmetic: everything is binary64, every operation is rounded once, there is no fused multiply-add.
+     1. T[v] := the frame's decoder input (channel LLR; punctured 0, shortened shorten_llr).  Every message m[c][j] := +0.0.
+     2. One sweep visits the steps of the layered plan (libldpc_amd/csrc/plan.cpp, build_layer_plan: check nodes in file order
+        within each degree, each put into the first step of its degree that has a free lane — 64 per step — and none of its
+        variable nodes yet; steps ordered by their first check node) in order.  For each check node c of the step, with
+        neighbours v_j:
+          t_j = fl(T[v_j] - m[c][j])
+          a_j = the smallest |t_k| over k != j
+          s_j = XOR of the sign bits of t_k, k != j (a zero carries its sign bit)
+          r_j = max(fl(fl(scale * a_j) - offset), +0.0), exactly the rule of ldpc_hip_set_min_sum_correction ((1, 0): a_j)
+          m[c][j] := r_j with sign bit s_j
+          T[v_j] := fl(t_j + m[c][j])
+        The check nodes of a step share no variable node, so the result depends on the step order only.
+     3. After every sweep hard = (T <= 0).  With early termination a zero syndrome stops the frame; iters = sweeps completed
+        before the sweep whose syndrome passed (the reference's convention).  Otherwise iters = iterations.
+     4. llr_out = T.
+     5. bit_errors, llr_in and codeword are as everywhere.
+     6. iterations == 0: hard and llr_out all zero (as the layered modes of ldpc_hip_set_fast_mode). */
+enum
+{
+    LDPC_HIP_MS_SCHEDULE_FLOODING = 0,
+    LDPC_HIP_MS_SCHEDULE_LAYERED = 1
+};
+int ldpc_hip_set_min_sum_schedule(ldpc_hip_ctx *ctx, int schedule);
+/* the schedule in force (LDPC_HIP_MS_SCHEDULE_*); ctx is a live context, as for every entry that takes one */
+int ldpc_hip_min_sum_schedule(const ldpc_hip_ctx *ctx);
+/* LDS bytes one frame of layered min-sum takes on this context's code (host only; worked out once per context), -1 where the
+   layered plan does not take the code, or on an error (last_error set) */
+int64_t ldpc_hip_layered_min_sum_lds_bytes(const ldpc_hip_ctx *ctx);
+
 /* decode n frames of given LLRs llr_in[n][nc] (column order, device or host). 0 on success. */
 int ldpc_hip_decode_batch(ldpc_hip_ctx *ctx, decoder_param dec, uint64_t n, const double *llr_in,
                           const ldpc_hip_out *out, void *hip_stream);
@@ -261,9 +304,9 @@ int ldpc_hip_comm_allgather(ldpc_hip_comm *comm, const void *send, void *recv, u
    take it): info = {the code qualifies, message slots, variable-node blocks per wave, leaf calls per wave, the small
    instantiation applies, check-node calls per wave + 1, the code has shortened bits, entries of the slot table} */
 void ldpc_hip_fused_plan_info(const ldpc_hip_ctx *ctx, int64_t info[8]);
-/* the launches a batch decoded with `dec` takes on this context, in order (host only; honours ldpc_hip_set_fast_mode;
-   DESIGN.md section 4): stages[i] = 0 whole, 1 ratio-first, 2 ratio-separate, 3 list-chain, 4 llr-redo, 5 handover-first,
-   6 handover-resume; returns their number, 1 to 3 */
+/* the launches a batch decoded with `dec` takes on this context, in order (host only; honours ldpc_hip_set_fast_mode and
+   ldpc_hip_set_min_sum_schedule): stages[i] = 0 whole, 1 ratio-first, 2 ratio-separate, 3 list-chain,
+   4 llr-redo, 5 handover-first, 6 handover-resume; returns their number, 1 to 3 */
 int ldpc_hip_decode_stages(const ldpc_hip_ctx *ctx, decoder_param dec, int32_t stages[3]);
 /* Host arithmetic only. The simulation loop's counters over given per-frame results. Frames [0, n) are presented as
    consecutive ranges; ends[k] is the end of range k (ascending, <= n; ranges may be empty); `world` consecutive ranges form

@@ -61,6 +61,12 @@ def load_library(path=LIB_PATH):
     L.ldpc_hip_set_noise.argtypes = [vp, i32]
     L.ldpc_hip_set_min_sum_correction.restype = i32
     L.ldpc_hip_set_min_sum_correction.argtypes = [vp, ct.c_double, ct.c_double]
+    L.ldpc_hip_set_min_sum_schedule.restype = i32
+    L.ldpc_hip_set_min_sum_schedule.argtypes = [vp, i32]
+    L.ldpc_hip_min_sum_schedule.restype = i32
+    L.ldpc_hip_min_sum_schedule.argtypes = [vp]
+    L.ldpc_hip_layered_min_sum_lds_bytes.restype = ct.c_int64
+    L.ldpc_hip_layered_min_sum_lds_bytes.argtypes = [vp]
     L.ldpc_hip_philox.restype = i32
     L.ldpc_hip_philox.argtypes = [vp, u64, ct.c_uint32, u64, ct.c_uint32, u64, vp, vp]
     L.ldpc_hip_decode_batch.restype = i32
@@ -298,6 +304,24 @@ class HipDecoder:
         (1, 0), which switches it off (include/ldpc_amd.h).  0 < scale <= 1, 0 <= offset <= 1e6; touches no GPU."""
         self._check(self.lib.ldpc_hip_set_min_sum_correction(self.ctx, float(scale), float(offset)),
                     f"ldpc_hip_set_min_sum_correction({scale!r}, {offset!r})")
+
+    MS_SCHEDULES = {"flooding": 0, "layered": 1}
+
+    def set_min_sum_schedule(self, schedule):
+        """Schedule of every "BP_MS" decode from the next call on: "flooding" (the default, the reference's) or "layered"
+        (row-serial, NON-PARITY; include/ldpc_amd.h, ldpc_hip_set_min_sum_schedule).  Combines with set_min_sum_correction and
+        both noise modes; raises, leaving the setting as it is, for a code the layered kernel does not take.  Touches no GPU."""
+        m = self.MS_SCHEDULES.get(schedule, -1) if isinstance(schedule, str) else int(schedule)
+        self._check(self.lib.ldpc_hip_set_min_sum_schedule(self.ctx, int(m)), f"ldpc_hip_set_min_sum_schedule({schedule!r})")
+
+    @property
+    def min_sum_schedule(self):
+        """The schedule of "BP_MS" decoding in force: "flooding" or "layered"."""
+        return ("flooding", "layered")[int(self.lib.ldpc_hip_min_sum_schedule(self.ctx))]
+
+    def layered_min_sum_lds_bytes(self):
+        """LDS bytes one frame of layered min-sum takes (-1: the layered plan does not take the code)."""
+        return int(self.lib.ldpc_hip_layered_min_sum_lds_bytes(self.ctx))
 
     def philox(self, seed, tag, frame, first_block, n_blocks):
         """The counter mode's raw words, [n_blocks][4] uint32: blocks first_block.. of `frame` under `tag` (0 AWGN, 1 BSC /

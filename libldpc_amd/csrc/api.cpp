@@ -302,6 +302,20 @@ int ldpc_hip_set_min_sum_correction(ldpc_hip_ctx *ctx, double scale, double offs
     });
 }
 
+int ldpc_hip_set_min_sum_schedule(ldpc_hip_ctx *ctx, int schedule)
+{
+    return guarded([&] { ctx->eng->set_ms_schedule(schedule); });
+}
+
+int ldpc_hip_min_sum_schedule(const ldpc_hip_ctx *ctx) { return ctx->eng->ms_schedule; }
+
+int64_t ldpc_hip_layered_min_sum_lds_bytes(const ldpc_hip_ctx *ctx)
+{
+    int64_t bytes = -1;
+    const int rc = guarded([&] { bytes = ctx->eng->layered_ms_lds_bytes(); }); // (the plan builder allocates)
+    return rc ? rc : bytes;
+}
+
 int ldpc_hip_philox(ldpc_hip_ctx *ctx, uint64_t seed, uint32_t tag, uint64_t frame, uint32_t first_block, uint64_t n_blocks,
                     uint32_t *out, void *hip_stream)
 {

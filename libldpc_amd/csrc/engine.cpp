@@ -756,6 +756,44 @@ void Engine::ensure_layer_plan()
     const size_t tot_bytes = 4 * ((nc + 3) & ~size_t(3));
     dev_layer_.region_bytes = static_cast<uint32_t>((std::max(8 * nc, tot_bytes + 4 * size_t(layer_plan_.slots)) + 15) & ~size_t(15));
     dev_layer_.region_bytes_half = static_cast<uint32_t>((std::max(8 * nc, tot_bytes + 2 * size_t(layer_plan_.slots)) + 15) & ~size_t(15));
+    // layered min-sum: where each step's records sit behind the totals
+    std::vector<uint32_t> rec_off;
+    dev_layer_.record_bytes = static_cast<uint32_t>(layered_ms_records(layer_plan_, &rec_off));
+    dev_layer_.region_bytes_ms = static_cast<uint32_t>(layered_ms_region_bytes(layer_plan_, nc));
+    void *d_rec = nullptr;
+    check(hipMalloc(&d_rec, rec_off.size() * 4), "hipMalloc layer plan");
+    owned_.push_back(d_rec);
+    check(hipMemcpy(d_rec, rec_off.data(), rec_off.size() * 4, hipMemcpyHostToDevice), "upload layer plan");
+    dev_layer_.rec_off = static_cast<const uint32_t *>(d_rec);
+}
+
+// Host only (no device call): the layered min-sum kernel takes the codes the layered plan takes, without an isolated variable
+// node, whose totals and records fit the LDS of one CU — the formula ensure_layer_plan uploads
+int64_t Engine::layered_ms_lds_bytes()
+{
+    if (layered_ms_bytes_ == -2)
+    {
+        const LayerPlan L = build_layer_plan(*code_, plan_);
+        layered_ms_bytes_ = !L.ok || plan_.has_isolated_vn ? -1 : static_cast<int64_t>(layered_ms_region_bytes(L, static_cast<size_t>(plan_.nc)));
+    }
+    return layered_ms_bytes_;
+}
+
+void Engine::set_ms_schedule(int schedule)
+{
+    if (schedule != 0 && schedule != 1)
+        throw std::runtime_error("ldpc_hip_set_min_sum_schedule: unknown schedule " + std::to_string(schedule) + " (0 = flooding, 1 = layered)");
+    if (schedule == 1)
+    {
+        const int64_t bytes = layered_ms_lds_bytes();
+        if (bytes < 0)
+            throw std::runtime_error("ldpc_hip_set_min_sum_schedule: the layered schedule takes codes whose check nodes all have degree 2..8, "
+                                     "with at most 65535 columns and no isolated variable node");
+        if (bytes > static_cast<int64_t>(kLayeredMsLdsLimit))
+            throw std::runtime_error("ldpc_hip_set_min_sum_schedule: a frame's totals and check-node records take " + std::to_string(bytes) +
+                                     " bytes of LDS, more than " + std::to_string(kLayeredMsLdsLimit));
+    }
+    ms_schedule = schedule;
 }
 
 void Engine::finish_batch(OutStage &st, const BatchOut &out, uint64_t n, const uint8_t *codeword, int noise_buffer, void *stream)
@@ -810,6 +848,14 @@ void Engine::run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, 
     // the caller asked for a non-parity mode (never chosen by itself): one launch, no ratio form
     const bool fast = fast_mode && !p.min_sum;
     const auto launch = [&](Stage stage) {
+        if (p.min_sum && ms_schedule == 1) // layered min-sum (the setter has checked that the kernel takes the code)
+        {
+            ensure_layer_plan();
+            if (!layer_plan_.ok || plan_.has_isolated_vn || dev_layer_.region_bytes_ms > kLayeredMsLdsLimit)
+                throw std::runtime_error("layered min-sum: this code is outside what the kernel takes");
+            check(launch_decode_layered_ms(a, dev_layer_, s), "decode (layered min-sum)");
+            return;
+        }
         if (fast && fast_mode == 1)
         {
             if (!fast_mode_supported(dev_, plan_.max_cn_degree) || plan_.has_isolated_vn)

@@ -76,9 +76,15 @@ struct StageSeq
     Stage s[3] = {};
 };
 // shared6: not LDS-resident and a check node of degree 6; ratio_width: no check node wider than kMaxCnDegree (wider ones
-// run the LLR-domain form only; the oracle applies the same rule); fast: a non-parity fast / layered mode applies
-inline StageSeq decode_stages(Residency r, bool shared6, bool ratio_width, bool min_sum, bool early_term, bool iterations, bool fast)
+// run the LLR-domain form only; the oracle applies the same rule); fast: a non-parity fast / layered mode applies;
+// layered_ms: min-sum under the layered schedule (Engine::ms_schedule)
+inline StageSeq decode_stages(Residency r, bool shared6, bool ratio_width, bool min_sum, bool early_term, bool iterations, bool fast,
+                              bool layered_ms)
 {
+    // layered min-sum is one launch of its own kernel whatever flooding min-sum takes: run_decode's layered branch does not
+    // look at the stage
+    if (min_sum && layered_ms)
+        return {1, {Stage::kWhole}};
     // Sum-product runs in likelihood-ratio form (detmath.h: no exp/log inside the iteration); the few frames whose values
     // leave the box that form can represent come back in a list and go on to the next stage.  Which form finishes a frame
     // depends on that frame's data only, never on the batch it travels in.
@@ -233,11 +239,11 @@ class Engine
     const Reg2Plan &reg2_plan() const { return reg2_plan_; }
     const FusedPlan &fused_plan() const { return fused_plan_; }
     Residency residency() const { return residency_; }
-    // the launches a batch with these parameters takes (honours fast_mode; needs no device)
+    // the launches a batch with these parameters takes (honours fast_mode and ms_schedule; needs no device)
     StageSeq stages(const DecParams &p) const
     {
         return decode_stages(residency_, shared6_, plan_.max_cn_degree <= kMaxCnDegree, p.min_sum, p.early_term, p.iterations > 0,
-                             fast_mode && !p.min_sum);
+                             fast_mode && !p.min_sum, ms_schedule == 1);
     }
     int device() const { return device_; }
     bool bec_deg1_compat = false;
@@ -250,6 +256,14 @@ class Engine
     // corrected min-sum of BP_MS decoding (include/ldpc_amd.h, ldpc_hip_set_min_sum_correction), NON-PARITY unless (1, 0):
     // check-node output magnitudes max(fl(fl(ms_scale * m) - ms_offset), +0.0) (device_cn.hpp, MsCorr); read at every decode
     double ms_scale = 1.0, ms_offset = 0.0;
+    // schedule of BP_MS decoding (include/ldpc_amd.h, ldpc_hip_set_min_sum_schedule): 0 = flooding (the reference's), 1 =
+    // LAYERED, NON-PARITY (kernels_layered_ms.hip); set through set_ms_schedule only, read at every decode
+    int ms_schedule = 0;
+    // host only: throws, leaving the setting as it is, for an unknown value or a code the layered kernel does not take
+    void set_ms_schedule(int schedule);
+    // host only: LDS bytes of one frame of layered min-sum (plan.hpp, layered_ms_region_bytes), -1 where the layered plan
+    // does not take the code; worked out at the first call
+    int64_t layered_ms_lds_bytes();
 
     // ---- decode given LLRs (C-ABI decode(), shared.cpp:47-65, batched) ----
     void decode_llr(const DecParams &p, uint64_t n, const double *llr_in, const BatchOut &out, void *stream);
@@ -367,6 +381,7 @@ class Engine
     uint32_t mem_occ_lds_ = 0; // memory-resident: the dummy LDS request that bounds the resident frames per CU
     DevFusedPlan dev_fused_{};
     LayerPlan layer_plan_;
+    int64_t layered_ms_bytes_ = -2; // layered_ms_lds_bytes: -2 not worked out yet
     DevLayerPlan dev_layer_{};
     DevPlan dev_{};
     DevRegPlan dev_reg_{};

@@ -248,8 +248,15 @@ struct DevLayerPlan
     const uint32_t *vn4;   // [(step * 4 + w) * 64 + lane]: VN ranks of edges 2w, 2w+1 of the step's lane-th check node (16 bits each)
     uint32_t n_steps, slots;
     uint32_t region_bytes, region_bytes_half; // LDS per frame with binary32 / binary16 messages
+    // layered min-sum (kernels_layered_ms.hip): byte offset of each step's check-node records behind the frame's totals
+    // (plan.hpp, layered_ms_records), their size in all, and the frame's LDS: 8 nc bytes of totals + the records
+    const uint32_t *rec_off; // [n_steps]
+    uint32_t record_bytes, region_bytes_ms;
 };
 int launch_decode_layered(const DecodeArgs &a, const DevLayerPlan &L, bool half_messages, void *stream);
+// opt-in non-parity layered schedule of min-sum (kernels_layered_ms.hip): binary64 totals, compressed check-node records;
+// the correction of a.ms_scale / a.ms_offset always applies ((1, 0) is plain min-sum, bit for bit)
+int launch_decode_layered_ms(const DecodeArgs &a, const DevLayerPlan &L, void *stream);
 int launch_bec(const BecArgs &a, void *stream);
 
 // ---- mt19937_64 on the device ----

@@ -10,7 +10,8 @@
 // the counters exchanged over RCCL — results are those of the one-GPU run; --comm shm puts the exchange on host
 // shared memory instead, for rehearsals with a repeated device such as --devices 0,0); --noise counter (NON-PARITY
 // counter-based noise, include/ldpc_amd.h ldpc_hip_set_noise); --ms-scale A / --ms-offset B with --decoding BP_MS
-// (NON-PARITY normalized / offset min-sum, include/ldpc_amd.h ldpc_hip_set_min_sum_correction); --bec-compat (reproduce
+// (NON-PARITY normalized / offset min-sum, include/ldpc_amd.h ldpc_hip_set_min_sum_correction); --ms-schedule layered with
+// --decoding BP_MS (NON-PARITY layered schedule, include/ldpc_amd.h ldpc_hip_set_min_sum_schedule); --bec-compat (reproduce
 // the reference's out-of-bounds read for erased degree-1 variable nodes).
 #include <fcntl.h>
 #include <signal.h>
@@ -61,7 +62,9 @@ const char *kUsage =
     "                    \twith the reference only statistically).\n"
     "--ms-scale          \tBP_MS only: normalized min-sum, check-node magnitudes times A, 0 < A <= 1 (NON-PARITY).\n"
     "--ms-offset         \tBP_MS only: offset min-sum, B subtracted from check-node magnitudes, 0 <= B <= 1e6,\n"
-    "                    \tclamped at zero (NON-PARITY; with --ms-scale: the offset after the scale).\n";
+    "                    \tclamped at zero (NON-PARITY; with --ms-scale: the offset after the scale).\n"
+    "--ms-schedule       \tBP_MS only: \"flooding\" (default) or \"layered\" (row-serial sweeps over conflict-free steps of\n"
+    "                    \tcheck nodes; NON-PARITY: the reference's schedule is flooding).\n";
 
 std::vector<int> parse_devices(const std::string &spec)
 {
@@ -106,6 +109,7 @@ int main(int argc, char *argv[])
     std::string noise = "reference";
     std::string ms_scale_arg, ms_offset_arg; // corrected min-sum: the values as given (empty: not given)
     double ms_scale = 1.0, ms_offset = 0.0;
+    std::string ms_schedule; // empty: not given
     try
     {
         for (int i = 1; i < argc; ++i)
@@ -153,6 +157,8 @@ int main(int argc, char *argv[])
                 ms_scale = std::stod(ms_scale_arg = value());
             else if (a == "--ms-offset")
                 ms_offset = std::stod(ms_offset_arg = value());
+            else if (a == "--ms-schedule")
+                ms_schedule = value();
             else if (a.size() > 1 && a[0] == '-' && !(std::isdigit(static_cast<unsigned char>(a[1])) || a[1] == '.'))
                 throw std::runtime_error("Unknown argument: " + a);
             else
@@ -173,6 +179,13 @@ int main(int argc, char *argv[])
                 throw std::runtime_error("--ms-scale: need 0 < A <= 1");
             if (!(ms_offset >= 0.0 && ms_offset <= 1e6))
                 throw std::runtime_error("--ms-offset: need 0 <= B <= 1e6");
+        }
+        if (!ms_schedule.empty())
+        {
+            if (decoding != "BP_MS")
+                throw std::runtime_error("--ms-schedule: the schedule of min-sum, for --decoding BP_MS only");
+            if (ms_schedule != "flooding" && ms_schedule != "layered")
+                throw std::runtime_error("--ms-schedule: flooding or layered");
         }
     }
     catch (const std::exception &e)
@@ -318,6 +331,12 @@ int main(int argc, char *argv[])
         ldpc_hip_destroy(ctx);
         return reap(EXIT_FAILURE);
     }
+    if (ms_schedule == "layered" && ldpc_hip_set_min_sum_schedule(ctx, LDPC_HIP_MS_SCHEDULE_LAYERED) != 0)
+    {
+        std::cout << "Error: " << ldpc_hip_last_error() << std::endl;
+        ldpc_hip_destroy(ctx);
+        return reap(EXIT_FAILURE);
+    }
     int64_t info[10];
     ldpc_hip_code_info(ctx, info);
 
@@ -333,6 +352,8 @@ int main(int argc, char *argv[])
         std::cout << " Min-Sum Correction: scale " << (ms_scale_arg.empty() ? "1" : ms_scale_arg) << ", offset "
                   << (ms_offset_arg.empty() ? "0" : ms_offset_arg)
                   << " (c2v magnitude max(scale * min - offset, 0)), NON-PARITY\n";
+    if (ms_schedule == "layered")
+        std::cout << " Min-Sum Schedule: layered (row-serial sweeps; the reference's is flooding), NON-PARITY\n";
     std::cout << "== Channel Parameters\n";
     std::cout << " Type: " << channel << "\n Seed: " << seed << "\n Range: Min: " << range[0] << ", Max: " << range[1]
               << ", Step: " << range[2] << "\n";

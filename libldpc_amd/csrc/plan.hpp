@@ -187,6 +187,24 @@ struct LayerPlan
     std::vector<int> step_of_row; // (tests: the step each check node is processed in)
 };
 LayerPlan build_layer_plan(const LdpcCode &code, const Plan &plan);
+// Layered min-sum (kernels_layered_ms.hip) keeps a 20-byte RECORD per check node instead of its messages: two binary64
+// magnitudes and one 32-bit word, [field][lane] within a step over the step's real check nodes rounded up to an even
+// number (every step stays 8-byte aligned).  Returns the records' size in bytes; rec_off (if given) receives each step's
+// byte offset.
+inline size_t layered_ms_records(const LayerPlan &L, std::vector<uint32_t> *rec_off = nullptr)
+{
+    size_t bytes = 0;
+    for (const LayerStep &st : L.steps)
+    {
+        if (rec_off)
+            rec_off->push_back(static_cast<uint32_t>(bytes));
+        bytes += 20 * ((static_cast<size_t>(st.count) + 1) & ~size_t(1));
+    }
+    return bytes;
+}
+// ... and the LDS of one frame: the binary64 totals and the records
+inline size_t layered_ms_region_bytes(const LayerPlan &L, size_t nc) { return (8 * nc + layered_ms_records(L) + 15) & ~size_t(15); }
+constexpr size_t kLayeredMsLdsLimit = 160 * 1024;
 
 // ---- fused form of the likelihood-ratio iteration (kernels_fused.hip; detmath.h "Fused form", fused_rule.h) ----------
 // First launch of sum-product with early termination for codes the rule takes (check nodes of degree 2..4 with at most one

@@ -1,0 +1,250 @@
+"""Layered min-sum on the GPU (include/ldpc_amd.h, ldpc_hip_set_min_sum_schedule; kernels_layered_ms.hip) against the numpy
+mirror (tests/layered_minsum_ref.py), bit for bit: iters, hard, bit_errors, and llr_out as uint64.  Then the fused channel
+paths, the paths that must not move, the simulation loop and the CLI, and what the schedule is for: fewer sweeps."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import orc
+from layered_minsum_ref import LayeredMinSumMirror
+from test_gpu_random_codes import make_code_by_degrees
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+WANT = ("iters", "hard", "llr_out", "bit_errors")
+
+
+def _same(r, m, what, rows=slice(None)):
+    for k in WANT:
+        a, b = r[k], np.asarray(m[k])[rows].astype(r[k].dtype)
+        if k == "llr_out":
+            a, b = a.view(np.uint64), b.view(np.uint64)
+        assert np.array_equal(a, b), (what, k)
+
+
+def _dumped(d, ch, x, n, seed=3):
+    """llr_in of n frames of the reference stream."""
+    d.set_min_sum_schedule("flooding")
+    d.set_min_sum_correction()
+    d.stream_begin(ch, seed, x)
+    return d.stream_decode(n, decoding="BP_MS", want=("llr_in",))["llr_in"]
+
+
+def _layered(d, llr, s, o, early, iters):
+    d.set_min_sum_schedule("layered")
+    d.set_min_sum_correction(s, o)
+    return d.decode_batch(llr, early_term=early, iterations=iters, decoding="BP_MS", want=WANT)
+
+
+def _against_mirror(d, mir, llr, corrections, settings):
+    """Every (correction, (early, iterations)) against the mirror; returns the mirror's results."""
+    out = {}
+    for s, o in corrections:
+        for early, iters in settings:
+            m = out[(s, o, early)] = mir.decode(llr, s, o, early_term=early, iterations=iters)
+            _same(_layered(d, llr, s, o, early, iters), m, (s, o, early))
+    d.set_min_sum_correction()
+    d.set_min_sum_schedule("flooding")
+    return out
+
+
+def test_h_txt():
+    """h.txt: 24 steps of degree 3 and 4, partial steps of 16 / 32 / 48 lanes, 128 punctured columns; 48 frames at -5.0 dB,
+    three corrections, with early termination at 50 iterations and without at 20; tail workgroups (n = 1, 7) and a batch
+    split in two."""
+    import libldpc_amd
+    d = libldpc_amd.HipDecoder(orc.H_TXT)
+    code = orc.Code(orc.H_TXT)
+    n_steps, step_of = code.layer_steps()
+    counts = np.bincount(step_of, minlength=n_steps)
+    assert n_steps == 24 and {16, 32, 48, 64} >= set(counts.tolist()) and len(set(counts.tolist())) > 1 and code.num_puncture == 128
+    llr = _dumped(d, "AWGN", -5.0, 48)
+    mir = LayeredMinSumMirror(code)
+    ms = _against_mirror(d, mir, llr, [(1.0, 0.0), (0.75, 0.0), (0.8125, 0.25)], [(True, 50), (False, 20)])
+    m = ms[(1.0, 0.0, True)]
+    converged, failed = (m["iters"] < 50) & (m["bit_errors"] == 0), m["bit_errors"] > 0
+    assert converged.any() and failed.any(), (int(converged.sum()), int(failed.sum()))
+    for n in (1, 7):
+        _same(_layered(d, llr[:n], 1.0, 0.0, True, 50), m, n, slice(0, n))
+    one = _layered(d, llr, 0.75, 0.0, True, 50)
+    a, b = _layered(d, llr[:20], 0.75, 0.0, True, 50), _layered(d, llr[20:], 0.75, 0.0, True, 50)
+    for k in WANT:
+        assert np.array_equal(np.concatenate((a[k], b[k])), one[k]), k
+    # no sweep at all: decisions and outputs all zero, as the layered sum-product modes
+    z = _layered(d, llr[:3], 1.0, 0.0, True, 0)
+    assert not z["hard"].any() and not z["llr_out"].view(np.uint64).any() and not z["iters"].any()
+    assert np.array_equal(z["bit_errors"], np.zeros(3, np.uint32))
+
+
+def test_8k_code(h8k_file):
+    """The 8k (3,6) code: 144 KB of totals and records, the frame that nearly fills a CU's LDS."""
+    import libldpc_amd
+    d = libldpc_amd.HipDecoder(h8k_file)
+    assert 140 * 1024 < d.layered_min_sum_lds_bytes() <= 160 * 1024
+    llr = _dumped(d, "AWGN", 1.4, 8)
+    _against_mirror(d, LayeredMinSumMirror(orc.Code(h8k_file)), llr, [(1.0, 0.0), (0.8125, 0.0)], [(True, 25), (False, 25)])
+
+
+def irregular_code(path):
+    """237 x 125, every check degree 2..8, variable degrees 1, 2, 3 and one of 22 (its 22 check nodes sit in 22 different
+    steps: steps of few lanes, down to one), punctured and shortened columns."""
+    rng = np.random.default_rng(20)
+    cn = [2] * 10 + [3] * 30 + [4] * 30 + [5] * 20 + [6] * 15 + [7] * 10 + [8] * 10
+    vn = [22] + [1] * 20 + [2] * 120 + [3] * 96
+    rng.shuffle(cn)
+    make_code_by_degrees(path, vn, cn, rng)
+    body = open(path).read()
+    open(path, "w").write("puncture [3]: 5 40 41\nshorten [2]: 100 230\n" + body)
+    return path
+
+
+def test_irregular_code(tmp_path):
+    import libldpc_amd
+    path = irregular_code(str(tmp_path / "irregular.txt"))
+    code = orc.Code(path)
+    assert (code.nc, code.mc, code.num_puncture, code.num_shorten) == (237, 125, 3, 2)
+    assert set(np.bincount(code.edge_row).tolist()) == set(range(2, 9))
+    vdeg = np.bincount(code.edge_col, minlength=code.nc)
+    assert (vdeg == 1).any() and vdeg.max() >= 20 and vdeg.min() >= 1
+    n_steps, step_of = code.layer_steps()
+    counts = np.bincount(step_of, minlength=n_steps)
+    assert n_steps >= 22 and counts.min() == 1 and (counts % 2 == 1).any() and counts.max() < 64
+    d = libldpc_amd.HipDecoder(path)
+    llr = _dumped(d, "AWGN", 2.0, 16)
+    ms = _against_mirror(d, LayeredMinSumMirror(code), llr, [(1.0, 0.0), (0.8125, 0.25)], [(True, 15), (False, 15)])
+    for m in ms.values():
+        assert not np.isnan(m["llr_out"]).any()
+    m = ms[(1.0, 0.0, True)]
+    assert (m["iters"] < 15).any() and (m["bit_errors"] > 0).any()
+
+
+def test_fused_channel_equals_decode_of_its_llrs():
+    """stream_decode with the schedule set == decode_batch of the same frames' dumped llr_in: AWGN and BSC, the reference
+    stream and the counter-based noise."""
+    import libldpc_amd
+    d = libldpc_amd.HipDecoder(orc.H_TXT)
+    d.set_min_sum_schedule("layered")
+    d.set_min_sum_correction(0.8125, 0.25)
+    for noise in ("reference", "counter"):
+        d.set_noise(noise)
+        for ch, x in (("AWGN", -5.0), ("BSC", 0.2)):
+            for early in (True, False):
+                d.stream_begin(ch, 6, x)
+                r = d.stream_decode(64, early_term=early, iterations=30, decoding="BP_MS", want=WANT + ("llr_in",))
+                b = d.decode_batch(r["llr_in"], early_term=early, iterations=30, decoding="BP_MS", want=WANT)
+                _same(b, r, (noise, ch, x, early))
+                assert r["iters"].max() > 0
+    d.set_noise("reference")
+    # ... and it is the layered decoder that ran: the mirror on the last frames
+    m = LayeredMinSumMirror(orc.Code(orc.H_TXT)).decode(r["llr_in"][:8], 0.8125, 0.25, early_term=False, iterations=30)
+    _same({k: r[k][:8] for k in WANT}, m, "mirror")
+
+
+def test_nothing_else_moves():
+    """With the schedule set, BP (AWGN, BSC) and BEC outputs equal a fresh context's; after switching back to flooding,
+    BP_MS equals a fresh context's."""
+    import libldpc_amd
+    want = ("iters", "hard", "llr_out", "bit_errors", "llr_in")
+    lay = libldpc_amd.HipDecoder(orc.H_TXT, orc.G_TXT)
+    fresh = libldpc_amd.HipDecoder(orc.H_TXT, orc.G_TXT)
+    lay.set_min_sum_schedule("layered")
+    for ch, x, dec, early in (("AWGN", -4.0, "BP", True), ("AWGN", -4.0, "BP", False), ("BSC", 0.24, "BP", True),
+                              ("BEC", 0.7, "BP", True), ("BEC", 0.7, "BP_MS", True)):
+        rs = []
+        for d in (lay, fresh):
+            d.stream_begin(ch, 2, x)
+            rs.append(d.stream_decode(64, early_term=early, iterations=50, decoding=dec, want=want))
+        for k in want:
+            assert np.array_equal(rs[0][k], rs[1][k]), (ch, dec, early, k)
+        if ch != "BEC":
+            a = lay.decode_batch(rs[1]["llr_in"], early_term=early, decoding=dec, want=WANT)
+            b = fresh.decode_batch(rs[1]["llr_in"], early_term=early, decoding=dec, want=WANT)
+            for k in WANT:
+                assert np.array_equal(a[k], b[k]), (ch, dec, k)
+    # the schedule does change BP_MS ...
+    rs = []
+    for d in (lay, fresh):
+        d.stream_begin("AWGN", 4, -4.5)
+        rs.append(d.stream_decode(32, iterations=50, decoding="BP_MS", want=want))
+    assert np.array_equal(rs[0]["llr_in"], rs[1]["llr_in"]) and not np.array_equal(rs[0]["iters"], rs[1]["iters"])
+    # ... and flooding is back when asked for
+    lay.set_min_sum_schedule("flooding")
+    for early in (True, False):
+        rs = []
+        for d in (lay, fresh):
+            d.stream_begin("AWGN", 4, -4.5)
+            rs.append(d.stream_decode(32, early_term=early, iterations=50, decoding="BP_MS", want=want))
+        for k in want:
+            assert np.array_equal(rs[0][k], rs[1][k]), (early, k)
+
+
+def _fold(d, x, frames, seed):
+    d.stream_begin("AWGN", seed, x)
+    r = d.stream_decode(frames, early_term=True, iterations=50, decoding="BP_MS", want=("iters", "bit_errors"))
+    return frames, int((r["bit_errors"] > 0).sum()), int(r["bit_errors"].sum()), int(r["iters"].sum())
+
+
+def _file_rows(path):
+    return [ln.split()[:5] for ln in open(path).read().splitlines()]
+
+
+def test_simulation_and_cli(tmp_path):
+    """simulate() with the schedule gives the totals of a host fold of stream_decode over the same frames; the CLI with
+    --ms-schedule layered writes the same result file as the Python run, alone and as two ranks over shared memory."""
+    import libldpc_amd
+    d = libldpc_amd.HipDecoder(orc.H_TXT)
+    d.set_min_sum_schedule("layered")
+    d.set_min_sum_correction(0.8125, 0.0)
+    frames, xr, seed = 6000, (-4.5, -3.5, 0.5), 5
+    py_file = str(tmp_path / "py.txt")
+    res = d.simulate("AWGN", xr, seed=seed, decoding="BP_MS", max_frames=frames, fec=10**9, result_file=py_file,
+                     cli_output=True)  # (the result file is written with the console table)
+    assert res["totals"].shape == (2, 4)
+    for i, x in enumerate((-4.5, -4.0)):
+        n, fe, be, it = _fold(d, x, frames, seed)
+        assert res["totals"][i].tolist() == [n, fe, be, it], (x, res["totals"][i], (n, fe, be, it))
+        assert 0 < fe < n
+    exe = os.path.join(ROOT, "libldpc_amd", "ldpcsim")
+    head = [exe, orc.H_TXT]
+    tail = ["-4.5", "-3.5", "0.5", "-s", str(seed), "--decoding", "BP_MS", "--max-frames", str(frames),
+            "--frame-error-count", str(10**9)]
+    flags = ["--ms-schedule", "layered", "--ms-scale", "0.8125"]
+    one, two = str(tmp_path / "one.txt"), str(tmp_path / "two.txt")
+    p = subprocess.run(head + [one] + tail + flags, stdout=subprocess.PIPE, text=True, timeout=120, check=True)
+    assert "NON-PARITY" in p.stdout and "Min-Sum Schedule: layered" in p.stdout
+    subprocess.run(head + [two] + tail + flags + ["--devices", "0,0", "--comm", "shm"], stdout=subprocess.PIPE, text=True,
+                   timeout=120, check=True)
+    assert _file_rows(one) == _file_rows(py_file) == _file_rows(two)
+    # without the flag: today's output and file (flooding, normalized: its own NON-PARITY line, no schedule line)
+    d.set_min_sum_schedule("flooding")
+    flood_py, flood = str(tmp_path / "flood_py.txt"), str(tmp_path / "flood.txt")
+    d.simulate("AWGN", xr, seed=seed, decoding="BP_MS", max_frames=frames, fec=10**9, result_file=flood_py, cli_output=True)
+    p = subprocess.run(head + [flood] + tail + flags[2:], stdout=subprocess.PIPE, text=True, timeout=120, check=True)
+    assert "Min-Sum Schedule" not in p.stdout and _file_rows(flood) == _file_rows(flood_py) != _file_rows(one)
+    plain = str(tmp_path / "plain.txt")
+    p = subprocess.run(head + [plain] + tail, stdout=subprocess.PIPE, text=True, timeout=120, check=True)
+    assert "NON-PARITY" not in p.stdout
+    # BP_MS only
+    p = subprocess.run(head + [plain] + tail[:5] + flags[:2], stdout=subprocess.PIPE, text=True, timeout=120)
+    assert p.returncode != 0 and "--ms-schedule" in p.stdout
+
+
+def test_what_it_is_for():
+    """h.txt, AWGN -3.5 dB, plain min-sum, the same 8 192 frames of one stream under both schedules: over the frames both
+    converge on, the layered schedule needs fewer than 0.7 of the flooding iterations (CPU prototype: 0.56), and it is still
+    a decoder: fer_layered < 2 fer_flooding + 0.005."""
+    import libldpc_amd
+    d = libldpc_amd.HipDecoder(orc.H_TXT)
+    N, r = 8192, {}
+    for sched in ("flooding", "layered"):
+        d.set_min_sum_schedule(sched)
+        d.stream_begin("AWGN", 1, -3.5)
+        r[sched] = d.stream_decode(N, early_term=True, iterations=50, decoding="BP_MS", want=("iters", "bit_errors"))
+    both = (r["flooding"]["iters"] < 50) & (r["layered"]["iters"] < 50)
+    sweeps, its = r["layered"]["iters"][both].mean(), r["flooding"]["iters"][both].mean()
+    fer = {k: float((v["bit_errors"] > 0).mean()) for k, v in r.items()}
+    print("sweeps", sweeps, "iterations", its, "ratio", sweeps / its, "fer", fer, "both", int(both.sum()))
+    assert both.sum() > N // 2 and sweeps < 0.7 * its
+    assert fer["layered"] < 2 * fer["flooding"] + 0.005
