@@ -208,6 +208,49 @@ int ldpc_hip_min_sum_schedule(const ldpc_hip_ctx *ctx);
    layered plan does not take the code, or on an error (last_error set) */
 int64_t ldpc_hip_layered_min_sum_lds_bytes(const ldpc_hip_ctx *ctx);
 
+/* Quantized (fixed-point) min-sum: "BP_MS" decoding with messages of `bits` bits on a saturating integer datapath and the
+   LLR step `step` — the decoder that is built in hardware.  NON-PARITY (the reference's min-sum is binary64,
+   decoder.cpp:22-76), off by default and never chosen by the library itself.
+   bits 0 = off (the default; step ignored), 2..8 = on.  The setter is host-only and takes effect at the next decode call.
+   It returns -1 with ldpc_hip_last_error set and the setting unchanged for bits outside {0, 2..8}, for a step that is NaN,
+   infinite, <= 0 or outside [2^-20, 2^20], for a code it does not take, and while LDPC_HIP_MS_SCHEDULE_LAYERED is in force
+   (ldpc_hip_set_min_sum_schedule(LAYERED) in turn returns -1 while quantization is on).
+   Where it applies: whenever a call's decoder_param.type is "BP_MS" in ldpc_hip_decode_batch,
+   ldpc_hip_stream_decode(_sharded) and ldpc_hip_simulate(_sharded).  Sum-product, the BEC decoder and Part 1 never see it.
+   It combines with both noise modes (ldpc_hip_set_noise) and with ldpc_hip_set_min_sum_correction (through the table of
+   item 3).  ldpc_hip_decode_stages reports one `whole` launch for "BP_MS" while it is on and unchanged stages for "BP".
+   Which codes it takes: every code the library loads — any check-node degree >= 2, any column degree, isolated columns
+   included — with at most 65 535 columns and the frame's LDS (below) within 160 KB.
+   Arithmetic, with q = bits, D = step, Qmax = 2^(q-1) - 1 (symmetric: there is no -2^(q-1)) and inv = fl(1 / D), computed
+   once on the host in binary64:
+     1. Channel.  llr = the frame's decoder input as everywhere (binary64; punctured columns 0, shortened columns
+        shorten_llr).  It is quantized once: L[v] = clamp(rint(fl(llr[v] * inv)), -Qmax, +Qmax), rint = round-half-to-even,
+        the clamp applied in binary64 before the conversion to an integer (an infinity and 99999.9 saturate; a NaN gives
+        0).  The llr_in output stays the unquantized binary64 value.
+     2. Start.  v2c[e] = L[col(e)].
+     3. Correction table, built on the host from ldpc_hip_set_min_sum_correction(scale, offset): for m = 0..Qmax
+        lut[m] = max(0, (int) rint(fl(fl(scale * m) - fl(offset * inv)))), binary64, every operation rounded once, no
+        fused multiply-add.  (1, 0) gives the identity.  lut is non-decreasing, so applying it after the minimum equals
+        applying it before.  The kernel sees the table only (at most 128 bytes), never scale or offset.
+     4. Check node c, edge j: magnitude = lut[min over k != j of |v2c_k|]; negative iff an odd number of the other v2c_k
+        are < 0 (an integer zero is not negative); c2v_j = +-magnitude.
+     5. Variable node v: A[v] = L[v] + the sum of its c2v (an exact integer sum in 32 bits: the order does not matter);
+        v2c_e = clamp(A[v] - c2v_e, -Qmax, +Qmax); hard[v] = (A[v] <= 0), the reference's convention: a tie decides 1.
+     6. Schedule and stop: flooding, the syndrome early stop and the iteration count of the reference, exactly as for
+        "BP_MS" without quantization: iters = the index of the iteration whose decisions passed the syndrome check,
+        otherwise iters = iterations.  iterations == 0: hard and llr_out all zero, as the other min-sum kernels.
+     7. llr_out[v] = fl((double) A[v] * D).  bit_errors and codeword are as everywhere. */
+int ldpc_hip_set_min_sum_quantization(ldpc_hip_ctx *ctx, int bits, double step);
+/* the setting in force: *bits (0 = off) and *step (the last step set; 1.0 before any); either pointer may be null */
+int ldpc_hip_min_sum_quantization(const ldpc_hip_ctx *ctx, int *bits, double *step);
+/* LDS bytes one frame of quantized min-sum takes on this context's code (host only; worked out once per context), -1 for a
+   code it does not take, or on an error (last_error set).  With `slots` = the check-node degrees, each rounded up to a
+   multiple of 4, summed (one byte per message, a check node's messages padded to whole words):
+     bytes = max(8 nc, slots + 4 nc + 144) rounded up to 4, + nc, rounded up to 16
+   — the nc binary64 channel LLRs first, later reused for the messages, the nc 32-bit totals, the 128-byte table and 16
+   bytes of the workgroup's vote; behind them the nc quantized channel values. */
+int64_t ldpc_hip_quantized_min_sum_lds_bytes(const ldpc_hip_ctx *ctx);
+
 /* decode n frames of given LLRs llr_in[n][nc] (column order, device or host). 0 on success. */
 int ldpc_hip_decode_batch(ldpc_hip_ctx *ctx, decoder_param dec, uint64_t n, const double *llr_in,
                           const ldpc_hip_out *out, void *hip_stream);
@@ -304,8 +347,8 @@ int ldpc_hip_comm_allgather(ldpc_hip_comm *comm, const void *send, void *recv, u
    take it): info = {the code qualifies, message slots, variable-node blocks per wave, leaf calls per wave, the small
    instantiation applies, check-node calls per wave + 1, the code has shortened bits, entries of the slot table} */
 void ldpc_hip_fused_plan_info(const ldpc_hip_ctx *ctx, int64_t info[8]);
-/* the launches a batch decoded with `dec` takes on this context, in order (host only; honours ldpc_hip_set_fast_mode and
-   ldpc_hip_set_min_sum_schedule): stages[i] = 0 whole, 1 ratio-first, 2 ratio-separate, 3 list-chain,
+/* the launches a batch decoded with `dec` takes on this context, in order (host only; honours ldpc_hip_set_fast_mode,
+   ldpc_hip_set_min_sum_schedule and ldpc_hip_set_min_sum_quantization): stages[i] = 0 whole, 1 ratio-first, 2 ratio-separate, 3 list-chain,
    4 llr-redo, 5 handover-first, 6 handover-resume; returns their number, 1 to 3 */
 int ldpc_hip_decode_stages(const ldpc_hip_ctx *ctx, decoder_param dec, int32_t stages[3]);
 /* Host arithmetic only. The simulation loop's counters over given per-frame results. Frames [0, n) are presented as

@@ -67,6 +67,12 @@ def load_library(path=LIB_PATH):
     L.ldpc_hip_min_sum_schedule.argtypes = [vp]
     L.ldpc_hip_layered_min_sum_lds_bytes.restype = ct.c_int64
     L.ldpc_hip_layered_min_sum_lds_bytes.argtypes = [vp]
+    L.ldpc_hip_set_min_sum_quantization.restype = i32
+    L.ldpc_hip_set_min_sum_quantization.argtypes = [vp, i32, ct.c_double]
+    L.ldpc_hip_min_sum_quantization.restype = i32
+    L.ldpc_hip_min_sum_quantization.argtypes = [vp, ct.POINTER(i32), ct.POINTER(ct.c_double)]
+    L.ldpc_hip_quantized_min_sum_lds_bytes.restype = ct.c_int64
+    L.ldpc_hip_quantized_min_sum_lds_bytes.argtypes = [vp]
     L.ldpc_hip_philox.restype = i32
     L.ldpc_hip_philox.argtypes = [vp, u64, ct.c_uint32, u64, ct.c_uint32, u64, vp, vp]
     L.ldpc_hip_decode_batch.restype = i32
@@ -322,6 +328,25 @@ class HipDecoder:
     def layered_min_sum_lds_bytes(self):
         """LDS bytes one frame of layered min-sum takes (-1: the layered plan does not take the code)."""
         return int(self.lib.ldpc_hip_layered_min_sum_lds_bytes(self.ctx))
+
+    def set_min_sum_quantization(self, bits=0, step=1.0):
+        """Quantized (fixed-point) min-sum for every "BP_MS" decode from the next call on: messages of `bits` bits (2..8; 0 =
+        off, the default) on a saturating integer datapath with LLR step `step` (NON-PARITY; include/ldpc_amd.h,
+        ldpc_hip_set_min_sum_quantization).  Combines with set_min_sum_correction and both noise modes, not with the layered
+        schedule; raises, leaving the setting as it is, for invalid values or a code the kernel does not take.  Touches no GPU."""
+        self._check(self.lib.ldpc_hip_set_min_sum_quantization(self.ctx, int(bits), float(step)),
+                    f"ldpc_hip_set_min_sum_quantization({bits!r}, {step!r})")
+
+    @property
+    def min_sum_quantization(self):
+        """(bits, step) of quantized min-sum in force; bits 0 = off."""
+        bits, step = ct.c_int32(0), ct.c_double(0.0)
+        self.lib.ldpc_hip_min_sum_quantization(self.ctx, ct.byref(bits), ct.byref(step))
+        return int(bits.value), float(step.value)
+
+    def quantized_min_sum_lds_bytes(self):
+        """LDS bytes one frame of quantized min-sum takes (-1: the kernel does not take the code)."""
+        return int(self.lib.ldpc_hip_quantized_min_sum_lds_bytes(self.ctx))
 
     def philox(self, seed, tag, frame, first_block, n_blocks):
         """The counter mode's raw words, [n_blocks][4] uint32: blocks first_block.. of `frame` under `tag` (0 AWGN, 1 BSC /

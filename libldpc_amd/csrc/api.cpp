@@ -316,6 +316,27 @@ int64_t ldpc_hip_layered_min_sum_lds_bytes(const ldpc_hip_ctx *ctx)
     return rc ? rc : bytes;
 }
 
+int ldpc_hip_set_min_sum_quantization(ldpc_hip_ctx *ctx, int bits, double step)
+{
+    return guarded([&] { ctx->eng->set_ms_quantization(bits, step); });
+}
+
+int ldpc_hip_min_sum_quantization(const ldpc_hip_ctx *ctx, int *bits, double *step)
+{
+    if (bits)
+        *bits = ctx->eng->ms_bits;
+    if (step)
+        *step = ctx->eng->ms_step;
+    return 0;
+}
+
+int64_t ldpc_hip_quantized_min_sum_lds_bytes(const ldpc_hip_ctx *ctx)
+{
+    int64_t bytes = -1;
+    const int rc = guarded([&] { bytes = ctx->eng->qms_lds_bytes(); }); // (the plan builder allocates)
+    return rc ? rc : (bytes > static_cast<int64_t>(kLayeredMsLdsLimit) ? -1 : bytes);
+}
+
 int ldpc_hip_philox(ldpc_hip_ctx *ctx, uint64_t seed, uint32_t tag, uint64_t frame, uint32_t first_block, uint64_t n_blocks,
                     uint32_t *out, void *hip_stream)
 {

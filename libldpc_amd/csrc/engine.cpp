@@ -785,6 +785,9 @@ void Engine::set_ms_schedule(int schedule)
         throw std::runtime_error("ldpc_hip_set_min_sum_schedule: unknown schedule " + std::to_string(schedule) + " (0 = flooding, 1 = layered)");
     if (schedule == 1)
     {
+        if (ms_bits)
+            throw std::runtime_error("ldpc_hip_set_min_sum_schedule: the layered schedule does not combine with quantized min-sum "
+                                     "(ldpc_hip_set_min_sum_quantization(ctx, 0, 0) first)");
         const int64_t bytes = layered_ms_lds_bytes();
         if (bytes < 0)
             throw std::runtime_error("ldpc_hip_set_min_sum_schedule: the layered schedule takes codes whose check nodes all have degree 2..8, "
@@ -794,6 +797,81 @@ void Engine::set_ms_schedule(int schedule)
                                      " bytes of LDS, more than " + std::to_string(kLayeredMsLdsLimit));
     }
     ms_schedule = schedule;
+}
+
+// Host only (no device call): quantized min-sum takes every code of at most 65535 columns whose frame fits the LDS of one CU
+int64_t Engine::qms_lds_bytes()
+{
+    if (!qms_built_)
+    {
+        qms_plan_ = build_qms_plan(*code_, plan_);
+        qms_built_ = true;
+    }
+    return qms_plan_.ok ? static_cast<int64_t>(qms_region_bytes(qms_plan_.slots, static_cast<size_t>(plan_.nc))) : -1;
+}
+
+void Engine::set_ms_quantization(int bits, double step)
+{
+    if (bits == 0) // off: the step is ignored
+    {
+        ms_bits = 0;
+        return;
+    }
+    // (the comparisons are false for NaN: a NaN fails them)
+    if (bits < 2 || bits > 8 || !(step >= 0x1p-20 && step <= 0x1p20))
+        throw std::runtime_error("ldpc_hip_set_min_sum_quantization: need bits 0 (off) or 2..8 and 2^-20 <= step <= 2^20, got (" +
+                                 std::to_string(bits) + ", " + std::to_string(step) + ")");
+    if (ms_schedule == 1)
+        throw std::runtime_error("ldpc_hip_set_min_sum_quantization: quantized min-sum does not combine with the layered schedule "
+                                 "(ldpc_hip_set_min_sum_schedule(ctx, LDPC_HIP_MS_SCHEDULE_FLOODING) first)");
+    const int64_t bytes = qms_lds_bytes();
+    if (bytes < 0)
+        throw std::runtime_error("ldpc_hip_set_min_sum_quantization: quantized min-sum takes codes of at most 65535 columns");
+    if (bytes > static_cast<int64_t>(kLayeredMsLdsLimit))
+        throw std::runtime_error("ldpc_hip_set_min_sum_quantization: a frame's messages, totals and channel values take " +
+                                 std::to_string(bytes) + " bytes of LDS, more than " + std::to_string(kLayeredMsLdsLimit));
+    ms_bits = bits, ms_step = step;
+}
+
+// the tables of quantized min-sum: uploaded at the first launch that needs them
+void Engine::ensure_qms_plan()
+{
+    if (dev_qms_.cn_desc || qms_lds_bytes() < 0)
+        return;
+    const auto upload = [&](const void *src, size_t bytes) {
+        void *d = nullptr;
+        check(hipMalloc(&d, std::max<size_t>(bytes, 4)), "hipMalloc quantized min-sum plan");
+        owned_.push_back(d);
+        if (bytes)
+            check(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice), "upload quantized min-sum plan");
+        return d;
+    };
+    const QmsPlan &q = qms_plan_;
+    dev_qms_.cn_vn = static_cast<const uint16_t *>(upload(q.cn_vn.data(), 2 * q.cn_vn.size()));
+    dev_qms_.vn_start = static_cast<const uint32_t *>(upload(q.vn_start.data(), 4 * q.vn_start.size()));
+    dev_qms_.vn_slot = static_cast<const uint32_t *>(upload(q.vn_slot.data(), 4 * q.vn_slot.size()));
+    dev_qms_.slots = q.slots;
+    dev_qms_.work_bytes = static_cast<uint32_t>(qms_work_bytes(q.slots, static_cast<size_t>(plan_.nc)));
+    dev_qms_.region_bytes = static_cast<uint32_t>(qms_region_bytes(q.slots, static_cast<size_t>(plan_.nc)));
+    dev_qms_.cn_desc = static_cast<const uint32_t *>(upload(q.cn_desc.data(), 4 * q.cn_desc.size()));
+}
+
+// the quantizer and the correction table of one launch (include/ldpc_amd.h, ldpc_hip_set_min_sum_quantization, items 1 and
+// 3): binary64, every operation rounded once (-ffp-contract=off), rint = round-half-to-even
+static QmsArgs make_qms_args(int bits, double step, double scale, double offset)
+{
+    QmsArgs q{};
+    q.step = step, q.inv = 1.0 / step;
+    q.qmax = (1 << (bits - 1)) - 1;
+    const double off = offset * q.inv;
+    for (int m = 0; m <= q.qmax; ++m)
+    {
+        const double t = scale * static_cast<double>(m);
+        const double r = std::rint(t - off); // (scale <= 1 and off >= 0: never above m)
+        const uint32_t v = r > 0.0 ? static_cast<uint32_t>(r) : 0u;
+        q.lut[m >> 2] |= v << (8 * (m & 3));
+    }
+    return q;
 }
 
 void Engine::finish_batch(OutStage &st, const BatchOut &out, uint64_t n, const uint8_t *codeword, int noise_buffer, void *stream)
@@ -854,6 +932,14 @@ void Engine::run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, 
             if (!layer_plan_.ok || plan_.has_isolated_vn || dev_layer_.region_bytes_ms > kLayeredMsLdsLimit)
                 throw std::runtime_error("layered min-sum: this code is outside what the kernel takes");
             check(launch_decode_layered_ms(a, dev_layer_, s), "decode (layered min-sum)");
+            return;
+        }
+        if (p.min_sum && ms_bits) // quantized min-sum (the setter has checked that the kernel takes the code)
+        {
+            ensure_qms_plan();
+            if (!dev_qms_.cn_desc || dev_qms_.region_bytes > kLayeredMsLdsLimit || ms_schedule == 1)
+                throw std::runtime_error("quantized min-sum: this code is outside what the kernel takes");
+            check(launch_decode_qms(a, dev_qms_, make_qms_args(ms_bits, ms_step, ms_scale, ms_offset), s), "decode (quantized min-sum)");
             return;
         }
         if (fast && fast_mode == 1)

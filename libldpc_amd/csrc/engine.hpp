@@ -77,12 +77,12 @@ struct StageSeq
 };
 // shared6: not LDS-resident and a check node of degree 6; ratio_width: no check node wider than kMaxCnDegree (wider ones
 // run the LLR-domain form only; the oracle applies the same rule); fast: a non-parity fast / layered mode applies;
-// layered_ms: min-sum under the layered schedule (Engine::ms_schedule)
+// layered_ms: min-sum under the layered schedule (Engine::ms_schedule) or quantized (Engine::ms_bits): a kernel of its own
 inline StageSeq decode_stages(Residency r, bool shared6, bool ratio_width, bool min_sum, bool early_term, bool iterations, bool fast,
                               bool layered_ms)
 {
-    // layered min-sum is one launch of its own kernel whatever flooding min-sum takes: run_decode's layered branch does not
-    // look at the stage
+    // layered and quantized min-sum are one launch of their own kernel whatever flooding min-sum takes: run_decode's
+    // branches for them do not look at the stage
     if (min_sum && layered_ms)
         return {1, {Stage::kWhole}};
     // Sum-product runs in likelihood-ratio form (detmath.h: no exp/log inside the iteration); the few frames whose values
@@ -239,11 +239,11 @@ class Engine
     const Reg2Plan &reg2_plan() const { return reg2_plan_; }
     const FusedPlan &fused_plan() const { return fused_plan_; }
     Residency residency() const { return residency_; }
-    // the launches a batch with these parameters takes (honours fast_mode and ms_schedule; needs no device)
+    // the launches a batch with these parameters takes (honours fast_mode, ms_schedule and ms_bits; needs no device)
     StageSeq stages(const DecParams &p) const
     {
         return decode_stages(residency_, shared6_, plan_.max_cn_degree <= kMaxCnDegree, p.min_sum, p.early_term, p.iterations > 0,
-                             fast_mode && !p.min_sum, ms_schedule == 1);
+                             fast_mode && !p.min_sum, ms_schedule == 1 || ms_bits != 0);
     }
     int device() const { return device_; }
     bool bec_deg1_compat = false;
@@ -264,6 +264,17 @@ class Engine
     // host only: LDS bytes of one frame of layered min-sum (plan.hpp, layered_ms_region_bytes), -1 where the layered plan
     // does not take the code; worked out at the first call
     int64_t layered_ms_lds_bytes();
+    // quantized min-sum of BP_MS decoding (include/ldpc_amd.h, ldpc_hip_set_min_sum_quantization), NON-PARITY: ms_bits = 0
+    // off, 2..8 = messages of that many bits on a saturating integer datapath with LLR step ms_step (kernels_qms.hip); set
+    // through set_ms_quantization only, read at every decode.  It and the layered schedule exclude each other.
+    int ms_bits = 0;
+    double ms_step = 1.0;
+    // host only: throws, leaving the setting as it is, for invalid values, a code the kernel does not take, or while the
+    // layered schedule is in force
+    void set_ms_quantization(int bits, double step);
+    // host only: LDS bytes of one frame of quantized min-sum (plan.hpp, qms_region_bytes), -1 for a code with more than
+    // 65535 columns; the plan is worked out at the first call
+    int64_t qms_lds_bytes();
 
     // ---- decode given LLRs (C-ABI decode(), shared.cpp:47-65, batched) ----
     void decode_llr(const DecParams &p, uint64_t n, const double *llr_in, const BatchOut &out, void *stream);
@@ -383,6 +394,10 @@ class Engine
     LayerPlan layer_plan_;
     int64_t layered_ms_bytes_ = -2; // layered_ms_lds_bytes: -2 not worked out yet
     DevLayerPlan dev_layer_{};
+    QmsPlan qms_plan_;
+    bool qms_built_ = false; // qms_plan_ has been worked out (qms_lds_bytes)
+    DevQmsPlan dev_qms_{};   // uploaded at the first launch that needs it (cn_desc == nullptr: not yet)
+    void ensure_qms_plan();
     DevPlan dev_{};
     DevRegPlan dev_reg_{};
     DevReg2Plan dev_reg2_{};

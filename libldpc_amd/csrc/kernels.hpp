@@ -257,6 +257,28 @@ int launch_decode_layered(const DecodeArgs &a, const DevLayerPlan &L, bool half_
 // opt-in non-parity layered schedule of min-sum (kernels_layered_ms.hip): binary64 totals, compressed check-node records;
 // the correction of a.ms_scale / a.ms_offset always applies ((1, 0) is plain min-sum, bit for bit)
 int launch_decode_layered_ms(const DecodeArgs &a, const DevLayerPlan &L, void *stream);
+// opt-in non-parity quantized (fixed-point) min-sum (kernels_qms.hip; include/ldpc_amd.h,
+// ldpc_hip_set_min_sum_quantization): device copy of QmsPlan (plan.hpp) and the frame's LDS
+struct DevQmsPlan
+{
+    const uint32_t *cn_desc;  // [mc][2]: byte offset of the check node's first slot (a multiple of 4), its degree
+    const uint16_t *cn_vn;    // [slots]
+    const uint32_t *vn_start; // [nc + 1]
+    const uint32_t *vn_slot;  // [nnz]
+    uint32_t slots;           // message bytes of a frame (a multiple of 4)
+    uint32_t work_bytes;      // plan.hpp, qms_work_bytes: the quantized channel values sit behind it
+    uint32_t region_bytes;    // plan.hpp, qms_region_bytes
+};
+// what the host works out for one launch: the quantizer and the correction table.  The kernel never sees the correction's
+// scale and offset (a.ms_scale / a.ms_offset are not read), only lut[m] for the magnitudes m = 0..qmax, four per word
+struct QmsArgs
+{
+    double step, inv; // the LLR step and fl(1 / step)
+    int32_t qmax;     // 2^(bits - 1) - 1, 1..127
+    int32_t pad;
+    uint32_t lut[32];
+};
+int launch_decode_qms(const DecodeArgs &a, const DevQmsPlan &Q, const QmsArgs &q, void *stream);
 int launch_bec(const BecArgs &a, void *stream);
 
 // ---- mt19937_64 on the device ----

@@ -11,7 +11,8 @@
 // shared memory instead, for rehearsals with a repeated device such as --devices 0,0); --noise counter (NON-PARITY
 // counter-based noise, include/ldpc_amd.h ldpc_hip_set_noise); --ms-scale A / --ms-offset B with --decoding BP_MS
 // (NON-PARITY normalized / offset min-sum, include/ldpc_amd.h ldpc_hip_set_min_sum_correction); --ms-schedule layered with
-// --decoding BP_MS (NON-PARITY layered schedule, include/ldpc_amd.h ldpc_hip_set_min_sum_schedule); --bec-compat (reproduce
+// --decoding BP_MS (NON-PARITY layered schedule, include/ldpc_amd.h ldpc_hip_set_min_sum_schedule); --ms-bits Q --ms-step D
+// with --decoding BP_MS (NON-PARITY quantized min-sum, include/ldpc_amd.h ldpc_hip_set_min_sum_quantization); --bec-compat (reproduce
 // the reference's out-of-bounds read for erased degree-1 variable nodes).
 #include <fcntl.h>
 #include <signal.h>
@@ -64,7 +65,10 @@ const char *kUsage =
     "--ms-offset         \tBP_MS only: offset min-sum, B subtracted from check-node magnitudes, 0 <= B <= 1e6,\n"
     "                    \tclamped at zero (NON-PARITY; with --ms-scale: the offset after the scale).\n"
     "--ms-schedule       \tBP_MS only: \"flooding\" (default) or \"layered\" (row-serial sweeps over conflict-free steps of\n"
-    "                    \tcheck nodes; NON-PARITY: the reference's schedule is flooding).\n";
+    "                    \tcheck nodes; NON-PARITY: the reference's schedule is flooding).\n"
+    "--ms-bits           \tBP_MS only: quantized min-sum with messages of Q bits, 2 <= Q <= 8, on a saturating integer\n"
+    "                    \tdatapath (NON-PARITY; not with --ms-schedule layered).\n"
+    "--ms-step           \tBP_MS only, with --ms-bits: the LLR step D of the quantizer, 2^-20 <= D <= 2^20 (Default: 1).\n";
 
 std::vector<int> parse_devices(const std::string &spec)
 {
@@ -110,6 +114,9 @@ int main(int argc, char *argv[])
     std::string ms_scale_arg, ms_offset_arg; // corrected min-sum: the values as given (empty: not given)
     double ms_scale = 1.0, ms_offset = 0.0;
     std::string ms_schedule; // empty: not given
+    std::string ms_bits_arg, ms_step_arg; // quantized min-sum: the values as given (empty: not given)
+    int ms_bits = 0;
+    double ms_step = 1.0;
     try
     {
         for (int i = 1; i < argc; ++i)
@@ -159,6 +166,10 @@ int main(int argc, char *argv[])
                 ms_offset = std::stod(ms_offset_arg = value());
             else if (a == "--ms-schedule")
                 ms_schedule = value();
+            else if (a == "--ms-bits")
+                ms_bits = std::stoi(ms_bits_arg = value());
+            else if (a == "--ms-step")
+                ms_step = std::stod(ms_step_arg = value());
             else if (a.size() > 1 && a[0] == '-' && !(std::isdigit(static_cast<unsigned char>(a[1])) || a[1] == '.'))
                 throw std::runtime_error("Unknown argument: " + a);
             else
@@ -186,6 +197,20 @@ int main(int argc, char *argv[])
                 throw std::runtime_error("--ms-schedule: the schedule of min-sum, for --decoding BP_MS only");
             if (ms_schedule != "flooding" && ms_schedule != "layered")
                 throw std::runtime_error("--ms-schedule: flooding or layered");
+        }
+        if (!ms_bits_arg.empty() || !ms_step_arg.empty())
+        {
+            if (decoding != "BP_MS")
+                throw std::runtime_error("--ms-bits / --ms-step: quantized min-sum, for --decoding BP_MS only");
+            if (ms_bits_arg.empty())
+                throw std::runtime_error("--ms-step: the step of quantized min-sum, with --ms-bits only");
+            // (include/ldpc_amd.h, ldpc_hip_set_min_sum_quantization; the comparisons are false for NaN)
+            if (ms_bits < 2 || ms_bits > 8)
+                throw std::runtime_error("--ms-bits: need 2 <= Q <= 8");
+            if (!(ms_step >= 0x1p-20 && ms_step <= 0x1p20))
+                throw std::runtime_error("--ms-step: need 2^-20 <= D <= 2^20");
+            if (ms_schedule == "layered")
+                throw std::runtime_error("--ms-bits: quantized min-sum does not combine with --ms-schedule layered");
         }
     }
     catch (const std::exception &e)
@@ -337,6 +362,12 @@ int main(int argc, char *argv[])
         ldpc_hip_destroy(ctx);
         return reap(EXIT_FAILURE);
     }
+    if (ms_bits && ldpc_hip_set_min_sum_quantization(ctx, ms_bits, ms_step) != 0)
+    {
+        std::cout << "Error: " << ldpc_hip_last_error() << std::endl;
+        ldpc_hip_destroy(ctx);
+        return reap(EXIT_FAILURE);
+    }
     int64_t info[10];
     ldpc_hip_code_info(ctx, info);
 
@@ -354,6 +385,9 @@ int main(int argc, char *argv[])
                   << " (c2v magnitude max(scale * min - offset, 0)), NON-PARITY\n";
     if (ms_schedule == "layered")
         std::cout << " Min-Sum Schedule: layered (row-serial sweeps; the reference's is flooding), NON-PARITY\n";
+    if (ms_bits)
+        std::cout << " Min-Sum Quantization: " << ms_bits << " bits, step " << (ms_step_arg.empty() ? "1" : ms_step_arg)
+                  << " (saturating fixed-point messages), NON-PARITY\n";
     std::cout << "== Channel Parameters\n";
     std::cout << " Type: " << channel << "\n Seed: " << seed << "\n Range: Min: " << range[0] << ", Max: " << range[1]
               << ", Step: " << range[2] << "\n";

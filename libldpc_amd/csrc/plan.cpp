@@ -829,4 +829,39 @@ LayerPlan build_layer_plan(const LdpcCode &code, const Plan &plan)
     return L;
 }
 
+// Quantized min-sum: check nodes in the slot-space order of the general plan (by degree), each one's slots in row file
+// order and padded to a whole number of words; variable nodes in rank order, their slots in column file order.
+QmsPlan build_qms_plan(const LdpcCode &code, const Plan &plan)
+{
+    QmsPlan q;
+    const SparseGF2 &H = code.H;
+    if (H.cols > 0xFFFF || code.min_cn_degree() < 2)
+        return q;
+    std::vector<uint32_t> edge_slot(H.nnz(), 0);
+    uint32_t off = 0;
+    for (uint32_t row : plan.cn_rank_row)
+    {
+        const int deg = H.rptr[row + 1] - H.rptr[row];
+        q.cn_desc.push_back(off), q.cn_desc.push_back(static_cast<uint32_t>(deg));
+        q.cn_vn.resize(off + ((static_cast<size_t>(deg) + 3) & ~size_t(3)), 0);
+        for (int k = 0; k < deg; ++k)
+        {
+            q.cn_vn[off + k] = static_cast<uint16_t>(plan.col_rank[H.rcol[H.rptr[row] + k]]);
+            edge_slot[H.redge[H.rptr[row] + k]] = off + k;
+        }
+        off = static_cast<uint32_t>(q.cn_vn.size());
+    }
+    q.slots = off;
+    q.vn_start.push_back(0);
+    for (int r = 0; r < plan.nc; ++r)
+    {
+        const int col = static_cast<int>(plan.rank_col[r]);
+        for (int p = H.cptr[col]; p < H.cptr[col + 1]; ++p)
+            q.vn_slot.push_back(edge_slot[H.cedge[p]]);
+        q.vn_start.push_back(static_cast<uint32_t>(q.vn_slot.size()));
+    }
+    q.ok = true;
+    return q;
+}
+
 } // namespace ldpc_amd

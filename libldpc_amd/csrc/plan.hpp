@@ -17,6 +17,7 @@
 // only where they live changes.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <vector>
 
@@ -205,6 +206,27 @@ inline size_t layered_ms_records(const LayerPlan &L, std::vector<uint32_t> *rec_
 // ... and the LDS of one frame: the binary64 totals and the records
 inline size_t layered_ms_region_bytes(const LayerPlan &L, size_t nc) { return (8 * nc + layered_ms_records(L) + 15) & ~size_t(15); }
 constexpr size_t kLayeredMsLdsLimit = 160 * 1024;
+
+// ---- quantized (fixed-point) min-sum (kernels_qms.hip; include/ldpc_amd.h, ldpc_hip_set_min_sum_quantization) ----------
+// One byte per message.  Check nodes in CSR, in the order of Plan::cn_rank_row (by degree, so neighbouring threads loop
+// alike); a check node's message slots are consecutive bytes, padded to a multiple of 4 so that the check-node pass reads
+// and writes whole words.  Variable nodes in CSC, in rank order (the order channel_init writes the LLRs in).
+struct QmsPlan
+{
+    bool ok = false;                // nc <= 65535 (a VN rank takes 16 bits)
+    uint32_t slots = 0;             // message bytes of a frame, padding included (a multiple of 4)
+    std::vector<uint32_t> cn_desc;  // [mc][2]: byte offset of the check node's first slot, its degree
+    std::vector<uint16_t> cn_vn;    // [slots]: VN rank of the slot's edge (0 in the padding)
+    std::vector<uint32_t> vn_start; // [nc + 1] into vn_slot
+    std::vector<uint32_t> vn_slot;  // [nnz]: slots of the variable node's edges
+};
+QmsPlan build_qms_plan(const LdpcCode &code, const Plan &plan);
+// The LDS of one frame.  The channel first writes nc binary64 LLRs; behind them sit the nc quantized channel values (one
+// byte each).  Once those are taken, the binary64 area is used again for the messages (`slots` bytes), the nc 32-bit totals
+// the 128-byte correction table and 16 bytes for the workgroup's vote, and grows to hold them where 8 nc bytes are too few:
+//   bytes = max(8 nc, slots + 4 nc + 144) rounded up to 4, + nc, rounded up to 16
+inline size_t qms_work_bytes(size_t slots, size_t nc) { return (std::max(8 * nc, slots + 4 * nc + 144) + 3) & ~size_t(3); }
+inline size_t qms_region_bytes(size_t slots, size_t nc) { return (qms_work_bytes(slots, nc) + nc + 15) & ~size_t(15); }
 
 // ---- fused form of the likelihood-ratio iteration (kernels_fused.hip; detmath.h "Fused form", fused_rule.h) ----------
 // First launch of sum-product with early termination for codes the rule takes (check nodes of degree 2..4 with at most one
