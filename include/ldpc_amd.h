@@ -351,6 +351,10 @@ void ldpc_hip_fused_plan_info(const ldpc_hip_ctx *ctx, int64_t info[8]);
    ldpc_hip_set_min_sum_schedule and ldpc_hip_set_min_sum_quantization): stages[i] = 0 whole, 1 ratio-first, 2 ratio-separate, 3 list-chain,
    4 llr-redo, 5 handover-first, 6 handover-resume; returns their number, 1 to 3 */
 int ldpc_hip_decode_stages(const ldpc_hip_ctx *ctx, decoder_param dec, int32_t stages[3]);
+/* the decoder that runs such a batch (host only; the same switches): 0 resident (the library's own choice by the code),
+   1 fast32, 2 layered32, 3 layered16 (ldpc_hip_set_fast_mode 1 / 2 / 3, sum-product only), 4 layered min-sum, 5 quantized
+   min-sum ("BP_MS" only).  Anything but 0 is one `whole` launch. */
+int ldpc_hip_decoder_choice(const ldpc_hip_ctx *ctx, decoder_param dec);
 /* Host arithmetic only. The simulation loop's counters over given per-frame results. Frames [0, n) are presented as
    consecutive ranges; ends[k] is the end of range k (ascending, <= n; ranges may be empty); `world` consecutive ranges form
    one step (world == 1: the ranges are the batches of the one-rank loop, world > 1: the ranks' ranges of a sharded step).
@@ -360,7 +364,8 @@ int ldpc_hip_decode_stages(const ldpc_hip_ctx *ctx, decoder_param dec, int32_t s
 int ldpc_hip_selftest_sim_fold(const uint32_t *iters, const uint32_t *bit_errors, uint64_t n, const uint64_t *ends,
                                uint64_t n_ranges, int world, uint64_t min_fec, uint64_t max_frames, uint64_t out[8]);
 /* the steps of the layered schedule of the non-parity modes 2 / 3 (host only): step_of_row[mc] = the step each check node
-   is processed in; returns the number of steps, -1 when the schedule does not take the code */
+   is processed in; returns the number of steps, -1 when the schedule does not take the code.  step_of_row == NULL: returns
+   how many times the context has built that plan so far instead (at most once, whoever asks for it) */
 int ldpc_hip_selftest_layer_plan(ldpc_hip_ctx *ctx, int32_t *step_of_row);
 /* the placement step of ldpc_hip_stream_decode_sharded by itself, without a GPU (tests): this rank reports {pairs in its
    piece, pairs including the margin, status}; after the all-gather over `comm` out = {first frame, frames of this rank,

@@ -113,6 +113,8 @@ def load_library(path=LIB_PATH):
     L.ldpc_hip_fused_plan_info.argtypes = [vp, vp]
     L.ldpc_hip_decode_stages.restype = i32
     L.ldpc_hip_decode_stages.argtypes = [vp, decoder_param, vp]
+    L.ldpc_hip_decoder_choice.restype = i32
+    L.ldpc_hip_decoder_choice.argtypes = [vp, decoder_param]
     L.ldpc_hip_selftest_sim_fold.restype = i32
     L.ldpc_hip_selftest_sim_fold.argtypes = [vp, vp, u64, vp, u64, i32, u64, u64, vp]
     L.ldpc_hip_selftest_layer_plan.restype = i32
@@ -289,6 +291,13 @@ class HipDecoder:
         stages = (ct.c_int32 * 3)()
         n = self.lib.ldpc_hip_decode_stages(self.ctx, _dec(early_term, iterations, decoding), stages)
         return [self.STAGES[stages[i]] for i in range(n)]
+
+    DECODERS = ("resident", "fast32", "layered32", "layered16", "layered-min-sum", "quantized-min-sum")
+
+    def decoder_choice(self, early_term=True, iterations=50, decoding="BP"):
+        """The decoder that runs a batch with these parameters under the switches in force (include/ldpc_amd.h,
+        ldpc_hip_decoder_choice; touches no GPU)."""
+        return self.DECODERS[self.lib.ldpc_hip_decoder_choice(self.ctx, _dec(early_term, iterations, decoding))]
 
     def set_fast_mode(self, on):
         """Opt-in NON-PARITY mode: sum-product with binary32 messages (include/ldpc_amd.h)."""

@@ -307,13 +307,13 @@ int ldpc_hip_set_min_sum_schedule(ldpc_hip_ctx *ctx, int schedule)
     return guarded([&] { ctx->eng->set_ms_schedule(schedule); });
 }
 
-int ldpc_hip_min_sum_schedule(const ldpc_hip_ctx *ctx) { return ctx->eng->ms_schedule; }
+int ldpc_hip_min_sum_schedule(const ldpc_hip_ctx *ctx) { return ctx->eng->ms_schedule(); }
 
 int64_t ldpc_hip_layered_min_sum_lds_bytes(const ldpc_hip_ctx *ctx)
 {
     int64_t bytes = -1;
-    const int rc = guarded([&] { bytes = ctx->eng->layered_ms_lds_bytes(); }); // (the plan builder allocates)
-    return rc ? rc : bytes;
+    guarded([&] { bytes = ctx->eng->layered_ms_lds_bytes(); }); // (the plan builder allocates)
+    return bytes;
 }
 
 int ldpc_hip_set_min_sum_quantization(ldpc_hip_ctx *ctx, int bits, double step)
@@ -324,17 +324,17 @@ int ldpc_hip_set_min_sum_quantization(ldpc_hip_ctx *ctx, int bits, double step)
 int ldpc_hip_min_sum_quantization(const ldpc_hip_ctx *ctx, int *bits, double *step)
 {
     if (bits)
-        *bits = ctx->eng->ms_bits;
+        *bits = ctx->eng->ms_bits();
     if (step)
-        *step = ctx->eng->ms_step;
+        *step = ctx->eng->ms_step();
     return 0;
 }
 
 int64_t ldpc_hip_quantized_min_sum_lds_bytes(const ldpc_hip_ctx *ctx)
 {
-    int64_t bytes = -1;
-    const int rc = guarded([&] { bytes = ctx->eng->qms_lds_bytes(); }); // (the plan builder allocates)
-    return rc ? rc : (bytes > static_cast<int64_t>(kLayeredMsLdsLimit) ? -1 : bytes);
+    int64_t bytes = -1; // (the plan builder allocates; -1 for every code the setter refuses)
+    guarded([&] { bytes = ctx->eng->refusal(Decoder::kQuantizedMinSum).empty() ? ctx->eng->qms_lds_bytes() : -1; });
+    return bytes;
 }
 
 int ldpc_hip_philox(ldpc_hip_ctx *ctx, uint64_t seed, uint32_t tag, uint64_t frame, uint32_t first_block, uint64_t n_blocks,
@@ -689,11 +689,15 @@ int ldpc_hip_decode_stages(const ldpc_hip_ctx *ctx, decoder_param dec, int32_t s
     return seq.n;
 }
 
+int ldpc_hip_decoder_choice(const ldpc_hip_ctx *ctx, decoder_param dec) { return static_cast<int>(ctx->eng->decoder(to_params(dec))); }
+
 int ldpc_hip_selftest_layer_plan(ldpc_hip_ctx *ctx, int32_t *step_of_row)
 {
+    if (!step_of_row)
+        return ctx->eng->layer_plan_builds();
     int n = -1;
     if (guarded([&] {
-            const LayerPlan L = build_layer_plan(ctx->eng->code(), ctx->eng->plan());
+            const LayerPlan &L = ctx->eng->layer_plan();
             if (!L.ok)
                 throw std::runtime_error("the layered schedule does not take this code");
             for (size_t i = 0; i < L.step_of_row.size(); ++i)

@@ -454,6 +454,12 @@ Engine::Engine(const std::string &pc_file, const std::string &gen_file, int devi
     if (code_->min_cn_degree() < 2)
         throw std::runtime_error("check nodes of degree < 2 are not supported (undefined in the reference decoder)");
     plan_ = build_plan(*code_);
+    // the device plan's sizes: known before anything is uploaded (refusal reads them on the host)
+    dev_.nc = plan_.nc, dev_.mc = plan_.mc, dev_.nnz = plan_.nnz, dev_.nct = plan_.nct;
+    dev_.n_bitpos = plan_.n_bitpos;
+    dev_.n_cn_blocks = static_cast<int>(plan_.cn_blocks.size());
+    dev_.n_vn_blocks = static_cast<int>(plan_.vn_blocks.size());
+    dev_.cn_work_stride = plan_.cn_work_stride, dev_.vn_work_stride = plan_.vn_work_stride;
     const size_t nc = plan_.nc, nnz = plan_.nnz;
     if (plan_.lds_ok)
     {
@@ -462,7 +468,7 @@ Engine::Engine(const std::string &pc_file, const std::string &gen_file, int devi
         // Input LLRs: in registers when that frees the LDS for one more resident frame per CU (n=1024 code: 40 KB -> 31 KB,
         // five frames instead of four) and the plan allows it; in LDS otherwise.  (Device memory also reached five frames
         // but paid for it in memory reads: measured, no net gain.)
-        const size_t cu_lds = 160 * 1024, with_llr = plan_.lds_bytes, without = plan_.lds_bytes - 8 * nc;
+        const size_t cu_lds = kCuLdsBytes, with_llr = plan_.lds_bytes, without = plan_.lds_bytes - 8 * nc;
         if (cu_lds / without > cu_lds / with_llr && plan_.vn_work_stride <= 8 && !plan_.has_isolated_vn && plan_.nc <= plan_.nnz &&
             !plan_.vn_packed.empty())
             lds_llr_mode_ = 2;
@@ -476,7 +482,7 @@ Engine::Engine(const std::string &pc_file, const std::string &gen_file, int devi
     struct Tile { int nt, kc, maxd; };
     for (Tile t : {Tile{1024, 4, 6}, Tile{1024, 8, 4}, Tile{1024, 2, 8}, Tile{512, 8, 6}, Tile{512, 16, 4}, Tile{512, 4, 8}})
     {
-        reg_plan_ = build_reg_plan(*code_, plan_, t.nt, t.kc, t.maxd, t.nt == 512 ? 80 * 1024 : 160 * 1024);
+        reg_plan_ = build_reg_plan(*code_, plan_, t.nt, t.kc, t.maxd, t.nt == 512 ? 80 * 1024 : kCuLdsBytes);
         if (reg_plan_.ok)
             break;
     }
@@ -498,7 +504,7 @@ Engine::Engine(const std::string &pc_file, const std::string &gen_file, int devi
         // (256 CUs x frames/CU x state bytes) stay inside the 256 MiB Infinity Cache
         const uint64_t per_frame = 8ull * nnz + 8ull * nc + nnz;
         const uint64_t frames_per_cu = std::clamp<uint64_t>((224ull << 20) / (256 * per_frame), 1, 8);
-        mem_occ_lds_ = frames_per_cu >= 8 ? 0 : static_cast<uint32_t>((160 * 1024) / (frames_per_cu + 1) + 1024) & ~15u;
+        mem_occ_lds_ = frames_per_cu >= 8 ? 0 : static_cast<uint32_t>(kCuLdsBytes / (frames_per_cu + 1) + 1024) & ~15u;
     }
 }
 
@@ -603,25 +609,24 @@ float Engine::last_ms(int which)
     return spans ? static_cast<float>(sum / spans) : 0.f;
 }
 
+// (at least 16 bytes, so that an empty table still has an address a wave may load a descriptor from)
+const void *Engine::upload_table(const void *src, size_t bytes, const char *what)
+{
+    void *d = nullptr;
+    check(hipMalloc(&d, std::max<size_t>(bytes, 16)), (std::string("hipMalloc ") + what).c_str());
+    owned_.push_back(d);
+    if (bytes)
+        check(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice), (std::string("upload ") + what).c_str());
+    return d;
+}
+
 void Engine::upload_plan()
 {
     bind_device();
     if (dev_.cn_blocks)
         return;
-    auto up = [&](const void *src, size_t bytes) -> void * {
-        void *d = nullptr;
-        check(hipMalloc(&d, std::max<size_t>(bytes, 16)), "hipMalloc plan");
-        owned_.push_back(d);
-        if (bytes)
-            check(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice), "upload plan");
-        return d;
-    };
+    const auto up = [&](const void *src, size_t bytes) { return upload_table(src, bytes, "plan"); };
     const Plan &p = plan_;
-    dev_.nc = p.nc, dev_.mc = p.mc, dev_.nnz = p.nnz, dev_.nct = p.nct;
-    dev_.n_bitpos = p.n_bitpos;
-    dev_.n_cn_blocks = static_cast<int>(p.cn_blocks.size());
-    dev_.n_vn_blocks = static_cast<int>(p.vn_blocks.size());
-    dev_.cn_work_stride = p.cn_work_stride, dev_.vn_work_stride = p.vn_work_stride;
 #define UP(field, vec) dev_.field = static_cast<decltype(dev_.field)>(up(vec.data(), vec.size() * sizeof(vec[0])))
     UP(cn_blocks, p.cn_blocks);
     UP(vn_blocks, p.vn_blocks);
@@ -629,10 +634,8 @@ void Engine::upload_plan()
     UP(cn_work, p.cn_work);
     UP(cn_work_desc, p.cn_work_desc);
     UP(vn_work_desc, p.vn_work_desc);
-    if (!p.vn_packed.empty())
+    if (!p.vn_packed.empty()) // (else it stays null)
         UP(vn_packed, p.vn_packed);
-    else
-        dev_.vn_packed = nullptr;
     dev_.cn_desc_stride = p.cn_desc_stride;
     UP(vn_work, p.vn_work);
     UP(col_rank, p.col_rank);
@@ -723,150 +726,162 @@ uint64_t Engine::max_sub_batch() const
     return std::max<uint64_t>(1, std::min<uint64_t>({1u << 17, (8ull << 30) / per_frame, by_noise}));
 }
 
-// The layered schedule of non-parity modes 2 / 3 (kernels_layered.hip): built and uploaded at the first launch that needs it
-void Engine::ensure_layer_plan()
+// The host plans of the opt-in variants: built at the first question (a setter, an LDS figure, a launch, the self-test), kept
+const LayerPlan &Engine::layer_plan()
 {
-    if (layer_plan_.ok || !layer_plan_.steps.empty())
-        return;
-    layer_plan_ = build_layer_plan(*code_, plan_);
-    if (!layer_plan_.ok)
-        return;
-    const size_t nc = plan_.nc;
-    std::vector<uint32_t> steps;
-    for (const LayerStep &l : layer_plan_.steps)
-        steps.push_back(l.off), steps.push_back(static_cast<uint32_t>(l.count) | static_cast<uint32_t>(l.degree) << 16);
-    // the steps' neighbour tables as the kernel fetches them: four words per lane, two VN ranks per word
-    std::vector<uint32_t> vn4(layer_plan_.steps.size() * 4 * kWaveSize, 0);
-    for (size_t si = 0; si < layer_plan_.steps.size(); ++si)
-        for (int j = 0; j < layer_plan_.steps[si].degree; ++j)
-            for (int l = 0; l < kWaveSize; ++l)
-                vn4[(si * 4 + j / 2) * kWaveSize + l] |=
-                    static_cast<uint32_t>(layer_plan_.vn[layer_plan_.steps[si].off + static_cast<size_t>(j) * kWaveSize + l]) << (16 * (j & 1));
-    void *d_steps = nullptr, *d_vn = nullptr;
-    check(hipMalloc(&d_steps, steps.size() * 4), "hipMalloc layer plan");
-    owned_.push_back(d_steps);
-    check(hipMalloc(&d_vn, vn4.size() * 4), "hipMalloc layer plan");
-    owned_.push_back(d_vn);
-    check(hipMemcpy(d_steps, steps.data(), steps.size() * 4, hipMemcpyHostToDevice), "upload layer plan");
-    check(hipMemcpy(d_vn, vn4.data(), vn4.size() * 4, hipMemcpyHostToDevice), "upload layer plan");
-    dev_layer_.steps = static_cast<const uint32_t *>(d_steps);
-    dev_layer_.vn4 = static_cast<const uint32_t *>(d_vn);
-    dev_layer_.n_steps = static_cast<uint32_t>(layer_plan_.steps.size());
-    dev_layer_.slots = layer_plan_.slots;
-    const size_t tot_bytes = 4 * ((nc + 3) & ~size_t(3));
-    dev_layer_.region_bytes = static_cast<uint32_t>((std::max(8 * nc, tot_bytes + 4 * size_t(layer_plan_.slots)) + 15) & ~size_t(15));
-    dev_layer_.region_bytes_half = static_cast<uint32_t>((std::max(8 * nc, tot_bytes + 2 * size_t(layer_plan_.slots)) + 15) & ~size_t(15));
-    // layered min-sum: where each step's records sit behind the totals
-    std::vector<uint32_t> rec_off;
-    dev_layer_.record_bytes = static_cast<uint32_t>(layered_ms_records(layer_plan_, &rec_off));
-    dev_layer_.region_bytes_ms = static_cast<uint32_t>(layered_ms_region_bytes(layer_plan_, nc));
-    void *d_rec = nullptr;
-    check(hipMalloc(&d_rec, rec_off.size() * 4), "hipMalloc layer plan");
-    owned_.push_back(d_rec);
-    check(hipMemcpy(d_rec, rec_off.data(), rec_off.size() * 4, hipMemcpyHostToDevice), "upload layer plan");
-    dev_layer_.rec_off = static_cast<const uint32_t *>(d_rec);
+    return layer_plan_ ? *layer_plan_ : (++layer_plan_builds_, layer_plan_.emplace(build_layer_plan(*code_, plan_)));
+}
+const QmsPlan &Engine::qms_plan() { return qms_plan_ ? *qms_plan_ : qms_plan_.emplace(build_qms_plan(*code_, plan_)); }
+
+// LDS of one frame of layered sum-product (kernels_layered.hip): binary32 totals and messages of msg_bytes each, or the 8 nc
+// bytes the channel writes first
+static size_t layered_region_bytes(const LayerPlan &L, size_t nc, size_t msg_bytes)
+{
+    return (std::max(8 * nc, 4 * ((nc + 3) & ~size_t(3)) + msg_bytes * L.slots) + 15) & ~size_t(15);
 }
 
-// Host only (no device call): the layered min-sum kernel takes the codes the layered plan takes, without an isolated variable
-// node, whose totals and records fit the LDS of one CU — the formula ensure_layer_plan uploads
 int64_t Engine::layered_ms_lds_bytes()
 {
-    if (layered_ms_bytes_ == -2)
+    const LayerPlan &L = layer_plan();
+    return !L.ok || plan_.has_isolated_vn ? -1 : static_cast<int64_t>(layered_ms_region_bytes(L, static_cast<size_t>(plan_.nc)));
+}
+
+int64_t Engine::qms_lds_bytes()
+{
+    return qms_plan().ok ? static_cast<int64_t>(qms_region_bytes(qms_plan().slots, static_cast<size_t>(plan_.nc))) : -1;
+}
+
+// What each opt-in variant takes, once (engine.hpp).  The texts are what callers see: the two sum-product modes whole, at
+// the first decode; the min-sum ones behind their setter's name, at set time
+std::string Engine::refusal(Decoder d)
+{
+    switch (d)
     {
-        const LayerPlan L = build_layer_plan(*code_, plan_);
-        layered_ms_bytes_ = !L.ok || plan_.has_isolated_vn ? -1 : static_cast<int64_t>(layered_ms_region_bytes(L, static_cast<size_t>(plan_.nc)));
+    case Decoder::kResident:
+        break;
+    case Decoder::kFast32:
+        if (!fast_mode_supported(dev_, plan_.max_cn_degree) || plan_.has_isolated_vn)
+            return "fast mode: this code is outside what the binary32 kernel takes (check nodes up to degree 8, "
+                   "nc <= 8192, LDS-resident, no isolated variable node)";
+        break;
+    case Decoder::kLayered32:
+    case Decoder::kLayered16:
+        if (!layer_plan().ok || plan_.has_isolated_vn ||
+            layered_region_bytes(layer_plan(), static_cast<size_t>(plan_.nc), d == Decoder::kLayered16 ? 2 : 4) > kCuLdsBytes)
+            return "layered mode: this code is outside what the layered kernel takes (check nodes of degree 2..8, at "
+                   "most 65535 columns, totals and messages of one frame within 160 KB of LDS, no isolated variable node)";
+        break;
+    case Decoder::kLayeredMinSum:
+    case Decoder::kQuantizedMinSum:
+    {
+        const bool q = d == Decoder::kQuantizedMinSum;
+        const int64_t bytes = q ? qms_lds_bytes() : layered_ms_lds_bytes();
+        if (bytes < 0)
+            return q ? "quantized min-sum takes codes of at most 65535 columns"
+                     : "the layered schedule takes codes whose check nodes all have degree 2..8, with at most 65535 columns and no "
+                       "isolated variable node";
+        if (bytes > static_cast<int64_t>(kCuLdsBytes))
+            return std::string("a frame's ") + (q ? "messages, totals and channel values" : "totals and check-node records") + " take " +
+                   std::to_string(bytes) + " bytes of LDS, more than " + std::to_string(kCuLdsBytes);
+        break;
     }
-    return layered_ms_bytes_;
+    }
+    return "";
 }
 
 void Engine::set_ms_schedule(int schedule)
 {
+    const std::string who = "ldpc_hip_set_min_sum_schedule: ";
     if (schedule != 0 && schedule != 1)
-        throw std::runtime_error("ldpc_hip_set_min_sum_schedule: unknown schedule " + std::to_string(schedule) + " (0 = flooding, 1 = layered)");
+        throw std::runtime_error(who + "unknown schedule " + std::to_string(schedule) + " (0 = flooding, 1 = layered)");
     if (schedule == 1)
     {
-        if (ms_bits)
-            throw std::runtime_error("ldpc_hip_set_min_sum_schedule: the layered schedule does not combine with quantized min-sum "
-                                     "(ldpc_hip_set_min_sum_quantization(ctx, 0, 0) first)");
-        const int64_t bytes = layered_ms_lds_bytes();
-        if (bytes < 0)
-            throw std::runtime_error("ldpc_hip_set_min_sum_schedule: the layered schedule takes codes whose check nodes all have degree 2..8, "
-                                     "with at most 65535 columns and no isolated variable node");
-        if (bytes > static_cast<int64_t>(kLayeredMsLdsLimit))
-            throw std::runtime_error("ldpc_hip_set_min_sum_schedule: a frame's totals and check-node records take " + std::to_string(bytes) +
-                                     " bytes of LDS, more than " + std::to_string(kLayeredMsLdsLimit));
+        if (ms_bits_)
+            throw std::runtime_error(who + "the layered schedule does not combine with quantized min-sum "
+                                           "(ldpc_hip_set_min_sum_quantization(ctx, 0, 0) first)");
+        if (const std::string why = refusal(Decoder::kLayeredMinSum); !why.empty())
+            throw std::runtime_error(who + why);
     }
-    ms_schedule = schedule;
-}
-
-// Host only (no device call): quantized min-sum takes every code of at most 65535 columns whose frame fits the LDS of one CU
-int64_t Engine::qms_lds_bytes()
-{
-    if (!qms_built_)
-    {
-        qms_plan_ = build_qms_plan(*code_, plan_);
-        qms_built_ = true;
-    }
-    return qms_plan_.ok ? static_cast<int64_t>(qms_region_bytes(qms_plan_.slots, static_cast<size_t>(plan_.nc))) : -1;
+    ms_schedule_ = schedule;
 }
 
 void Engine::set_ms_quantization(int bits, double step)
 {
+    const std::string who = "ldpc_hip_set_min_sum_quantization: ";
     if (bits == 0) // off: the step is ignored
     {
-        ms_bits = 0;
+        ms_bits_ = 0;
         return;
     }
     // (the comparisons are false for NaN: a NaN fails them)
     if (bits < 2 || bits > 8 || !(step >= 0x1p-20 && step <= 0x1p20))
-        throw std::runtime_error("ldpc_hip_set_min_sum_quantization: need bits 0 (off) or 2..8 and 2^-20 <= step <= 2^20, got (" +
-                                 std::to_string(bits) + ", " + std::to_string(step) + ")");
-    if (ms_schedule == 1)
-        throw std::runtime_error("ldpc_hip_set_min_sum_quantization: quantized min-sum does not combine with the layered schedule "
-                                 "(ldpc_hip_set_min_sum_schedule(ctx, LDPC_HIP_MS_SCHEDULE_FLOODING) first)");
-    const int64_t bytes = qms_lds_bytes();
-    if (bytes < 0)
-        throw std::runtime_error("ldpc_hip_set_min_sum_quantization: quantized min-sum takes codes of at most 65535 columns");
-    if (bytes > static_cast<int64_t>(kLayeredMsLdsLimit))
-        throw std::runtime_error("ldpc_hip_set_min_sum_quantization: a frame's messages, totals and channel values take " +
-                                 std::to_string(bytes) + " bytes of LDS, more than " + std::to_string(kLayeredMsLdsLimit));
-    ms_bits = bits, ms_step = step;
+        throw std::runtime_error(who + "need bits 0 (off) or 2..8 and 2^-20 <= step <= 2^20, got (" + std::to_string(bits) + ", " +
+                                 std::to_string(step) + ")");
+    if (ms_schedule_ == 1)
+        throw std::runtime_error(who + "quantized min-sum does not combine with the layered schedule "
+                                       "(ldpc_hip_set_min_sum_schedule(ctx, LDPC_HIP_MS_SCHEDULE_FLOODING) first)");
+    if (const std::string why = refusal(Decoder::kQuantizedMinSum); !why.empty())
+        throw std::runtime_error(who + why);
+    ms_bits_ = bits, ms_step_ = step;
 }
 
-// the tables of quantized min-sum: uploaded at the first launch that needs them
-void Engine::ensure_qms_plan()
+// The tables of the layered schedule, as kernels_layered.hip and kernels_layered_ms.hip read them (a code refusal() passed)
+void Engine::upload_layer_plan()
 {
-    if (dev_qms_.cn_desc || qms_lds_bytes() < 0)
+    if (dev_layer_.rec_off)
         return;
-    const auto upload = [&](const void *src, size_t bytes) {
-        void *d = nullptr;
-        check(hipMalloc(&d, std::max<size_t>(bytes, 4)), "hipMalloc quantized min-sum plan");
-        owned_.push_back(d);
-        if (bytes)
-            check(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice), "upload quantized min-sum plan");
-        return d;
-    };
-    const QmsPlan &q = qms_plan_;
-    dev_qms_.cn_vn = static_cast<const uint16_t *>(upload(q.cn_vn.data(), 2 * q.cn_vn.size()));
-    dev_qms_.vn_start = static_cast<const uint32_t *>(upload(q.vn_start.data(), 4 * q.vn_start.size()));
-    dev_qms_.vn_slot = static_cast<const uint32_t *>(upload(q.vn_slot.data(), 4 * q.vn_slot.size()));
+    const LayerPlan &L = layer_plan();
+    const size_t nc = plan_.nc;
+    std::vector<uint32_t> steps;
+    for (const LayerStep &l : L.steps)
+        steps.push_back(l.off), steps.push_back(static_cast<uint32_t>(l.count) | static_cast<uint32_t>(l.degree) << 16);
+    // the steps' neighbour tables as the kernel fetches them: four words per lane, two VN ranks per word
+    std::vector<uint32_t> vn4(L.steps.size() * 4 * kWaveSize, 0);
+    for (size_t si = 0; si < L.steps.size(); ++si)
+        for (int j = 0; j < L.steps[si].degree; ++j)
+            for (int l = 0; l < kWaveSize; ++l)
+                vn4[(si * 4 + j / 2) * kWaveSize + l] |=
+                    static_cast<uint32_t>(L.vn[L.steps[si].off + static_cast<size_t>(j) * kWaveSize + l]) << (16 * (j & 1));
+    // layered min-sum: where each step's records sit behind the totals
+    std::vector<uint32_t> rec_off;
+    dev_layer_.record_bytes = static_cast<uint32_t>(layered_ms_records(L, &rec_off));
+    dev_layer_.region_bytes_ms = static_cast<uint32_t>(layered_ms_region_bytes(L, nc));
+    dev_layer_.n_steps = static_cast<uint32_t>(L.steps.size());
+    dev_layer_.slots = L.slots;
+    dev_layer_.region_bytes = static_cast<uint32_t>(layered_region_bytes(L, nc, 4));
+    dev_layer_.region_bytes_half = static_cast<uint32_t>(layered_region_bytes(L, nc, 2));
+    dev_layer_.steps = static_cast<const uint32_t *>(upload_table(steps.data(), steps.size() * 4, "layer plan"));
+    dev_layer_.vn4 = static_cast<const uint32_t *>(upload_table(vn4.data(), vn4.size() * 4, "layer plan"));
+    dev_layer_.rec_off = static_cast<const uint32_t *>(upload_table(rec_off.data(), rec_off.size() * 4, "layer plan")); // last: the mark
+}
+
+// the tables of quantized min-sum (a code refusal() passed)
+void Engine::upload_qms_plan()
+{
+    if (dev_qms_.cn_desc)
+        return;
+    const QmsPlan &q = qms_plan();
+    const char *what = "quantized min-sum plan";
+    dev_qms_.cn_vn = static_cast<const uint16_t *>(upload_table(q.cn_vn.data(), 2 * q.cn_vn.size(), what));
+    dev_qms_.vn_start = static_cast<const uint32_t *>(upload_table(q.vn_start.data(), 4 * q.vn_start.size(), what));
+    dev_qms_.vn_slot = static_cast<const uint32_t *>(upload_table(q.vn_slot.data(), 4 * q.vn_slot.size(), what));
     dev_qms_.slots = q.slots;
     dev_qms_.work_bytes = static_cast<uint32_t>(qms_work_bytes(q.slots, static_cast<size_t>(plan_.nc)));
     dev_qms_.region_bytes = static_cast<uint32_t>(qms_region_bytes(q.slots, static_cast<size_t>(plan_.nc)));
-    dev_qms_.cn_desc = static_cast<const uint32_t *>(upload(q.cn_desc.data(), 4 * q.cn_desc.size()));
+    dev_qms_.cn_desc = static_cast<const uint32_t *>(upload_table(q.cn_desc.data(), 4 * q.cn_desc.size(), what)); // last: the mark
 }
 
 // the quantizer and the correction table of one launch (include/ldpc_amd.h, ldpc_hip_set_min_sum_quantization, items 1 and
 // 3): binary64, every operation rounded once (-ffp-contract=off), rint = round-half-to-even
-static QmsArgs make_qms_args(int bits, double step, double scale, double offset)
+QmsArgs Engine::qms_args() const
 {
     QmsArgs q{};
-    q.step = step, q.inv = 1.0 / step;
-    q.qmax = (1 << (bits - 1)) - 1;
-    const double off = offset * q.inv;
+    q.step = ms_step_, q.inv = 1.0 / ms_step_;
+    q.qmax = (1 << (ms_bits_ - 1)) - 1;
+    const double off = ms_offset * q.inv;
     for (int m = 0; m <= q.qmax; ++m)
     {
-        const double t = scale * static_cast<double>(m);
+        const double t = ms_scale * static_cast<double>(m);
         const double r = std::rint(t - off); // (scale <= 1 and off >= 0: never above m)
         const uint32_t v = r > 0.0 ? static_cast<uint32_t>(r) : 0u;
         q.lut[m >> 2] |= v << (8 * (m & 3));
@@ -909,6 +924,10 @@ void Engine::run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, 
 {
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t nc = plan_.nc, nnz = plan_.nnz;
+    // the caller's opt-in variant, or the resident decoder; a variant that does not take the code launches nothing
+    const Decoder dec = decoder(p);
+    if (const std::string why = refusal(dec); !why.empty())
+        throw std::runtime_error(why);
     OutStage st;
     a.plan = dev_;
     a.iterations = p.iterations;
@@ -923,43 +942,29 @@ void Engine::run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, 
     a.ms_correct = p.min_sum && !(ms_scale == 1.0 && ms_offset == 0.0);
     a.ms_scale = ms_scale, a.ms_offset = ms_offset;
     prof_mark(0, s);
-    // the caller asked for a non-parity mode (never chosen by itself): one launch, no ratio form
-    const bool fast = fast_mode && !p.min_sum;
     const auto launch = [&](Stage stage) {
-        if (p.min_sum && ms_schedule == 1) // layered min-sum (the setter has checked that the kernel takes the code)
+        switch (dec)
         {
-            ensure_layer_plan();
-            if (!layer_plan_.ok || plan_.has_isolated_vn || dev_layer_.region_bytes_ms > kLayeredMsLdsLimit)
-                throw std::runtime_error("layered min-sum: this code is outside what the kernel takes");
+        case Decoder::kLayeredMinSum:
+            upload_layer_plan();
             check(launch_decode_layered_ms(a, dev_layer_, s), "decode (layered min-sum)");
             return;
-        }
-        if (p.min_sum && ms_bits) // quantized min-sum (the setter has checked that the kernel takes the code)
-        {
-            ensure_qms_plan();
-            if (!dev_qms_.cn_desc || dev_qms_.region_bytes > kLayeredMsLdsLimit || ms_schedule == 1)
-                throw std::runtime_error("quantized min-sum: this code is outside what the kernel takes");
-            check(launch_decode_qms(a, dev_qms_, make_qms_args(ms_bits, ms_step, ms_scale, ms_offset), s), "decode (quantized min-sum)");
+        case Decoder::kQuantizedMinSum:
+            upload_qms_plan();
+            check(launch_decode_qms(a, dev_qms_, qms_args(), s), "decode (quantized min-sum)");
             return;
-        }
-        if (fast && fast_mode == 1)
-        {
-            if (!fast_mode_supported(dev_, plan_.max_cn_degree) || plan_.has_isolated_vn)
-                throw std::runtime_error("fast mode: this code is outside what the binary32 kernel takes (check nodes up to degree 8, "
-                                         "nc <= 8192, LDS-resident, no isolated variable node)");
+        case Decoder::kFast32:
             a.ws_hb = static_cast<uint8_t *>(ws_hb_.reserve(n * nc));
             check(launch_decode_fast(a, plan_.max_cn_degree, s), "decode (fast mode, binary32)");
             return;
-        }
-        if (fast)
-        {
-            ensure_layer_plan();
-            const bool half = fast_mode == 3;
-            if (!layer_plan_.ok || plan_.has_isolated_vn || (half ? dev_layer_.region_bytes_half : dev_layer_.region_bytes) > 160 * 1024)
-                throw std::runtime_error("layered mode: this code is outside what the layered kernel takes (check nodes of degree 2..8, at "
-                                         "most 65535 columns, totals and messages of one frame within 160 KB of LDS, no isolated variable node)");
-            check(launch_decode_layered(a, dev_layer_, half, s), half ? "decode (layered, binary16 messages)" : "decode (layered, binary32 messages)");
+        case Decoder::kLayered32:
+        case Decoder::kLayered16:
+            upload_layer_plan();
+            check(launch_decode_layered(a, dev_layer_, dec == Decoder::kLayered16, s),
+                  dec == Decoder::kLayered16 ? "decode (layered, binary16 messages)" : "decode (layered, binary32 messages)");
             return;
+        case Decoder::kResident:
+            break;
         }
         switch (residency_)
         {
@@ -1080,7 +1085,7 @@ void Engine::run_bec(const DecParams &p, const BatchOut &out, uint64_t n, const 
     const size_t state = static_cast<size_t>((plan_.nnz + 15) / 16) * 16 + 2 * ((nc + 15) / 16) * 16;
     OutStage st;
     BecArgs a{};
-    a.ws = state > 160 * 1024 ? static_cast<uint8_t *>(ws_msg_.reserve(n * state)) : nullptr; // beyond LDS: state in memory
+    a.ws = state > kCuLdsBytes ? static_cast<uint8_t *>(ws_msg_.reserve(n * state)) : nullptr; // beyond LDS: state in memory
     a.plan = dev_;
     a.iterations = p.iterations;
     a.early_term = p.early_term;

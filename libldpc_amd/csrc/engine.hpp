@@ -8,6 +8,7 @@
 
 #include <cstdint>
 #include <memory>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -75,35 +76,53 @@ struct StageSeq
     int n = 0;
     Stage s[3] = {};
 };
-// shared6: not LDS-resident and a check node of degree 6; ratio_width: no check node wider than kMaxCnDegree (wider ones
-// run the LLR-domain form only; the oracle applies the same rule); fast: a non-parity fast / layered mode applies;
-// layered_ms: min-sum under the layered schedule (Engine::ms_schedule) or quantized (Engine::ms_bits): a kernel of its own
-inline StageSeq decode_stages(Residency r, bool shared6, bool ratio_width, bool min_sum, bool early_term, bool iterations, bool fast,
-                              bool layered_ms)
+
+// Which kernel family decodes a batch: the resident decoders the library picks by the code (Residency), or one of the opt-in
+// NON-PARITY variants the caller switched on — flooding sum-product with binary32 messages (kernels_fast.hip), layered
+// sum-product with binary32 / binary16 messages (kernels_layered.hip), layered min-sum (kernels_layered_ms.hip), quantized
+// min-sum (kernels_qms.hip).  One value per batch: Engine::stages names its launches from it, run_decode switches on it,
+// Engine::refusal says whether that decoder takes the code.
+enum class Decoder : int { kResident, kFast32, kLayered32, kLayered16, kLayeredMinSum, kQuantizedMinSum };
+// min-sum follows its schedule and quantization and ignores the fast mode; sum-product follows the fast mode alone
+constexpr Decoder choose_decoder(bool min_sum, int fast_mode, int ms_schedule, int ms_bits)
 {
-    // layered and quantized min-sum are one launch of their own kernel whatever flooding min-sum takes: run_decode's
-    // branches for them do not look at the stage
-    if (min_sum && layered_ms)
+    if (min_sum)
+        return ms_schedule == 1 ? Decoder::kLayeredMinSum : ms_bits ? Decoder::kQuantizedMinSum : Decoder::kResident;
+    return fast_mode == 1 ? Decoder::kFast32 : fast_mode == 2 ? Decoder::kLayered32 : fast_mode == 3 ? Decoder::kLayered16 : Decoder::kResident;
+}
+
+// shared6: not LDS-resident and a check node of degree 6; ratio_width: no check node wider than kMaxCnDegree (wider ones
+// run the LLR-domain form only; the oracle applies the same rule)
+struct StageQuery
+{
+    Residency residency;
+    Decoder decoder;
+    bool shared6, ratio_width, min_sum, early_term, iterations;
+};
+inline StageSeq decode_stages(const StageQuery &q)
+{
+    // every opt-in variant is one launch of its own kernel, whatever the resident decoder would take
+    if (q.decoder != Decoder::kResident)
         return {1, {Stage::kWhole}};
     // Sum-product runs in likelihood-ratio form (detmath.h: no exp/log inside the iteration); the few frames whose values
     // leave the box that form can represent come back in a list and go on to the next stage.  Which form finishes a frame
     // depends on that frame's data only, never on the batch it travels in.
-    if (fast || min_sum || !iterations || !ratio_width || r == Residency::kNone)
+    if (q.min_sum || !q.iterations || !q.ratio_width || q.residency == Residency::kNone)
         return {1, {Stage::kWhole}};
     // LDS-resident: ONE more launch over the first one's list (kernels.hip, decode_kernel_list); without early termination
     // every frame still starts in the ratio form and is handed over to the LLR-domain form at an iteration boundary when
     // its totals near the edge of the box (detmath.h "Hand-over")
-    if (r == Residency::kLds)
-        return early_term ? StageSeq{2, {Stage::kRatioFirst, Stage::kListChain}}
+    if (q.residency == Residency::kLds)
+        return q.early_term ? StageSeq{2, {Stage::kRatioFirst, Stage::kListChain}}
                           : StageSeq{2, {Stage::kHandoverFirst, Stage::kHandoverResume}};
-    if (!early_term)
+    if (!q.early_term)
         return {1, {Stage::kWhole}};
-    if (r == Residency::kRegTotals) // the kernel chains all three forms in its workgroup: no frame is handed back
+    if (q.residency == Residency::kRegTotals) // the kernel chains all three forms in its workgroup: no frame is handed back
         return {1, {Stage::kRatioFirst}};
     // The first launch of a code with check nodes of degree 6 runs them with shared reciprocals (detmath.h, dm_cn6_shared),
     // whose denominator products leave their range in a few frames per ten thousand at the waterfall: those are decoded
     // again with every output divided separately, and only what leaves the box there goes on to the LLR domain.
-    return shared6 ? StageSeq{3, {Stage::kRatioFirst, Stage::kRatioSeparate, Stage::kLlrRedo}}
+    return q.shared6 ? StageSeq{3, {Stage::kRatioFirst, Stage::kRatioSeparate, Stage::kLlrRedo}}
                    : StageSeq{2, {Stage::kRatioFirst, Stage::kLlrRedo}};
 }
 
@@ -239,16 +258,21 @@ class Engine
     const Reg2Plan &reg2_plan() const { return reg2_plan_; }
     const FusedPlan &fused_plan() const { return fused_plan_; }
     Residency residency() const { return residency_; }
-    // the launches a batch with these parameters takes (honours fast_mode, ms_schedule and ms_bits; needs no device)
+    // the decoder and the launches a batch with these parameters takes (host only)
+    Decoder decoder(const DecParams &p) const { return choose_decoder(p.min_sum, fast_mode, ms_schedule_, ms_bits_); }
     StageSeq stages(const DecParams &p) const
     {
-        return decode_stages(residency_, shared6_, plan_.max_cn_degree <= kMaxCnDegree, p.min_sum, p.early_term, p.iterations > 0,
-                             fast_mode && !p.min_sum, ms_schedule == 1 || ms_bits != 0);
+        return decode_stages({.residency = residency_, .decoder = decoder(p), .shared6 = shared6_,
+                              .ratio_width = plan_.max_cn_degree <= kMaxCnDegree, .min_sum = p.min_sum, .early_term = p.early_term,
+                              .iterations = p.iterations > 0});
     }
+    // host only: empty when decoder d takes this code, else the reason.  The one statement of what each variant takes; the
+    // min-sum setters ask at set time, run_decode before the launch (set_fast_mode accepts anything: the first decode fails)
+    std::string refusal(Decoder d);
     int device() const { return device_; }
     bool bec_deg1_compat = false;
-    // opt-in NON-PARITY modes, off (0) by default and never chosen by the library: 1 = flooding sum-product with binary32
-    // messages (kernels_fast.hip); 2 / 3 = LAYERED sum-product with binary32 / binary16 messages (kernels_layered.hip)
+    // opt-in NON-PARITY modes of sum-product, off (0) by default and never chosen by the library: 1 / 2 / 3 = kFast32 /
+    // kLayered32 / kLayered16
     int fast_mode = 0;
     // noise of the stream interface (include/ldpc_amd.h, LDPC_HIP_NOISE_*): 0 = the reference's mt19937_64 stream (parity),
     // 1 = counter-based Philox4x32-10 of (seed, frame, bit), NON-PARITY (device_philox.hpp); stream_begin latches it
@@ -256,25 +280,22 @@ class Engine
     // corrected min-sum of BP_MS decoding (include/ldpc_amd.h, ldpc_hip_set_min_sum_correction), NON-PARITY unless (1, 0):
     // check-node output magnitudes max(fl(fl(ms_scale * m) - ms_offset), +0.0) (device_cn.hpp, MsCorr); read at every decode
     double ms_scale = 1.0, ms_offset = 0.0;
-    // schedule of BP_MS decoding (include/ldpc_amd.h, ldpc_hip_set_min_sum_schedule): 0 = flooding (the reference's), 1 =
-    // LAYERED, NON-PARITY (kernels_layered_ms.hip); set through set_ms_schedule only, read at every decode
-    int ms_schedule = 0;
-    // host only: throws, leaving the setting as it is, for an unknown value or a code the layered kernel does not take
+    // schedule (0 flooding, 1 layered) and quantization (bits 0 = off, 2..8, with LLR step) of BP_MS decoding, NON-PARITY
+    // (include/ldpc_amd.h, ldpc_hip_set_min_sum_schedule / _quantization).  The two exclude each other.  Host only; each
+    // setter throws, leaving the setting as it is, for invalid values, the other one in force, or a code refusal() names
     void set_ms_schedule(int schedule);
-    // host only: LDS bytes of one frame of layered min-sum (plan.hpp, layered_ms_region_bytes), -1 where the layered plan
-    // does not take the code; worked out at the first call
-    int64_t layered_ms_lds_bytes();
-    // quantized min-sum of BP_MS decoding (include/ldpc_amd.h, ldpc_hip_set_min_sum_quantization), NON-PARITY: ms_bits = 0
-    // off, 2..8 = messages of that many bits on a saturating integer datapath with LLR step ms_step (kernels_qms.hip); set
-    // through set_ms_quantization only, read at every decode.  It and the layered schedule exclude each other.
-    int ms_bits = 0;
-    double ms_step = 1.0;
-    // host only: throws, leaving the setting as it is, for invalid values, a code the kernel does not take, or while the
-    // layered schedule is in force
     void set_ms_quantization(int bits, double step);
-    // host only: LDS bytes of one frame of quantized min-sum (plan.hpp, qms_region_bytes), -1 for a code with more than
-    // 65535 columns; the plan is worked out at the first call
+    int ms_schedule() const { return ms_schedule_; }
+    int ms_bits() const { return ms_bits_; }
+    double ms_step() const { return ms_step_; }
+    // host only: LDS bytes of one frame (plan.hpp, layered_ms_region_bytes / qms_region_bytes), -1 where the plan does not
+    // take the code (a frame beyond the LDS of a CU still gets its byte count: refusal() judges it)
+    int64_t layered_ms_lds_bytes();
     int64_t qms_lds_bytes();
+    // host only, built at the first call, once per engine
+    const LayerPlan &layer_plan();
+    const QmsPlan &qms_plan();
+    int layer_plan_builds() const { return layer_plan_builds_; } // (tests: build_layer_plan runs at most once)
 
     // ---- decode given LLRs (C-ABI decode(), shared.cpp:47-65, batched) ----
     void decode_llr(const DecParams &p, uint64_t n, const double *llr_in, const BatchOut &out, void *stream);
@@ -332,8 +353,13 @@ class Engine
     // path's noise stream does; noise_raw_release() after the launch that reads them
     const uint64_t *noise_raw_async(uint64_t first, uint64_t count, void *stream, int &buffer);
     void noise_raw_release(int buffer, void *stream);
+    // hipMalloc (kept until the engine goes), synchronous copy; `what` names the table in an error
+    const void *upload_table(const void *src, size_t bytes, const char *what);
     void upload_plan();
-    void ensure_layer_plan(); // the layered schedule of non-parity modes 2 / 3, built and uploaded at their first use
+    // the device halves of layer_plan() and qms_plan(): at the first launch that needs them
+    void upload_layer_plan();
+    void upload_qms_plan();
+    QmsArgs qms_args() const; // the quantizer and the correction table of the settings in force
     bool register_resident() const { return residency_ == Residency::kRegTotals || residency_ == Residency::kRegMessages; }
     void run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, uint64_t n, void *stream);
     // BSC / BEC: the batch reads the noise stream's raw draws from word `raw_first` on
@@ -391,13 +417,13 @@ class Engine
     int lds_llr_mode_ = 0;     // LDS-resident: the input LLRs in LDS (0) or in registers (2), kernels.hpp launch_decode_lds
     uint32_t mem_occ_lds_ = 0; // memory-resident: the dummy LDS request that bounds the resident frames per CU
     DevFusedPlan dev_fused_{};
-    LayerPlan layer_plan_;
-    int64_t layered_ms_bytes_ = -2; // layered_ms_lds_bytes: -2 not worked out yet
-    DevLayerPlan dev_layer_{};
-    QmsPlan qms_plan_;
-    bool qms_built_ = false; // qms_plan_ has been worked out (qms_lds_bytes)
-    DevQmsPlan dev_qms_{};   // uploaded at the first launch that needs it (cn_desc == nullptr: not yet)
-    void ensure_qms_plan();
+    int ms_schedule_ = 0, ms_bits_ = 0;
+    double ms_step_ = 1.0;
+    std::optional<LayerPlan> layer_plan_;
+    int layer_plan_builds_ = 0;
+    DevLayerPlan dev_layer_{}; // (rec_off == nullptr: not uploaded yet)
+    std::optional<QmsPlan> qms_plan_;
+    DevQmsPlan dev_qms_{}; // (cn_desc == nullptr: not uploaded yet)
     DevPlan dev_{};
     DevRegPlan dev_reg_{};
     DevReg2Plan dev_reg2_{};

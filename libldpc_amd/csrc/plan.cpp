@@ -187,7 +187,7 @@ Plan build_plan(const LdpcCode &code)
 
     // ---- LDS footprint of one frame: messages (f64) + input LLRs (f64) + per-slot hard bits ----
     p.lds_bytes = static_cast<size_t>(8) * p.nnz + static_cast<size_t>(8) * p.nc + ((p.nnz + 15) / 16) * 16 + 16;
-    p.lds_ok = code.min_cn_degree() >= 2 && p.max_cn_degree <= kMaxLdsCnDegree && p.lds_bytes <= 160 * 1024 &&
+    p.lds_ok = code.min_cn_degree() >= 2 && p.max_cn_degree <= kMaxLdsCnDegree && p.lds_bytes <= kCuLdsBytes &&
                p.cn_blocks.size() < 0xFFFF && p.vn_blocks.size() < 0xFFFF;
     // the memory-resident decoder takes any check-node degree: up to kMaxCnDegree in registers, wider ones through a
     // scratch array (kernels.hip, cn_wide)
@@ -332,7 +332,7 @@ Reg2Plan build_reg2_plan(const LdpcCode &code, const Plan &plan, int nt, int kc,
     const uint32_t tot_base = r.e_max + n_tot0 <= kReg2TrashEntry ? r.e_max : kReg2TrashEntry + kWaveSize;
     r.neutral = std::max(tot_base + n_tot0, kReg2TrashEntry + 1);
     r.lds_entries = r.neutral + 2;
-    if (r.e_max > kReg2TrashEntry || static_cast<size_t>(r.lds_entries) * 8 + 64 > 160 * 1024)
+    if (r.e_max > kReg2TrashEntry || static_cast<size_t>(r.lds_entries) * 8 + 64 > kCuLdsBytes)
         return r;
     for (Reg2VnBlock *o : placed[0])
         o->tot_off += tot_base;

@@ -205,7 +205,7 @@ inline size_t layered_ms_records(const LayerPlan &L, std::vector<uint32_t> *rec_
 }
 // ... and the LDS of one frame: the binary64 totals and the records
 inline size_t layered_ms_region_bytes(const LayerPlan &L, size_t nc) { return (8 * nc + layered_ms_records(L) + 15) & ~size_t(15); }
-constexpr size_t kLayeredMsLdsLimit = 160 * 1024;
+constexpr size_t kCuLdsBytes = 160 * 1024; // the LDS of one CU: what a frame of any decoder has to fit
 
 // ---- quantized (fixed-point) min-sum (kernels_qms.hip; include/ldpc_amd.h, ldpc_hip_set_min_sum_quantization) ----------
 // One byte per message.  Check nodes in CSR, in the order of Plan::cn_rank_row (by degree, so neighbouring threads loop

@@ -9,27 +9,15 @@ import pytest
 
 import orc
 from layered_minsum_ref import LayeredMinSumMirror
+from minsum_common import WANT, against_mirror, check_no_iteration, check_split_batch, dumped, same
 from test_gpu_random_codes import make_code_by_degrees
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WANT = ("iters", "hard", "llr_out", "bit_errors")
 
 
-def _same(r, m, what, rows=slice(None)):
-    for k in WANT:
-        a, b = r[k], np.asarray(m[k])[rows].astype(r[k].dtype)
-        if k == "llr_out":
-            a, b = a.view(np.uint64), b.view(np.uint64)
-        assert np.array_equal(a, b), (what, k)
-
-
-def _dumped(d, ch, x, n, seed=3):
-    """llr_in of n frames of the reference stream."""
+def _flooding(d):
     d.set_min_sum_schedule("flooding")
-    d.set_min_sum_correction()
-    d.stream_begin(ch, seed, x)
-    return d.stream_decode(n, decoding="BP_MS", want=("llr_in",))["llr_in"]
 
 
 def _layered(d, llr, s, o, early, iters):
@@ -40,11 +28,8 @@ def _layered(d, llr, s, o, early, iters):
 
 def _against_mirror(d, mir, llr, corrections, settings):
     """Every (correction, (early, iterations)) against the mirror; returns the mirror's results."""
-    out = {}
-    for s, o in corrections:
-        for early, iters in settings:
-            m = out[(s, o, early)] = mir.decode(llr, s, o, early_term=early, iterations=iters)
-            _same(_layered(d, llr, s, o, early, iters), m, (s, o, early))
+    out = against_mirror(corrections, settings, lambda c, early, iters: _layered(d, llr, *c, early, iters),
+                         lambda c, early, iters: mir.decode(llr, *c, early_term=early, iterations=iters))
     d.set_min_sum_correction()
     d.set_min_sum_schedule("flooding")
     return out
@@ -60,22 +45,17 @@ def test_h_txt():
     n_steps, step_of = code.layer_steps()
     counts = np.bincount(step_of, minlength=n_steps)
     assert n_steps == 24 and {16, 32, 48, 64} >= set(counts.tolist()) and len(set(counts.tolist())) > 1 and code.num_puncture == 128
-    llr = _dumped(d, "AWGN", -5.0, 48)
+    llr = dumped(d, _flooding, "AWGN", -5.0, 48)
     mir = LayeredMinSumMirror(code)
     ms = _against_mirror(d, mir, llr, [(1.0, 0.0), (0.75, 0.0), (0.8125, 0.25)], [(True, 50), (False, 20)])
     m = ms[(1.0, 0.0, True)]
     converged, failed = (m["iters"] < 50) & (m["bit_errors"] == 0), m["bit_errors"] > 0
     assert converged.any() and failed.any(), (int(converged.sum()), int(failed.sum()))
     for n in (1, 7):
-        _same(_layered(d, llr[:n], 1.0, 0.0, True, 50), m, n, slice(0, n))
-    one = _layered(d, llr, 0.75, 0.0, True, 50)
-    a, b = _layered(d, llr[:20], 0.75, 0.0, True, 50), _layered(d, llr[20:], 0.75, 0.0, True, 50)
-    for k in WANT:
-        assert np.array_equal(np.concatenate((a[k], b[k])), one[k]), k
+        same(_layered(d, llr[:n], 1.0, 0.0, True, 50), m, n, slice(0, n))
+    check_split_batch(lambda part: _layered(d, part, 0.75, 0.0, True, 50), llr)
     # no sweep at all: decisions and outputs all zero, as the layered sum-product modes
-    z = _layered(d, llr[:3], 1.0, 0.0, True, 0)
-    assert not z["hard"].any() and not z["llr_out"].view(np.uint64).any() and not z["iters"].any()
-    assert np.array_equal(z["bit_errors"], np.zeros(3, np.uint32))
+    check_no_iteration(_layered(d, llr[:3], 1.0, 0.0, True, 0))
 
 
 def test_8k_code(h8k_file):
@@ -83,7 +63,7 @@ def test_8k_code(h8k_file):
     import libldpc_amd
     d = libldpc_amd.HipDecoder(h8k_file)
     assert 140 * 1024 < d.layered_min_sum_lds_bytes() <= 160 * 1024
-    llr = _dumped(d, "AWGN", 1.4, 8)
+    llr = dumped(d, _flooding, "AWGN", 1.4, 8)
     _against_mirror(d, LayeredMinSumMirror(orc.Code(h8k_file)), llr, [(1.0, 0.0), (0.8125, 0.0)], [(True, 25), (False, 25)])
 
 
@@ -112,7 +92,7 @@ def test_irregular_code(tmp_path):
     counts = np.bincount(step_of, minlength=n_steps)
     assert n_steps >= 22 and counts.min() == 1 and (counts % 2 == 1).any() and counts.max() < 64
     d = libldpc_amd.HipDecoder(path)
-    llr = _dumped(d, "AWGN", 2.0, 16)
+    llr = dumped(d, _flooding, "AWGN", 2.0, 16)
     ms = _against_mirror(d, LayeredMinSumMirror(code), llr, [(1.0, 0.0), (0.8125, 0.25)], [(True, 15), (False, 15)])
     for m in ms.values():
         assert not np.isnan(m["llr_out"]).any()
@@ -134,12 +114,12 @@ def test_fused_channel_equals_decode_of_its_llrs():
                 d.stream_begin(ch, 6, x)
                 r = d.stream_decode(64, early_term=early, iterations=30, decoding="BP_MS", want=WANT + ("llr_in",))
                 b = d.decode_batch(r["llr_in"], early_term=early, iterations=30, decoding="BP_MS", want=WANT)
-                _same(b, r, (noise, ch, x, early))
+                same(b, r, (noise, ch, x, early))
                 assert r["iters"].max() > 0
     d.set_noise("reference")
     # ... and it is the layered decoder that ran: the mirror on the last frames
     m = LayeredMinSumMirror(orc.Code(orc.H_TXT)).decode(r["llr_in"][:8], 0.8125, 0.25, early_term=False, iterations=30)
-    _same({k: r[k][:8] for k in WANT}, m, "mirror")
+    same({k: r[k][:8] for k in WANT}, m, "mirror")
 
 
 def test_nothing_else_moves():

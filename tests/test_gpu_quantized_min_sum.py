@@ -8,31 +8,19 @@ import numpy as np
 import pytest
 
 import orc
+from minsum_common import WANT, against_mirror, check_no_iteration, check_split_batch, dumped, same
 from quantized_minsum_ref import QuantizedMinSumMirror, quantize
 from test_gpu_random_codes import make_code_by_degrees
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WANT = ("iters", "hard", "llr_out", "bit_errors")
 # (bits, step, scale, offset)
 H_SETTINGS = [(6, 0.25, 1.0, 0.0), (6, 0.25, 0.8125, 0.0), (5, 0.5, 0.75, 0.5), (4, 1.0, 1.0, 0.0), (4, 0.25, 1.0, 0.0),
               (2, 2.0, 1.0, 0.0), (8, 0.0625, 0.8125, 0.1)]
 
 
-def _same(r, m, what, rows=slice(None)):
-    for k in WANT:
-        a, b = r[k], np.asarray(m[k])[rows].astype(r[k].dtype)
-        if k == "llr_out":
-            a, b = a.view(np.uint64), b.view(np.uint64)
-        assert np.array_equal(a, b), (what, k)
-
-
-def _dumped(d, ch, x, n, seed=3):
-    """llr_in of n frames of the reference stream."""
+def _binary64(d):
     d.set_min_sum_quantization(0)
-    d.set_min_sum_correction()
-    d.stream_begin(ch, seed, x)
-    return d.stream_decode(n, decoding="BP_MS", want=("llr_in",))["llr_in"]
 
 
 def _quantized(d, llr, setting, early, iters):
@@ -44,12 +32,8 @@ def _quantized(d, llr, setting, early, iters):
 
 def _against_mirror(d, mir, llr, settings, runs):
     """Every (setting, (early, iterations)) against the mirror; returns the mirror's results."""
-    out = {}
-    for st in settings:
-        for early, iters in runs:
-            bits, step, s, o = st
-            m = out[st + (early,)] = mir.decode(llr, bits, step, s, o, early_term=early, iterations=iters)
-            _same(_quantized(d, llr, st, early, iters), m, (st, early))
+    out = against_mirror(settings, runs, lambda st, early, iters: _quantized(d, llr, st, early, iters),
+                         lambda st, early, iters: mir.decode(llr, *st, early_term=early, iterations=iters))
     d.set_min_sum_correction()
     d.set_min_sum_quantization(0)
     return out
@@ -60,7 +44,7 @@ def h_txt():
     """h.txt, 48 frames of the reference stream at -5.0 dB, and a cache of the mirror's results on them."""
     import libldpc_amd
     d = libldpc_amd.HipDecoder(orc.H_TXT)
-    return {"d": d, "llr": _dumped(d, "AWGN", -5.0, 48), "mir": QuantizedMinSumMirror(orc.Code(orc.H_TXT)), "ref": {}}
+    return {"d": d, "llr": dumped(d, _binary64, "AWGN", -5.0, 48), "mir": QuantizedMinSumMirror(orc.Code(orc.H_TXT)), "ref": {}}
 
 
 def _h_ref(h, st, early, iters):
@@ -76,7 +60,7 @@ def test_h_txt(h_txt, setting):
     """Seven settings, each with early termination at 50 iterations and without at 20."""
     d, llr = h_txt["d"], h_txt["llr"]
     for early, iters in ((True, 50), (False, 20)):
-        _same(_quantized(d, llr, setting, early, iters), _h_ref(h_txt, setting, early, iters), (setting, early))
+        same(_quantized(d, llr, setting, early, iters), _h_ref(h_txt, setting, early, iters), (setting, early))
     bits, step = setting[:2]
     sat = float((np.abs(quantize(llr, bits, step)) == (1 << (bits - 1)) - 1).mean())
     print(setting, "channel values at +-Qmax:", sat)
@@ -96,17 +80,12 @@ def test_h_txt_batches(h_txt):
     st = (6, 0.25, 1.0, 0.0)
     m = _h_ref(h_txt, st, True, 50)
     for n in (1, 7):
-        _same(_quantized(d, llr[:n], st, True, 50), m, n, slice(0, n))
+        same(_quantized(d, llr[:n], st, True, 50), m, n, slice(0, n))
     st2 = (5, 0.5, 0.75, 0.5)
-    one = _quantized(d, llr, st2, True, 50)
-    a, b = _quantized(d, llr[:20], st2, True, 50), _quantized(d, llr[20:], st2, True, 50)
-    for k in WANT:
-        assert np.array_equal(np.concatenate((a[k], b[k])), one[k]), k
-    _same(one, _h_ref(h_txt, st2, True, 50), "whole batch")
+    one = check_split_batch(lambda part: _quantized(d, part, st2, True, 50), llr)
+    same(one, _h_ref(h_txt, st2, True, 50), "whole batch")
     for early in (True, False):
-        z = _quantized(d, llr[:3], st, early, 0)
-        assert not z["hard"].any() and not z["llr_out"].view(np.uint64).any() and not z["iters"].any()
-        assert np.array_equal(z["bit_errors"], np.zeros(3, np.uint32))
+        check_no_iteration(_quantized(d, llr[:3], st, early, 0))
     d.set_min_sum_correction()
     d.set_min_sum_quantization(0)
 
@@ -116,7 +95,7 @@ def test_8k_code(h8k_file):
     import libldpc_amd
     d = libldpc_amd.HipDecoder(h8k_file)
     assert 0 < 2 * d.quantized_min_sum_lds_bytes() <= 160 * 1024
-    llr = _dumped(d, "AWGN", 1.4, 8)
+    llr = dumped(d, _binary64, "AWGN", 1.4, 8)
     _against_mirror(d, QuantizedMinSumMirror(orc.Code(h8k_file)), llr, [(6, 0.25, 1.0, 0.0), (5, 0.5, 0.8125, 0.0)],
                     [(True, 25), (False, 25)])
 
@@ -146,7 +125,7 @@ def test_wide_irregular_code(tmp_path):
     d = libldpc_amd.HipDecoder(path)
     with pytest.raises(RuntimeError):
         d.set_min_sum_schedule("layered")  # (a code the layered kernel refuses)
-    llr = _dumped(d, "AWGN", 2.0, 16)
+    llr = dumped(d, _binary64, "AWGN", 2.0, 16)
     assert (np.abs(llr) > 90000).any() and (llr == 0).any()  # shortened columns saturate, punctured ones are zero
     ms = _against_mirror(d, QuantizedMinSumMirror(code), llr, [(6, 0.25, 1.0, 0.0), (5, 0.5, 0.8125, 0.25)],
                          [(True, 15), (False, 15)])
@@ -168,12 +147,12 @@ def test_fused_channel_equals_decode_of_its_llrs():
                 d.stream_begin(ch, 6, x)
                 r = d.stream_decode(64, early_term=early, iterations=30, decoding="BP_MS", want=WANT + ("llr_in",))
                 b = d.decode_batch(r["llr_in"], early_term=early, iterations=30, decoding="BP_MS", want=WANT)
-                _same(b, r, (noise, ch, x, early))
+                same(b, r, (noise, ch, x, early))
                 assert r["iters"].max() > 0
     d.set_noise("reference")
     # ... and it is the quantized decoder that ran: the mirror on the last frames
     m = QuantizedMinSumMirror(orc.Code(orc.H_TXT)).decode(r["llr_in"][:8], 5, 0.5, 0.8125, 0.25, early_term=False, iterations=30)
-    _same({k: r[k][:8] for k in WANT}, m, "mirror")
+    same({k: r[k][:8] for k in WANT}, m, "mirror")
 
 
 def test_nothing_else_moves():

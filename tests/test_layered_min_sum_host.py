@@ -9,6 +9,7 @@ import pytest
 
 import orc
 from layered_minsum_ref import LayeredMinSumMirror
+from minsum_common import check_decode_stages, write
 from minsum_ref import MinSumMirror
 
 
@@ -18,12 +19,6 @@ def lib():
     from libldpc_amd import build
     build.build()
     return libldpc_amd.load_library()
-
-
-def _write(path, rows):
-    """rows: list of column lists -> a parity-check file of "row col" lines."""
-    open(path, "w").write("\n".join(f"{i} {c}" for i, cs in enumerate(rows) for c in cs))
-    return str(path)
 
 
 def test_setter_accepts_and_rejects(lib, tmp_path, h8k_file):
@@ -53,7 +48,7 @@ def test_setter_accepts_and_rejects(lib, tmp_path, h8k_file):
     assert d8.min_sum_schedule == "layered"
     # codes outside what the layered plan takes
     base = [[0, 1, 2], [2, 3, 4], [4, 5, 0], [1, 3, 5]]
-    ok = libldpc_amd.HipDecoder(_write(tmp_path / "ok.txt", base))
+    ok = libldpc_amd.HipDecoder(write(tmp_path / "ok.txt", base))
     ok.set_min_sum_schedule("layered")
     cases = {
         "isolated_column": [[0, 1, 2], [2, 3, 5], [5, 6, 0], [1, 3, 6]],  # column 4 has no edge
@@ -61,7 +56,7 @@ def test_setter_accepts_and_rejects(lib, tmp_path, h8k_file):
         "degree1_row": base + [[3]],
     }
     for name, rows in cases.items():
-        path = _write(tmp_path / f"{name}.txt", rows)
+        path = write(tmp_path / f"{name}.txt", rows)
         if name == "degree1_row":
             # the library takes no such code at all (a check node of degree 1 is undefined in the reference decoder): there is
             # no context to set anything on; should that ever change, the setter's own check (build_layer_plan) still applies
@@ -79,7 +74,7 @@ def test_setter_accepts_and_rejects(lib, tmp_path, h8k_file):
     rows = [[(3 * i + j) % 16384 for j in range(3)] + [(5 * i + 7) % 16384] for i in range(8192)]
     rows = [sorted(set(r)) for r in rows]
     rows += [[c, (c + 1) % 16384] for c in range(0, 16384, 2)]  # every column has an edge
-    big = libldpc_amd.HipDecoder(_write(tmp_path / "big.txt", rows))
+    big = libldpc_amd.HipDecoder(write(tmp_path / "big.txt", rows))
     assert big.layered_min_sum_lds_bytes() > 160 * 1024
     with pytest.raises(RuntimeError, match="LDS"):
         big.set_min_sum_schedule("layered")
@@ -90,18 +85,8 @@ def test_decode_stages(lib, h8k_file):
     """One `whole` launch for BP_MS while the schedule is set; BP keeps its stages."""
     import libldpc_amd
     for path in (orc.H_TXT, h8k_file):
-        d = libldpc_amd.HipDecoder(path)
-        before = {(dec, early, it): d.decode_stages(early, it, dec) for dec in ("BP", "BP_MS") for early in (True, False)
-                  for it in (50, 0)}
-        d.set_min_sum_schedule("layered")
-        for (dec, early, it), st in before.items():
-            now = d.decode_stages(early, it, dec)
-            if dec == "BP_MS":
-                assert now == ["whole"], (path, early, it)
-            else:
-                assert now == st, (path, early, it)
-        d.set_min_sum_schedule("flooding")
-        assert all(d.decode_stages(e, i, dec) == st for (dec, e, i), st in before.items())
+        check_decode_stages(libldpc_amd.HipDecoder(path), lambda d: d.set_min_sum_schedule("layered"),
+                            lambda d: d.set_min_sum_schedule("flooding"))
 
 
 def _awgn_llrs(code, snr_db, n, seed):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import orc
+from minsum_common import check_decode_stages, write
 from minsum_ref import MinSumMirror
 from quantized_minsum_ref import QuantizedMinSumMirror, correction_table, quantize
 
@@ -20,12 +21,6 @@ def lib():
     from libldpc_amd import build
     build.build()
     return libldpc_amd.load_library()
-
-
-def _write(path, rows):
-    """rows: list of column lists -> a parity-check file of "row col" lines."""
-    open(path, "w").write("\n".join(f"{i} {c}" for i, cs in enumerate(rows) for c in cs))
-    return str(path)
 
 
 def test_setter_accepts_and_rejects(lib):
@@ -94,7 +89,7 @@ def test_codes(lib, tmp_path, h8k_file):
         "isolated_column": [[0, 1, 2], [2, 3, 5], [5, 6, 0], [1, 3, 6]],  # column 4 has no edge
     }
     for name, rows in cases.items():
-        path = _write(tmp_path / f"{name}.txt", rows)
+        path = write(tmp_path / f"{name}.txt", rows)
         dd = libldpc_amd.HipDecoder(path)
         with pytest.raises(RuntimeError, match="ldpc_hip_set_min_sum_schedule"):
             dd.set_min_sum_schedule("layered")
@@ -105,7 +100,7 @@ def test_codes(lib, tmp_path, h8k_file):
     nc = 30000
     rows = [sorted({(8 * i + j * (1 + i // 2500)) % nc for j in range(8)}) for i in range(21000)]
     assert all(len(r) == 8 for r in rows) and sum(len(r) for r in rows) > 163840
-    big = libldpc_amd.HipDecoder(_write(tmp_path / "big.txt", rows))
+    big = libldpc_amd.HipDecoder(write(tmp_path / "big.txt", rows))
     assert big.quantized_min_sum_lds_bytes() == -1
     with pytest.raises(RuntimeError, match="LDS"):
         big.set_min_sum_quantization(6, 0.25)
@@ -117,18 +112,8 @@ def test_decode_stages(lib, h8k_file):
     """One `whole` launch for BP_MS while quantization is on; BP keeps its stages; everything back when it is off."""
     import libldpc_amd
     for path in (orc.H_TXT, h8k_file):
-        d = libldpc_amd.HipDecoder(path)
-        before = {(dec, early, it): d.decode_stages(early, it, dec) for dec in ("BP", "BP_MS") for early in (True, False)
-                  for it in (50, 0)}
-        d.set_min_sum_quantization(6, 0.25)
-        for (dec, early, it), st in before.items():
-            now = d.decode_stages(early, it, dec)
-            if dec == "BP_MS":
-                assert now == ["whole"], (path, early, it)
-            else:
-                assert now == st, (path, early, it)
-        d.set_min_sum_quantization(0)
-        assert all(d.decode_stages(e, i, dec) == st for (dec, e, i), st in before.items())
+        check_decode_stages(libldpc_amd.HipDecoder(path), lambda d: d.set_min_sum_quantization(6, 0.25),
+                            lambda d: d.set_min_sum_quantization(0))
 
 
 def test_table():
