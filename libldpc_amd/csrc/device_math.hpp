@@ -43,6 +43,23 @@ __device__ __forceinline__ B load_block3(const B *table, uint32_t i) // {u32, u3
     return B{w0, w1, static_cast<uint16_t>(w2 & 0xFFFFu), static_cast<uint16_t>(w2 >> 16)};
 }
 
+// sum of v over the 64 lanes of the wave, in every lane
+__device__ __forceinline__ int wave_sum(int v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1)
+        v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// the high word of a double (sign, exponent, 20 mantissa bits), and a positive double with a sign bit put in: the
+// likelihood-ratio form keeps hard decisions in the sign bits of its (positive) messages
+__device__ __forceinline__ uint32_t hi_word(double x) { return static_cast<uint32_t>(dm_bits(x) >> 32); }
+__device__ __forceinline__ double with_sign(double mag, uint32_t sign_hi) // mag > 0, sign_hi = 0 or 0x80000000
+{
+    return dm_from_bits(dm_bits(mag) | (static_cast<uint64_t>(sign_hi) << 32));
+}
+
 // decoder.h:7-10 — sign(x) = 1 - 2*signbit(x)
 __device__ __forceinline__ int sgn(double x) { return 1 - 2 * static_cast<int>(__builtin_signbit(x) != 0); }
 

@@ -1082,7 +1082,7 @@ void Engine::run_bec(const DecParams &p, const BatchOut &out, uint64_t n, const 
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t nc = plan_.nc;
     const uint64_t nct = static_cast<uint64_t>(plan_.nct);
-    const size_t state = static_cast<size_t>((plan_.nnz + 15) / 16) * 16 + 2 * ((nc + 15) / 16) * 16;
+    const size_t state = bec_state_bytes(plan_.nnz, plan_.nc);
     OutStage st;
     BecArgs a{};
     a.ws = state > kCuLdsBytes ? static_cast<uint8_t *>(ws_msg_.reserve(n * state)) : nullptr; // beyond LDS: state in memory

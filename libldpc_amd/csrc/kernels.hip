@@ -1,4 +1,4 @@
-// kernels.hip — hand-written HIP kernels for gfx950 (MI355X, wave64).
+// kernels.hip — the flooding decoder: hand-written HIP kernels for gfx950 (MI355X, wave64).
 //
 // Hot path of heat1q/libldpc rebuilt for CDNA4: flooding BP (sum-product / min-sum) with the
 // channel + LLR initialisation fused into the same launch.  One workgroup (4 waves) decodes one frame;
@@ -18,9 +18,7 @@
 //   syndrome early-term    src/decoding/decoder.h:47-64
 //   AWGN channel + LLRs    src/sim/channel.cpp:62-93   (libstdc++ normal_distribution, polar method)
 //   BSC channel + LLRs     src/sim/channel.cpp:129-162
-//   BEC channel + decoder  src/sim/channel.cpp:199-229, src/decoding/decoder.cpp:91-192
-//   encoder                src/sim/channel.cpp:44-60, src/core/sparse.h:163-172
-//   bit-error count        src/sim/ldpcsim.cpp:184-188
+// (the erasure decoder: kernels_bec.hip; the encoder and the batch's counters: sim_kernels.hip)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -31,6 +29,7 @@
 #include "device_cn.hpp"
 #include "device_math.hpp"
 #include "kernels.hpp"
+#include "launch_lds.hpp"
 
 #ifndef LDPC_AMD_DECODE_PRIO
 #define LDPC_AMD_DECODE_PRIO 3
@@ -61,7 +60,6 @@ constexpr int kThreads = kDecodeWaves * kWaveSize;
 #define PHASE_START
 #define PHASE_TICK(acc)
 #endif
-constexpr uint8_t kErasure = 'E'; // functions.h:105
 
 // check-node update on the frame's message array: slot(j) = m[j*stride] (decoder.cpp:25-45, device_cn.hpp)
 template <int D, bool MINSUM, bool CORR = false>
@@ -324,11 +322,6 @@ __device__ __forceinline__ bool cn_pair(double *msg, uint32_t off0, uint32_t off
 // ---- likelihood-ratio form (RATIO instantiations): all messages are positive, so the sign bit of a message slot
 // is free and carries the hard decision of the edge's variable node (set by the VN pass, preserved by the CN
 // pass).  The CN pass therefore sees the syndrome of the previous iteration for free. ----
-__device__ __forceinline__ uint32_t hi_word(double x) { return static_cast<uint32_t>(dm_bits(x) >> 32); }
-__device__ __forceinline__ double with_sign(double mag, uint32_t sign_hi) // mag > 0, sign_hi = 0 or 0x80000000
-{
-    return dm_from_bits(dm_bits(mag) | (static_cast<uint64_t>(sign_hi) << 32));
-}
 
 // SH = 1: the shared-reciprocal form of degree-3 and degree-4 nodes (detmath.h); esc = the frame's escape tracking, which the
 // nodes' denominator products join.  SH = 2: that of degree-6 nodes (codes the LDS-resident decoder does not take); esc = the
@@ -992,14 +985,6 @@ __device__ __forceinline__ double vn_block_llr_lean(double *msg, uint8_t *hb, co
             hb[sl] = bit;
     }
     return out;
-}
-
-__device__ __forceinline__ int wave_sum(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-        v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1819,481 +1804,6 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(5, 5))
     decode_body<true, false, true, MAXD, LLR_MODE, false, false, false, kW5VnBlocks, false, true>(a, blockIdx.x);
 }
 
-// ---------------------------------------------------------------------------------------------
-// BEC: erasure decoder over the alphabet {0, 1, 'E'} (decoder.cpp:91-192), channel fused
-// (channel.cpp:199-229).  All state is bytes in LDS: msg[nnz], sym[nc] (decoder input), lout[nc].
-//
-// The reference runs the forward/backward recursion with
-//   cn_update(l, r) = 'E' if either is 'E' else l xor r                      (decoder.h:152-155)
-//   vn_update(l, r, x) = x if either equals x else 'E'                       (decoder.h:145-148)
-// Both recursions have closed forms over the node's other edges, used here (integer alphabet: the
-// results are the same values, not approximations):
-//   check node, edge j: 'E' if any other input is 'E', else the xor of the other inputs;
-//   erased VN of degree >= 3, edge j: x if any other input equals x, else 'E';
-//   erased VN of degree 2: the other input unchanged; degree 1: see deg1_compat.
-// ---------------------------------------------------------------------------------------------
-__host__ __device__ inline uint32_t bec_state_bytes(int nnz, int nc)
-{
-    return static_cast<uint32_t>(((nnz + 15) / 16) * 16 + 2 * (((nc + 15) / 16) * 16));
-}
-
-__global__ __launch_bounds__(kThreads) void bec_kernel(const BecArgs a)
-{
-    extern __shared__ double lds[];
-    __shared__ int misc[4];
-    const DevPlan &P = a.plan;
-    const int nnz = P.nnz, nc = P.nc, nct = P.nct;
-    // state bytes: LDS, or device memory (a.ws: bec_state_bytes() per frame) for codes beyond 160 KB
-    uint8_t *msg = a.ws ? a.ws + static_cast<uint64_t>(blockIdx.x) * bec_state_bytes(nnz, nc) : reinterpret_cast<uint8_t *>(lds);
-    uint8_t *sym = msg + ((nnz + 15) / 16) * 16;
-    uint8_t *lout = sym + ((nc + 15) / 16) * 16;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const uint64_t frame = blockIdx.x;
-    const uint8_t *cw = a.codeword ? a.codeword + frame * nc : nullptr;
-    auto cw_of_rank = [&](int r) -> uint8_t { return cw ? cw[P.rank_col[r]] : 0; };
-
-    if (tid == 0)
-        misc[0] = 0;
-    // ---- channel: channel.cpp:199-229 ----
-    if (a.raw || a.counter)
-    {
-        for (int r = tid; r < nc; r += kThreads)
-        {
-            uint8_t k = P.rank_kind[r];
-            if (k == 1)
-                sym[r] = kErasure;
-            else if (k == 2)
-            {
-                // channel.cpp:222 indexes the transmitted-symbol vector by the COLUMN index
-                uint32_t col = P.rank_col[r];
-                sym[r] = (col < static_cast<uint32_t>(nct) && cw) ? cw[P.bit_pos[col]] : 0;
-            }
-            else if (k == 3)
-                sym[r] = 0; // never written by the channel: the decoder's initial zero, a known 0 bit
-        }
-        if (a.counter) // counter-based noise (device_philox.hpp): a thread takes the four transmitted bits of a Philox block
-        {
-            for (int b = tid; 4 * b < nct; b += kThreads)
-            {
-                const uint4 w = philox_block(a.ctr_key[0], a.ctr_key[1], a.ctr_frame0 + frame, static_cast<uint32_t>(b), kTagDraw);
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                {
-                    const int i = 4 * b + k;
-                    if (i >= nct)
-                        break;
-                    const uint8_t xb = cw ? cw[P.bit_pos[i]] : 0;
-                    sym[P.tx_rank[i]] = counter_hit(word_of(w, k), a.eps) ? kErasure : xb;
-                }
-            }
-        }
-        else
-        {
-            const uint64_t *raw = a.raw + frame * static_cast<uint64_t>(nct);
-            for (int i = tid; i < nct; i += kThreads)
-            {
-                bool erased = canonical(raw[i]) < a.eps;
-                uint8_t xb = cw ? cw[P.bit_pos[i]] : 0;
-                sym[P.tx_rank[i]] = erased ? kErasure : xb;
-            }
-        }
-    }
-    else
-    {
-        const uint8_t *in = a.symbols + frame * nc;
-        for (int r = tid; r < nc; r += kThreads)
-            sym[r] = in[P.rank_col[r]];
-    }
-    __syncthreads();
-    if (a.llr_in_dump)
-    {
-        double *o = a.llr_in_dump + frame * nc;
-        for (int r = tid; r < nc; r += kThreads)
-            o[P.rank_col[r]] = static_cast<double>(sym[r]);
-    }
-    for (int r = tid; r < nc; r += kThreads)
-        lout[r] = 0; // mLLROut starts zeroed
-
-    // work lists with the block descriptors in place (plan.cpp): one scalar load per block, no dependent second one
-    const auto my_vdesc = uniform_table(P.vn_work_desc + wave * (P.vn_work_stride + 1) * 4);
-    const auto my_cdesc = uniform_table(reinterpret_cast<const uint32_t *>(P.cn_work_desc + wave * P.cn_desc_stride));
-    auto vn_desc = [&](int w) { // count 0 = none (every row ends in one)
-        const uint32_t d0 = my_vdesc[4 * w], d1 = my_vdesc[4 * w + 1], d2 = my_vdesc[4 * w + 2];
-        return VnBlock{d0, d1, static_cast<uint16_t>(d2 & 0xFFFFu), static_cast<uint16_t>(d2 >> 16)};
-    };
-    auto cn_desc = [&](int w) { // count 0 = none (every row ends in two)
-        const uint32_t d0 = my_cdesc[2 * w], d1 = my_cdesc[2 * w + 1];
-        return CnBlock{d0, static_cast<uint16_t>(d1 & 0xFFFFu), static_cast<uint16_t>(d1 >> 16)};
-    };
-    // v2c init: decoder.cpp:96-99
-    for (int w = 0; w < P.vn_work_stride; ++w)
-    {
-        const VnBlock b = vn_desc(w);
-        if (b.count == 0)
-            break;
-        if (lane < b.count)
-        {
-            uint8_t L = sym[b.first + lane];
-            const uint32_t *idx = P.vn_slot + b.idx_off + lane;
-            for (int p = 0; p < b.degree; ++p)
-                msg[idx[p * b.count]] = L;
-        }
-    }
-    __syncthreads();
-
-    uint32_t I = 0;
-    while (I < a.iterations)
-    {
-        // ---- CN update: decoder.cpp:105-123 ----
-        for (int w = 0; w < P.cn_work_stride; ++w)
-        {
-            const CnBlock b = cn_desc(w);
-            if (b.count == 0)
-                break;
-            if (lane < b.count)
-            {
-                uint8_t *m = msg + b.off + lane;
-                int n_e = 0, x = 0;
-                for (int j = 0; j < b.degree; ++j)
-                {
-                    uint8_t v = m[j * b.count];
-                    if (v == kErasure)
-                        ++n_e;
-                    else
-                        x ^= (v != 0);
-                }
-                for (int j = 0; j < b.degree; ++j)
-                {
-                    uint8_t v = m[j * b.count];
-                    uint8_t o;
-                    if (v == kErasure)
-                        o = (n_e == 1) ? static_cast<uint8_t>(x) : kErasure;
-                    else
-                        o = (n_e == 0) ? static_cast<uint8_t>(x ^ (v != 0)) : kErasure;
-                    m[j * b.count] = o;
-                }
-            }
-        }
-        __syncthreads();
-        // ---- VN update: decoder.cpp:126-167 ----
-        int any_e = 0;
-        for (int w = 0; w < P.vn_work_stride; ++w)
-        {
-            const VnBlock b = vn_desc(w);
-            if (b.count == 0)
-                break;
-            if (lane < b.count)
-            {
-                const int r = b.first + lane;
-                const uint32_t *idx = P.vn_slot + b.idx_off + lane;
-                const uint8_t x = cw_of_rank(r);
-                const int vw = b.degree;
-                if (sym[r] != kErasure)
-                {
-                    for (int p = 0; p < vw; ++p)
-                        msg[idx[p * b.count]] = x;
-                    lout[r] = x;
-                }
-                else if (vw == 0)
-                {
-                    // no edges: the reference would index an empty neighbour list; keep the erasure
-                    lout[r] = kErasure;
-                }
-                else if (vw == 1)
-                {
-                    uint8_t c0 = msg[idx[0]];
-                    msg[idx[0]] = a.deg1_compat ? 0 : kErasure;
-                    lout[r] = c0;
-                }
-                else if (vw == 2)
-                {
-                    uint8_t c0 = msg[idx[0]], c1 = msg[idx[b.count]];
-                    msg[idx[0]] = c1;
-                    msg[idx[b.count]] = c0;
-                    lout[r] = (c0 == x || c1 == x) ? x : kErasure;
-                }
-                else
-                {
-                    int hits = 0;
-                    for (int p = 0; p < vw; ++p)
-                        hits += msg[idx[p * b.count]] == x;
-                    for (int p = 0; p < vw; ++p)
-                    {
-                        const uint32_t s = idx[p * b.count];
-                        int own = msg[s] == x;
-                        msg[s] = (hits - own) > 0 ? x : kErasure;
-                    }
-                    lout[r] = hits > 0 ? x : kErasure;
-                }
-                any_e |= lout[r] == kErasure;
-            }
-        }
-        // early termination when no erasure is left (decoder.cpp:169-186); also the barrier of the pass
-        if (a.early_term)
-        {
-            if (!__syncthreads_or(any_e))
-                break;
-        }
-        else
-            __syncthreads();
-        ++I;
-    }
-    __syncthreads();
-
-    if (tid == 0 && a.iters)
-        a.iters[frame] = I;
-    const bool ran = a.iterations > 0;
-    // mCO: decoder.cpp:137,165 — the true bit, or 1 when the VN is still erased (-gf2 is always 1)
-    auto hard_of_rank = [&](int r) -> int {
-        if (!ran)
-            return 0;
-        return lout[r] == kErasure ? 1 : cw_of_rank(r);
-    };
-    if (a.hard)
-    {
-        uint8_t *h = a.hard + frame * nc;
-        for (int r = tid; r < nc; r += kThreads)
-            h[P.rank_col[r]] = static_cast<uint8_t>(hard_of_rank(r));
-    }
-    if (a.llr_out)
-    {
-        double *o = a.llr_out + frame * nc;
-        for (int r = tid; r < nc; r += kThreads)
-            o[P.rank_col[r]] = static_cast<double>(lout[r]);
-    }
-    if (a.bit_errors)
-    {
-        int err = 0;
-        for (int i = tid; i < P.n_bitpos; i += kThreads)
-        {
-            int r = P.tx_rank[i];
-            err += hard_of_rank(r) != static_cast<int>(cw_of_rank(r));
-        }
-        err = wave_sum(err);
-        if (lane == 0 && err)
-            atomicAdd(&misc[0], err);
-        __syncthreads();
-        if (tid == 0)
-            a.bit_errors[frame] = static_cast<uint32_t>(misc[0]);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// encoder (see EncodeArgs)
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void encode_info_kernel(const EncodeArgs a)
-{
-    // one thread per (frame, word): 64 bernoulli(0.5) draws -> one packed word
-    const uint64_t gid = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
-    if (gid >= a.n_frames * static_cast<uint64_t>(a.words))
-        return;
-    const uint64_t f = gid / a.words;
-    const int w = static_cast<int>(gid % a.words);
-    const uint64_t *raw = a.info_raw + f * static_cast<uint64_t>(a.kc) + 64 * w;
-    const int nb = min(64, a.kc - 64 * w);
-    uint64_t bits = 0;
-    for (int i = 0; i < nb; ++i)
-        bits |= static_cast<uint64_t>(canonical(raw[i]) < 0.5) << i;
-    a.prefix[gid] = bits;
-}
-
-// running XOR over frames, one workgroup per packed word column
-__global__ __launch_bounds__(1024) void encode_prefix_kernel(const EncodeArgs a)
-{
-    __shared__ uint64_t part[1024];
-    const int w = blockIdx.x, tid = threadIdx.x;
-    const uint64_t per = (a.n_frames + 1023) / 1024;
-    const uint64_t lo = min(tid * per, a.n_frames), hi = min(lo + per, a.n_frames);
-    uint64_t s = 0;
-    for (uint64_t f = lo; f < hi; ++f)
-        s ^= a.prefix[f * a.words + w];
-    part[tid] = s;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1)
-    {
-        uint64_t v = tid >= o ? part[tid - o] : 0;
-        __syncthreads();
-        part[tid] ^= v;
-        __syncthreads();
-    }
-    uint64_t run = tid ? part[tid - 1] : 0;
-    for (uint64_t f = lo; f < hi; ++f)
-    {
-        run ^= a.prefix[f * a.words + w];
-        a.prefix[f * a.words + w] = run;
-    }
-}
-
-// codeword[f][j] = cw_prev[j] ^ parity(prefix_f restricted to the rows of column j of G)
-__global__ __launch_bounds__(256) void encode_cw_kernel(const EncodeArgs a, uint64_t first_frame)
-{
-    extern __shared__ uint64_t pw[];
-    const uint64_t f = first_frame + blockIdx.x;
-    for (int w = threadIdx.x; w < a.words; w += 256)
-        pw[w] = a.prefix[f * a.words + w] ^ (a.base ? a.base[w] : 0ull);
-    __syncthreads();
-    const bool last = f + 1 == a.n_frames;
-    uint8_t *out = a.codeword ? a.codeword + f * a.nc : nullptr;
-    for (int j = threadIdx.x; j < a.nc; j += 256)
-    {
-        uint8_t b = a.cw_prev[j];
-        if (j < a.g_cols)
-            for (uint32_t p = a.g_col_ptr[j]; p < a.g_col_ptr[j + 1]; ++p)
-            {
-                uint32_t r = a.g_col_row[p];
-                b ^= static_cast<uint8_t>(pw[r >> 6] >> (r & 63) & 1);
-            }
-        if (out)
-            out[j] = b;
-        if (last)
-            a.cw_last[j] = b;
-    }
-}
-
-// the same with the columns of G as bit masks (EncodeArgs::g_mask): a workgroup takes kEncFrames consecutive frames, a thread
-// keeps the masks of its columns in registers (W words each) and the frames' prefixes arrive as scalars — a codeword bit is
-// W ANDs and a population count instead of a walk over the column's entries with a bit test each (the walk: 3.5 ms per
-// 65 536 frames of the n = 1024 code, more than the decode launch it feeds)
-constexpr int kEncFrames = 32, kEncCols = 8; // columns per thread the kernel provides for: nc <= 256 * kEncCols
-template <int W>
-__global__ __launch_bounds__(256) void encode_cw_dense_kernel(const EncodeArgs a, uint64_t first_frame, uint64_t n_do)
-{
-    uint64_t m[kEncCols][W];
-    uint8_t prev[kEncCols];
-#pragma unroll
-    for (int c = 0; c < kEncCols; ++c)
-    {
-        const int j = threadIdx.x + 256 * c;
-        prev[c] = j < a.nc ? a.cw_prev[j] : 0;
-#pragma unroll
-        for (int w = 0; w < W; ++w)
-            m[c][w] = j < a.nc ? a.g_mask[static_cast<size_t>(j) * W + w] : 0;
-    }
-    uint64_t base[W];
-#pragma unroll
-    for (int w = 0; w < W; ++w)
-        base[w] = a.base ? uniform_table(a.base)[w] : 0ull;
-    const uint64_t f0 = first_frame + static_cast<uint64_t>(blockIdx.x) * kEncFrames;
-    const auto pre = uniform_table(a.prefix);
-    for (int k = 0; k < kEncFrames; ++k)
-    {
-        const uint64_t f = f0 + k;
-        if (f >= first_frame + n_do)
-            break;
-        uint64_t p[W];
-#pragma unroll
-        for (int w = 0; w < W; ++w)
-            p[w] = pre[f * W + w] ^ base[w];
-        const bool last = f + 1 == a.n_frames;
-        uint8_t *out = a.codeword ? a.codeword + f * a.nc : nullptr;
-#pragma unroll
-        for (int c = 0; c < kEncCols; ++c)
-        {
-            const int j = threadIdx.x + 256 * c;
-            if (j >= a.nc)
-                break;
-            uint64_t x = 0;
-#pragma unroll
-            for (int w = 0; w < W; ++w)
-                x ^= p[w] & m[c][w];
-            const uint8_t b = prev[c] ^ static_cast<uint8_t>(__popcll(x) & 1);
-            if (out)
-                out[j] = b;
-            if (last)
-                a.cw_last[j] = b;
-        }
-    }
-}
-
-// one workgroup sums the per-frame outputs of a batch (64 K frames: 64 per thread) into the five counters of the
-// simulation loop (ldpcsim.cpp:175-200): frames, frame errors, bit errors, iterations, early stops
-__global__ __launch_bounds__(1024) void batch_counters_kernel(const uint32_t *iters, const uint32_t *bit_errors, uint64_t n,
-                                                              uint32_t max_iters, int early_term, long long *counters)
-{
-    __shared__ long long part[4][16];
-    long long fe = 0, be = 0, it = 0, es = 0;
-    auto take = [&](uint32_t b, uint32_t t) { fe += b > 0, be += b, it += t, es += early_term && t < max_iters; };
-    // four frames per load, four loads in flight per array: the kernel sits between two batches' decode launches, and 64
-    // dependent round trips per thread (one frame per load) were 35 us of every step
-    uint64_t done = 0;
-    if ((reinterpret_cast<uintptr_t>(iters) | reinterpret_cast<uintptr_t>(bit_errors)) % 16 == 0)
-    {
-        const uint4 *b4 = reinterpret_cast<const uint4 *>(bit_errors), *t4 = reinterpret_cast<const uint4 *>(iters);
-        const uint64_t n4 = n / 4;
-        uint64_t i = threadIdx.x;
-        for (; i + 3 * 1024 < n4; i += 4 * 1024)
-        {
-            uint4 b[4], t[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                b[k] = b4[i + k * 1024], t[k] = t4[i + k * 1024];
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                take(b[k].x, t[k].x), take(b[k].y, t[k].y), take(b[k].z, t[k].z), take(b[k].w, t[k].w);
-        }
-        for (; i < n4; i += 1024)
-        {
-            const uint4 b = b4[i], t = t4[i];
-            take(b.x, t.x), take(b.y, t.y), take(b.z, t.z), take(b.w, t.w);
-        }
-        done = n4 * 4;
-    }
-    for (uint64_t i = done + threadIdx.x; i < n; i += 1024)
-        take(bit_errors[i], iters[i]);
-    auto wave_total = [](long long v) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1)
-            v += __shfl_xor(v, o, 64);
-        return v;
-    };
-    fe = wave_total(fe), be = wave_total(be), it = wave_total(it), es = wave_total(es);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0)
-        part[0][wave] = fe, part[1][wave] = be, part[2][wave] = it, part[3][wave] = es;
-    __syncthreads();
-    if (threadIdx.x < 4)
-    {
-        long long s = 0;
-        for (int w = 0; w < 16; ++w)
-            s += part[threadIdx.x][w];
-        counters[1 + threadIdx.x] = s;
-    }
-    if (threadIdx.x == 4)
-        counters[0] = static_cast<long long>(n);
-}
-
-// operands a = 2^ea * ma, b = 2^eb * mb with ea, eb in [-500, 500] and random mantissas: a, b, a/b inside 2^-+1001
-__global__ __launch_bounds__(256) void division_selftest_kernel(uint64_t n, uint64_t seed, unsigned long long *mismatches)
-{
-    unsigned long long bad = 0;
-    for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull)
-    {
-        uint64_t x = (i + 1) * 0x9E3779B97F4A7C15ull ^ seed;
-        auto next = [&] {
-            x ^= x >> 12, x ^= x << 25, x ^= x >> 27;
-            return x * 0x2545F4914F6CDD1Dull;
-        };
-        auto operand = [&] {
-            const uint64_t m = next() >> 12, e = 1023 - 500 + (next() >> 33) % 1001;
-            return dm_from_bits((e << 52) | m);
-        };
-        const double a = operand(), b = operand();
-        volatile double bv = b; // keep the compiler from folding the two forms together
-        bad += dm_bits(dm_ratio_div(a, b)) != dm_bits(a / bv);
-        // dm_div_by (detmath.h): numerators of either sign up to 2^8 over divisors in [2^-7, 2^7] with THEIR correctly rounded
-        // reciprocal (here: the device's own IEEE division, which is correctly rounded) — the channel's 2 y / sigma^2
-        const uint64_t m2 = next() >> 12, e2 = 1023 - 7 + (next() >> 33) % 15;
-        const double d = dm_from_bits((e2 << 52) | m2);
-        volatile double dv = d;
-        const double rcp = 1.0 / dv;
-        const uint64_t m3 = next() >> 12, e3 = 1023 - 60 + (next() >> 33) % 69, s3 = next() >> 63;
-        const double num = dm_from_bits((s3 << 63) | (e3 << 52) | m3);
-        bad += dm_bits(dm_div_by(num, d, rcp)) != dm_bits(num / dv);
-    }
-    if (bad)
-        atomicAdd(mismatches, bad);
-}
-
 using DecodeKernel = void (*)(const DecodeArgs);
 
 // The kernel of a stage, or null where this decoder has none.  w5: the instantiations for small codes (at most kW5VnBlocks VN
@@ -2357,14 +1867,9 @@ int launch_decode_impl(const DecodeArgs &a, Stage stage, bool min_sum, uint32_t 
                                      : decode_kernel_of<false, LDS_RESIDENT, MAXD, LLR_MODE>(stage, min_sum, a.ms_correct, w5);
     if (!k)
         return hipErrorInvalidValue;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       static_cast<int>(lds_bytes));
-    if (e != hipSuccess)
-        return e;
     // (the chain kernel's small grid walks the list)
     const unsigned grid = static_cast<unsigned>(stage == Stage::kListChain ? std::min<uint64_t>(a.n_frames, 1024) : a.n_frames);
-    hipLaunchKernelGGL(k, dim3(grid), dim3(kThreads), lds_bytes, static_cast<hipStream_t>(stream), a);
-    return hipGetLastError();
+    return launch_with_lds(k, dim3(grid), dim3(kThreads), lds_bytes, stream, a);
 }
 
 template <bool LDS_RESIDENT, int MAXD, int LLR_MODE>
@@ -2418,89 +1923,6 @@ int launch_decode_mem(const DecodeArgs &a, Stage stage, bool min_sum, int max_cn
     if (max_cn_degree > 16 && (!a.ws_scr || stage != Stage::kWhole)) // wide nodes: scratch needed, no likelihood-ratio form
         return hipErrorInvalidValue;
     return launch_decode<false, 16, kLlrMem>(a, stage, min_sum, occupancy_lds, stream);
-}
-
-int launch_batch_counters(const uint32_t *iters, const uint32_t *bit_errors, uint64_t n, uint32_t max_iters, int early_term,
-                          long long *counters, void *stream)
-{
-    hipLaunchKernelGGL(batch_counters_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), iters, bit_errors, n,
-                       max_iters, early_term, counters);
-    return hipGetLastError();
-}
-
-int launch_division_selftest(uint64_t n, uint64_t seed, unsigned long long *mismatches, void *stream)
-{
-    if (n == 0)
-        return hipSuccess;
-    const unsigned blocks = static_cast<unsigned>(std::min<uint64_t>((n + 255) / 256, 8192));
-    hipLaunchKernelGGL(division_selftest_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), n, seed,
-                       mismatches);
-    return hipGetLastError();
-}
-
-int launch_bec(const BecArgs &a, void *stream)
-{
-    if (a.n_frames == 0)
-        return hipSuccess;
-    // codes whose bit-sliced state fits LDS: 64 frames per workgroup (kernels_bec.hip)
-    if (!a.ws && bec_sliced_fits(a.plan))
-        return launch_bec_sliced(a, stream);
-    const uint32_t lds = a.ws ? 16u : bec_state_bytes(a.plan.nnz, a.plan.nc);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(bec_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    if (e != hipSuccess)
-        return e;
-    hipLaunchKernelGGL(bec_kernel, dim3(static_cast<unsigned>(a.n_frames)), dim3(kThreads), lds,
-                       static_cast<hipStream_t>(stream), a);
-    return hipGetLastError();
-}
-
-int launch_encode_prefix(const EncodeArgs &a, void *stream)
-{
-    if (a.n_frames == 0)
-        return hipSuccess;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint64_t items = a.n_frames * static_cast<uint64_t>(a.words);
-    hipLaunchKernelGGL(encode_info_kernel, dim3(static_cast<unsigned>((items + 255) / 256)), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(encode_prefix_kernel, dim3(a.words), dim3(1024), 0, s, a);
-    return hipGetLastError();
-}
-
-int launch_encode_codewords(const EncodeArgs &a, void *stream, bool only_last)
-{
-    if (a.n_frames == 0)
-        return hipSuccess;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t lds = sizeof(uint64_t) * a.words;
-    const bool all = !only_last && a.codeword;
-    if (a.g_mask && a.words <= 4 && a.nc <= 256 * kEncCols)
-    {
-        const uint64_t first = all ? 0 : a.n_frames - 1, n_do = all ? a.n_frames : 1;
-        const dim3 grid(static_cast<unsigned>((n_do + kEncFrames - 1) / kEncFrames));
-        switch (a.words)
-        {
-        case 1: hipLaunchKernelGGL(encode_cw_dense_kernel<1>, grid, dim3(256), 0, s, a, first, n_do); break;
-        case 2: hipLaunchKernelGGL(encode_cw_dense_kernel<2>, grid, dim3(256), 0, s, a, first, n_do); break;
-        case 3: hipLaunchKernelGGL(encode_cw_dense_kernel<3>, grid, dim3(256), 0, s, a, first, n_do); break;
-        default: hipLaunchKernelGGL(encode_cw_dense_kernel<4>, grid, dim3(256), 0, s, a, first, n_do); break;
-        }
-        return hipGetLastError();
-    }
-    if (all)
-        hipLaunchKernelGGL(encode_cw_kernel, dim3(static_cast<unsigned>(a.n_frames)), dim3(256), lds, s, a, uint64_t(0));
-    else
-        hipLaunchKernelGGL(encode_cw_kernel, dim3(1), dim3(256), lds, s, a, a.n_frames - 1);
-    return hipGetLastError();
-}
-
-int launch_encode(const EncodeArgs &a, void *stream)
-{
-    if (a.n_frames == 0)
-        return hipSuccess;
-    int rc = launch_encode_prefix(a, stream);
-    if (rc != hipSuccess)
-        return rc;
-    return launch_encode_codewords(a, stream, a.codeword == nullptr); // (no codewords wanted: only the running one after the batch)
 }
 
 } // namespace ldpc_amd

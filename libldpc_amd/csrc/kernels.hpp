@@ -1,4 +1,4 @@
-// kernels.hpp — host-visible launch interface of the HIP kernels (kernels.hip).
+// kernels.hpp — host-visible launch interface of the HIP kernels (the .hip files of this directory).
 #pragma once
 
 #include <cstddef>
@@ -216,16 +216,21 @@ struct BecArgs
     uint8_t *hard;
     double *llr_out;     // symbol values 0, 1, 'E' widened to double
     double *llr_in_dump;
-    uint8_t *ws;         // per-frame state in device memory (codes whose nnz + 2 nc bytes exceed LDS), else nullptr
+    uint8_t *ws;         // per-frame state in device memory (codes whose bec_state_bytes() exceed LDS), else nullptr
     // counter-based noise (device_philox.hpp; raw == nullptr, symbols == nullptr): erasures from (ctr_key, ctr_frame0 + frame, bit)
     int counter;
     uint32_t ctr_key[2];
     uint64_t ctr_frame0;
 };
 
-// erasure decoder, 64 frames per workgroup (kernels_bec.hip); launch_bec (kernels.hip) takes it when the code fits
-bool bec_sliced_fits(const DevPlan &p);
-int launch_bec_sliced(const BecArgs &a, void *stream);
+// bytes of a frame's state in the byte-per-message erasure kernel (bec_kernel, kernels_bec.hip): msg[nnz], sym[nc], lout[nc],
+// each array from a 16-byte boundary.  Beyond kCuLdsBytes the state lives in device memory (BecArgs::ws)
+constexpr uint32_t bec_state_bytes(int nnz, int nc)
+{
+    return static_cast<uint32_t>(((nnz + 15) / 16) * 16 + 2 * (((nc + 15) / 16) * 16));
+}
+// the erasure decoder (kernels_bec.hip): bit-sliced, 32 frames per workgroup, where that state fits LDS, else bec_kernel
+int launch_bec(const BecArgs &a, void *stream);
 
 // All launchers enqueue on `stream` (hipStream_t passed as void*) and return a hipError_t as int.
 // LDS-resident decoder; llr_mode: 0 input LLRs in LDS, 2 in registers (needs plan.vn_work_stride <= 8 and no isolated
@@ -279,7 +284,6 @@ struct QmsArgs
     uint32_t lut[32];
 };
 int launch_decode_qms(const DecodeArgs &a, const DevQmsPlan &Q, const QmsArgs &q, void *stream);
-int launch_bec(const BecArgs &a, void *stream);
 
 // ---- mt19937_64 on the device ----
 constexpr int kMtN = 312;
@@ -348,7 +352,7 @@ struct NormalsResult
 int launch_normals_finish(const uint32_t *counts, uint32_t n, uint32_t n_piece, uint32_t n_full, uint64_t need, uint64_t target,
                           uint64_t *cum, NormalsResult *result, void *stream);
 
-// GF(2) encoding on the reference's info-word stream (channel.cpp:44-60, sparse.h:163-172).
+// GF(2) encoding on the reference's info-word stream (channel.cpp:44-60, sparse.h:163-172); sim_kernels.hip.
 // The reference draws kc bernoulli(0.5) bits per frame from mt19937_64(seed << 1) and ACCUMULATES u*G
 // into the codeword it never clears, so the codeword of frame f is cw_prev ^ (u_0 ^ ... ^ u_f) G:
 //   encode_info_kernel   info bit i of frame f = canonical(info_raw[f*kc + i]) < 0.5, packed 64 per word
@@ -387,11 +391,11 @@ int launch_philox(uint64_t seed, uint32_t tag, uint64_t frame, uint32_t first_bl
 // info bits 64 w .. 64 w + 63 of frame frame0 + f (bits from kc on zero)
 int launch_encode_info_counter(uint64_t seed, uint64_t frame0, uint64_t n, int kc, int words, uint64_t *prefix, void *stream);
 
-// {frames, frame errors, bit errors, iterations, early stops} of a batch (all device pointers), one launch
+// {frames, frame errors, bit errors, iterations, early stops} of a batch (all device pointers), one launch (sim_kernels.hip)
 int launch_batch_counters(const uint32_t *iters, const uint32_t *bit_errors, uint64_t n, uint32_t max_iters, int early_term,
                           long long *counters, void *stream);
 
-// dm_ratio_div vs the IEEE division on n pseudo-random operand pairs; *mismatches (device, zeroed by the caller)
+// selftest.hip: dm_ratio_div vs the IEEE division on n pseudo-random operand pairs; *mismatches (device, zeroed by the caller)
 int launch_division_selftest(uint64_t n, uint64_t seed, unsigned long long *mismatches, void *stream);
 
 // functions of detmath.h / device_cn.hpp evaluated element by element (include/ldpc_amd.h: ldpc_hip_selftest_math)

@@ -1,14 +1,16 @@
-// kernels_bec.hip — erasure decoding (BASELINE config 5, BEC) bit-sliced over 32 frames.
+// kernels_bec.hip — the erasure decoder (BASELINE config 5, BEC; channel + decoder: src/sim/channel.cpp:199-229,
+// src/decoding/decoder.cpp:91-192): bit-sliced over 32 frames where that state fits LDS (bec_sliced_kernel), a byte per
+// message and one frame per workgroup for every other code (bec_kernel, below it); launch_bec chooses.
 //
 // The erasure decoder's alphabet is {0, 1, 'E'} and its two updates are closed forms over a node's other edges
-// (src/decoding/decoder.cpp:96-186, decoder.h:145-155; kernels.hip states them): integer work, two bits per message.  One
+// (src/decoding/decoder.cpp:96-186, decoder.h:145-155; stated above bec_kernel): integer work, two bits per message.  One
 // workgroup therefore decodes THIRTY-TWO consecutive frames at once: every message, symbol and output is a pair of 32-bit
 // words in LDS — bit f of E = "erased in frame f", bit f of V = the value where it is not (V & E = 0 throughout) — and a
 // lane that visits a node updates it for all 32 frames with a dozen bitwise instructions.  (32, not 64: the vector ALU is
 // 32 bits wide, so a 64-bit word buys nothing per instruction; with 32 frames a group's state is 52 KB for h.txt and three
 // groups share a CU — one's channel prologue, which waits for memory, runs under the others' passes — and the group's pass
 // count, the maximum over its frames, is smaller.  Measured: 0.68 ms per 65 536 frames with 64-frame groups of 1024 threads.)  Per frame the results are
-// exactly the byte-per-message kernel's (bec_kernel, kernels.hip — which remains for codes whose sliced state exceeds LDS):
+// exactly the byte-per-message kernel's (bec_kernel — which remains for codes whose sliced state exceeds LDS):
 //   check node, edge j     'E' if another input is erased, else the xor of the others.  Erased inputs are counted up to two
 //                          bitwise (c0 = one or more, c1 = two or more): "no OTHER input erased" = ~c1 & (~c0 | E_j);
 //   variable node          received symbol known: every output and the node's value are the transmitted bit x;
@@ -31,6 +33,7 @@
 #include "device_math.hpp"
 #include "device_philox.hpp"
 #include "kernels.hpp"
+#include "launch_lds.hpp"
 
 namespace ldpc_amd
 {
@@ -38,14 +41,15 @@ namespace ldpc_amd
 namespace
 {
 
-constexpr int kBecThreads = 512, kBecWaves = kBecThreads / 64;
+constexpr int kThreads = kDecodeWaves * kWaveSize; // bec_kernel: the workgroup the plan's work lists are dealt to
+constexpr int kBecThreads = 512, kBecWaves = kBecThreads / 64; // the bit-sliced kernels
 constexpr int kBecFrames = 32; // frames per group = bits per word
 #ifndef LDPC_AMD_BEC_WIDE
 #define LDPC_AMD_BEC_WIDE 8
 #endif
 constexpr int kBecWideDegree = LDPC_AMD_BEC_WIDE; // variable nodes from this degree on are handled by four lanes each
 using word_t = uint32_t;
-constexpr uint8_t kErasureSym = 'E'; // functions.h:105
+constexpr uint8_t kErasure = 'E'; // functions.h:105
 
 __device__ __forceinline__ word_t wave_or(word_t v)
 {
@@ -180,7 +184,7 @@ __device__ __forceinline__ void bec_sliced_body(const BecArgs &a)
         for (int r = tid; r < nc; r += kBecThreads)
         {
             const uint8_t *s = in + P.rank_col[r];
-            const word_t se = slice(nf, valid, [&](int f) { return s[static_cast<size_t>(f) * nc] == kErasureSym; });
+            const word_t se = slice(nf, valid, [&](int f) { return s[static_cast<size_t>(f) * nc] == kErasure; });
             const word_t sv = slice(nf, valid, [&](int f) { return s[static_cast<size_t>(f) * nc] != 0; }) & ~se;
             SE[r] = se, LV[r] = sv;
         }
@@ -194,7 +198,7 @@ __device__ __forceinline__ void bec_sliced_body(const BecArgs &a)
             const word_t se = SE[r], sv = LV[r];
             double *d = o + P.rank_col[r];
             for (int f = 0; f < nf; ++f)
-                d[static_cast<size_t>(f) * nc] = (se >> f) & 1 ? static_cast<double>(kErasureSym) : static_cast<double>((sv >> f) & 1);
+                d[static_cast<size_t>(f) * nc] = (se >> f) & 1 ? static_cast<double>(kErasure) : static_cast<double>((sv >> f) & 1);
         }
     }
     // ---- v2c init: decoder.cpp:96-99 ----
@@ -459,7 +463,7 @@ __device__ __forceinline__ void bec_sliced_body(const BecArgs &a)
             const word_t le = LE[r], lv = LV[r];
             double *d = o + P.rank_col[r];
             for (int f = 0; f < nf; ++f)
-                d[static_cast<size_t>(f) * nc] = (le >> f) & 1 ? static_cast<double>(kErasureSym) : static_cast<double>((lv >> f) & 1);
+                d[static_cast<size_t>(f) * nc] = (le >> f) & 1 ? static_cast<double>(kErasure) : static_cast<double>((lv >> f) & 1);
         }
     }
     if (a.bit_errors)
@@ -497,7 +501,259 @@ __global__ __launch_bounds__(kBecThreads) __attribute__((amdgpu_waves_per_eu(6, 
     bec_sliced_body<true>(a);
 }
 
-} // namespace
+// ---------------------------------------------------------------------------------------------
+// BEC: erasure decoder over the alphabet {0, 1, 'E'} (decoder.cpp:91-192), channel fused
+// (channel.cpp:199-229).  All state is bytes in LDS: msg[nnz], sym[nc] (decoder input), lout[nc].
+//
+// The reference runs the forward/backward recursion with
+//   cn_update(l, r) = 'E' if either is 'E' else l xor r                      (decoder.h:152-155)
+//   vn_update(l, r, x) = x if either equals x else 'E'                       (decoder.h:145-148)
+// Both recursions have closed forms over the node's other edges, used here (integer alphabet: the
+// results are the same values, not approximations):
+//   check node, edge j: 'E' if any other input is 'E', else the xor of the other inputs;
+//   erased VN of degree >= 3, edge j: x if any other input equals x, else 'E';
+//   erased VN of degree 2: the other input unchanged; degree 1: see deg1_compat.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void bec_kernel(const BecArgs a)
+{
+    extern __shared__ double lds[];
+    __shared__ int misc[4];
+    const DevPlan &P = a.plan;
+    const int nnz = P.nnz, nc = P.nc, nct = P.nct;
+    // state bytes: LDS, or device memory (a.ws: bec_state_bytes() per frame) for codes beyond 160 KB
+    uint8_t *msg = a.ws ? a.ws + static_cast<uint64_t>(blockIdx.x) * bec_state_bytes(nnz, nc) : reinterpret_cast<uint8_t *>(lds);
+    uint8_t *sym = msg + ((nnz + 15) / 16) * 16;
+    uint8_t *lout = sym + ((nc + 15) / 16) * 16;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint64_t frame = blockIdx.x;
+    const uint8_t *cw = a.codeword ? a.codeword + frame * nc : nullptr;
+    auto cw_of_rank = [&](int r) -> uint8_t { return cw ? cw[P.rank_col[r]] : 0; };
+
+    if (tid == 0)
+        misc[0] = 0;
+    // ---- channel: channel.cpp:199-229 ----
+    if (a.raw || a.counter)
+    {
+        for (int r = tid; r < nc; r += kThreads)
+        {
+            uint8_t k = P.rank_kind[r];
+            if (k == 1)
+                sym[r] = kErasure;
+            else if (k == 2)
+            {
+                // channel.cpp:222 indexes the transmitted-symbol vector by the COLUMN index
+                uint32_t col = P.rank_col[r];
+                sym[r] = (col < static_cast<uint32_t>(nct) && cw) ? cw[P.bit_pos[col]] : 0;
+            }
+            else if (k == 3)
+                sym[r] = 0; // never written by the channel: the decoder's initial zero, a known 0 bit
+        }
+        if (a.counter) // counter-based noise (device_philox.hpp): a thread takes the four transmitted bits of a Philox block
+        {
+            for (int b = tid; 4 * b < nct; b += kThreads)
+            {
+                const uint4 w = philox_block(a.ctr_key[0], a.ctr_key[1], a.ctr_frame0 + frame, static_cast<uint32_t>(b), kTagDraw);
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                {
+                    const int i = 4 * b + k;
+                    if (i >= nct)
+                        break;
+                    const uint8_t xb = cw ? cw[P.bit_pos[i]] : 0;
+                    sym[P.tx_rank[i]] = counter_hit(word_of(w, k), a.eps) ? kErasure : xb;
+                }
+            }
+        }
+        else
+        {
+            const uint64_t *raw = a.raw + frame * static_cast<uint64_t>(nct);
+            for (int i = tid; i < nct; i += kThreads)
+            {
+                bool erased = canonical(raw[i]) < a.eps;
+                uint8_t xb = cw ? cw[P.bit_pos[i]] : 0;
+                sym[P.tx_rank[i]] = erased ? kErasure : xb;
+            }
+        }
+    }
+    else
+    {
+        const uint8_t *in = a.symbols + frame * nc;
+        for (int r = tid; r < nc; r += kThreads)
+            sym[r] = in[P.rank_col[r]];
+    }
+    __syncthreads();
+    if (a.llr_in_dump)
+    {
+        double *o = a.llr_in_dump + frame * nc;
+        for (int r = tid; r < nc; r += kThreads)
+            o[P.rank_col[r]] = static_cast<double>(sym[r]);
+    }
+    for (int r = tid; r < nc; r += kThreads)
+        lout[r] = 0; // mLLROut starts zeroed
+
+    // work lists with the block descriptors in place (plan.cpp): one scalar load per block, no dependent second one
+    const auto my_vdesc = uniform_table(P.vn_work_desc + wave * (P.vn_work_stride + 1) * 4);
+    const auto my_cdesc = uniform_table(reinterpret_cast<const uint32_t *>(P.cn_work_desc + wave * P.cn_desc_stride));
+    auto vn_desc = [&](int w) { // count 0 = none (every row ends in one)
+        const uint32_t d0 = my_vdesc[4 * w], d1 = my_vdesc[4 * w + 1], d2 = my_vdesc[4 * w + 2];
+        return VnBlock{d0, d1, static_cast<uint16_t>(d2 & 0xFFFFu), static_cast<uint16_t>(d2 >> 16)};
+    };
+    auto cn_desc = [&](int w) { // count 0 = none (every row ends in two)
+        const uint32_t d0 = my_cdesc[2 * w], d1 = my_cdesc[2 * w + 1];
+        return CnBlock{d0, static_cast<uint16_t>(d1 & 0xFFFFu), static_cast<uint16_t>(d1 >> 16)};
+    };
+    // v2c init: decoder.cpp:96-99
+    for (int w = 0; w < P.vn_work_stride; ++w)
+    {
+        const VnBlock b = vn_desc(w);
+        if (b.count == 0)
+            break;
+        if (lane < b.count)
+        {
+            uint8_t L = sym[b.first + lane];
+            const uint32_t *idx = P.vn_slot + b.idx_off + lane;
+            for (int p = 0; p < b.degree; ++p)
+                msg[idx[p * b.count]] = L;
+        }
+    }
+    __syncthreads();
+
+    uint32_t I = 0;
+    while (I < a.iterations)
+    {
+        // ---- CN update: decoder.cpp:105-123 ----
+        for (int w = 0; w < P.cn_work_stride; ++w)
+        {
+            const CnBlock b = cn_desc(w);
+            if (b.count == 0)
+                break;
+            if (lane < b.count)
+            {
+                uint8_t *m = msg + b.off + lane;
+                int n_e = 0, x = 0;
+                for (int j = 0; j < b.degree; ++j)
+                {
+                    uint8_t v = m[j * b.count];
+                    if (v == kErasure)
+                        ++n_e;
+                    else
+                        x ^= (v != 0);
+                }
+                for (int j = 0; j < b.degree; ++j)
+                {
+                    uint8_t v = m[j * b.count];
+                    uint8_t o;
+                    if (v == kErasure)
+                        o = (n_e == 1) ? static_cast<uint8_t>(x) : kErasure;
+                    else
+                        o = (n_e == 0) ? static_cast<uint8_t>(x ^ (v != 0)) : kErasure;
+                    m[j * b.count] = o;
+                }
+            }
+        }
+        __syncthreads();
+        // ---- VN update: decoder.cpp:126-167 ----
+        int any_e = 0;
+        for (int w = 0; w < P.vn_work_stride; ++w)
+        {
+            const VnBlock b = vn_desc(w);
+            if (b.count == 0)
+                break;
+            if (lane < b.count)
+            {
+                const int r = b.first + lane;
+                const uint32_t *idx = P.vn_slot + b.idx_off + lane;
+                const uint8_t x = cw_of_rank(r);
+                const int vw = b.degree;
+                if (sym[r] != kErasure)
+                {
+                    for (int p = 0; p < vw; ++p)
+                        msg[idx[p * b.count]] = x;
+                    lout[r] = x;
+                }
+                else if (vw == 0)
+                {
+                    // no edges: the reference would index an empty neighbour list; keep the erasure
+                    lout[r] = kErasure;
+                }
+                else if (vw == 1)
+                {
+                    uint8_t c0 = msg[idx[0]];
+                    msg[idx[0]] = a.deg1_compat ? 0 : kErasure;
+                    lout[r] = c0;
+                }
+                else if (vw == 2)
+                {
+                    uint8_t c0 = msg[idx[0]], c1 = msg[idx[b.count]];
+                    msg[idx[0]] = c1;
+                    msg[idx[b.count]] = c0;
+                    lout[r] = (c0 == x || c1 == x) ? x : kErasure;
+                }
+                else
+                {
+                    int hits = 0;
+                    for (int p = 0; p < vw; ++p)
+                        hits += msg[idx[p * b.count]] == x;
+                    for (int p = 0; p < vw; ++p)
+                    {
+                        const uint32_t s = idx[p * b.count];
+                        int own = msg[s] == x;
+                        msg[s] = (hits - own) > 0 ? x : kErasure;
+                    }
+                    lout[r] = hits > 0 ? x : kErasure;
+                }
+                any_e |= lout[r] == kErasure;
+            }
+        }
+        // early termination when no erasure is left (decoder.cpp:169-186); also the barrier of the pass
+        if (a.early_term)
+        {
+            if (!__syncthreads_or(any_e))
+                break;
+        }
+        else
+            __syncthreads();
+        ++I;
+    }
+    __syncthreads();
+
+    if (tid == 0 && a.iters)
+        a.iters[frame] = I;
+    const bool ran = a.iterations > 0;
+    // mCO: decoder.cpp:137,165 — the true bit, or 1 when the VN is still erased (-gf2 is always 1)
+    auto hard_of_rank = [&](int r) -> int {
+        if (!ran)
+            return 0;
+        return lout[r] == kErasure ? 1 : cw_of_rank(r);
+    };
+    if (a.hard)
+    {
+        uint8_t *h = a.hard + frame * nc;
+        for (int r = tid; r < nc; r += kThreads)
+            h[P.rank_col[r]] = static_cast<uint8_t>(hard_of_rank(r));
+    }
+    if (a.llr_out)
+    {
+        double *o = a.llr_out + frame * nc;
+        for (int r = tid; r < nc; r += kThreads)
+            o[P.rank_col[r]] = static_cast<double>(lout[r]);
+    }
+    if (a.bit_errors)
+    {
+        int err = 0;
+        for (int i = tid; i < P.n_bitpos; i += kThreads)
+        {
+            int r = P.tx_rank[i];
+            err += hard_of_rank(r) != static_cast<int>(cw_of_rank(r));
+        }
+        err = wave_sum(err);
+        if (lane == 0 && err)
+            atomicAdd(&misc[0], err);
+        __syncthreads();
+        if (tid == 0)
+            a.bit_errors[frame] = static_cast<uint32_t>(misc[0]);
+    }
+}
 
 uint32_t bec_sliced_lds_bytes(const DevPlan &p)
 {
@@ -508,23 +764,28 @@ bool bec_sliced_fits(const DevPlan &p)
 {
     // (n_bitpos words reuse the message array; block descriptors as kernels.hpp lays them out: 8 and 12 bytes)
     // (a wave's work list lives in the 64 lanes of a register: check-node blocks / 8, variable-node items / 8 <= 64)
-    return bec_sliced_lds_bytes(p) <= 160u * 1024u - 1024u && p.n_bitpos <= p.nnz && p.nnz > 0 && p.nnz < 65536 &&
+    return bec_sliced_lds_bytes(p) <= kCuLdsBytes - 1024u && p.n_bitpos <= p.nnz && p.nnz > 0 && p.nnz < 65536 &&
            p.n_cn_blocks <= 512 && 4 * p.n_vn_blocks <= 512;
 }
 
 int launch_bec_sliced(const BecArgs &a, void *stream)
 {
+    static_assert(sizeof(CnBlock) == 8 && sizeof(VnBlock) == 12, "block descriptors are read as 2 / 3 scalar words");
+    void (*k)(const BecArgs) = a.counter ? bec_sliced_ctr_kernel : bec_sliced_kernel;
+    return launch_with_lds(k, dim3(static_cast<unsigned>((a.n_frames + kBecFrames - 1) / kBecFrames)), dim3(kBecThreads),
+                           bec_sliced_lds_bytes(a.plan), stream, a);
+}
+
+} // namespace
+
+int launch_bec(const BecArgs &a, void *stream)
+{
     if (a.n_frames == 0)
         return hipSuccess;
-    static_assert(sizeof(CnBlock) == 8 && sizeof(VnBlock) == 12, "block descriptors are read as 2 / 3 scalar words");
-    const uint32_t lds = bec_sliced_lds_bytes(a.plan);
-    void (*k)(const BecArgs) = a.counter ? bec_sliced_ctr_kernel : bec_sliced_kernel;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    if (e != hipSuccess)
-        return e;
-    hipLaunchKernelGGL(k, dim3(static_cast<unsigned>((a.n_frames + kBecFrames - 1) / kBecFrames)), dim3(kBecThreads), lds,
-                       static_cast<hipStream_t>(stream), a);
-    return hipGetLastError();
+    if (!a.ws && bec_sliced_fits(a.plan))
+        return launch_bec_sliced(a, stream);
+    const uint32_t lds = a.ws ? 16u : bec_state_bytes(a.plan.nnz, a.plan.nc);
+    return launch_with_lds(bec_kernel, dim3(static_cast<unsigned>(a.n_frames)), dim3(kThreads), lds, stream, a);
 }
 
 } // namespace ldpc_amd

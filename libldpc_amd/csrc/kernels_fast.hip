@@ -189,14 +189,6 @@ __device__ __forceinline__ float vn_fast_wide(float *msg, const uint32_t (&packe
     }
 }
 
-__device__ __forceinline__ int wave_sum_fast(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-        v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 template <bool WANT_LLR>
 __global__ __launch_bounds__(kFastThreads) void decode_fast_kernel(const DecodeArgs a)
 {
@@ -401,7 +393,7 @@ __global__ __launch_bounds__(kFastThreads) void decode_fast_kernel(const DecodeA
             const int tx = cw ? static_cast<int>(cw[P.bit_pos[i]]) : 0;
             err += est != tx;
         }
-        err = wave_sum_fast(err);
+        err = wave_sum(err);
         if (lane == 0 && err)
             atomicAdd(&misc[0], err);
         __syncthreads();

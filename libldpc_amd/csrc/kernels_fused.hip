@@ -30,6 +30,7 @@
 #include "device_philox.hpp"
 #include "fused_rule.h"
 #include "kernels.hpp"
+#include "launch_lds.hpp"
 
 #ifndef LDPC_AMD_DECODE_PRIO
 #define LDPC_AMD_DECODE_PRIO 3
@@ -46,11 +47,6 @@ namespace
 
 constexpr int kThreads = kDecodeWaves * kWaveSize;
 
-__device__ __forceinline__ uint32_t hi_word(double x) { return static_cast<uint32_t>(dm_bits(x) >> 32); }
-__device__ __forceinline__ double with_sign(double mag, uint32_t sign_hi) // mag > 0, sign_hi = 0 or 0x80000000
-{
-    return dm_from_bits(dm_bits(mag) | (static_cast<uint64_t>(sign_hi) << 32));
-}
 __device__ __forceinline__ double *at(char *msg, uint32_t byte_off) { return reinterpret_cast<double *>(msg + byte_off); }
 
 // running extremes of the upper words of the v2c messages (detmath.h, dm_box_escaped) and of the inverted products
@@ -243,14 +239,6 @@ __device__ __forceinline__ double vn_table(char *msg, const uint32_t *tbl, int l
         *m = with_sign(o, sg);
     }
     return prod;
-}
-
-__device__ __forceinline__ int wave_sum(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-        v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // ---- the frame's channel values, one stage entry {lambda, rho} per transmitted bit (AWGN / BSC) or per column (given LLRs) ----
@@ -1421,11 +1409,7 @@ int launch_decode_fused(const DecodeArgs &a, const DevFusedPlan &f, Stage stage,
                       : fused_kernel_of<false, kFusedVnSlots, kFusedLeafCalls>(stage, counter, a.ms_correct, exclusive);
     if (!k)
         return hipErrorInvalidValue;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(f.lds_bytes));
-    if (e != hipSuccess)
-        return e;
-    hipLaunchKernelGGL(k, dim3(static_cast<unsigned>(a.n_frames)), dim3(kThreads), f.lds_bytes, static_cast<hipStream_t>(stream), a, f);
-    return hipGetLastError();
+    return launch_with_lds(k, dim3(static_cast<unsigned>(a.n_frames)), dim3(kThreads), f.lds_bytes, stream, a, f);
 }
 
 } // namespace ldpc_amd

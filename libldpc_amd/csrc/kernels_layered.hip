@@ -25,6 +25,7 @@
 #include "device_channel.hpp"
 #include "device_math.hpp"
 #include "kernels.hpp"
+#include "launch_lds.hpp"
 
 namespace ldpc_amd
 {
@@ -269,12 +270,8 @@ int launch_decode_layered(const DecodeArgs &a, const DevLayerPlan &L, bool half_
     void (*k)(const DecodeArgs, const DevLayerPlan) =
         half_messages ? (a.llr_out ? decode_layered_kernel<_Float16, true> : decode_layered_kernel<_Float16, false>)
                       : (a.llr_out ? decode_layered_kernel<float, true> : decode_layered_kernel<float, false>);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-    if (e != hipSuccess)
-        return e;
     const unsigned blocks = static_cast<unsigned>((a.n_frames + kLayWaves - 1) / kLayWaves);
-    hipLaunchKernelGGL(k, dim3(blocks), dim3(kLayThreads), lds, static_cast<hipStream_t>(stream), a, L);
-    return hipGetLastError();
+    return launch_with_lds(k, dim3(blocks), dim3(kLayThreads), lds, stream, a, L);
 }
 
 } // namespace ldpc_amd

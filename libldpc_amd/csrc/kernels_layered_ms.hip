@@ -27,6 +27,7 @@
 #include "device_cn.hpp"
 #include "device_math.hpp"
 #include "kernels.hpp"
+#include "launch_lds.hpp"
 
 namespace ldpc_amd
 {
@@ -232,15 +233,10 @@ int launch_decode_layered_ms(const DecodeArgs &a, const DevLayerPlan &L, void *s
 {
     if (a.n_frames == 0)
         return hipSuccess;
-    if (!L.steps || !L.rec_off || L.region_bytes_ms == 0 || L.region_bytes_ms > 160 * 1024 || a.n_frames > 0x7FFFFFFFull)
+    if (!L.steps || !L.rec_off || L.region_bytes_ms == 0 || L.region_bytes_ms > kCuLdsBytes || a.n_frames > 0x7FFFFFFFull)
         return hipErrorInvalidValue;
     void (*k)(const DecodeArgs, const DevLayerPlan) = a.llr_out ? decode_layered_ms_kernel<true> : decode_layered_ms_kernel<false>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       static_cast<int>(L.region_bytes_ms));
-    if (e != hipSuccess)
-        return e;
-    hipLaunchKernelGGL(k, dim3(static_cast<unsigned>(a.n_frames)), dim3(kLmsThreads), L.region_bytes_ms, static_cast<hipStream_t>(stream), a, L);
-    return hipGetLastError();
+    return launch_with_lds(k, dim3(static_cast<unsigned>(a.n_frames)), dim3(kLmsThreads), L.region_bytes_ms, stream, a, L);
 }
 
 } // namespace ldpc_amd

@@ -24,6 +24,7 @@
 
 #include "device_channel.hpp"
 #include "kernels.hpp"
+#include "launch_lds.hpp"
 
 namespace ldpc_amd
 {
@@ -239,15 +240,10 @@ int launch_decode_qms(const DecodeArgs &a, const DevQmsPlan &Q, const QmsArgs &q
     const uint64_t nc = static_cast<uint64_t>(a.plan.nc);
     if (!Q.cn_desc || !Q.cn_vn || !Q.vn_start || !Q.vn_slot || (Q.slots & 3u) || q.qmax < 1 || q.qmax > 127 || a.plan.nc <= 0 ||
         nc > 0xFFFF || Q.work_bytes < 8 * nc || Q.work_bytes < Q.slots + 4 * nc + 144 || Q.region_bytes < Q.work_bytes + nc ||
-        Q.region_bytes > 160 * 1024 || a.n_frames > 0x7FFFFFFFull)
+        Q.region_bytes > kCuLdsBytes || a.n_frames > 0x7FFFFFFFull)
         return hipErrorInvalidValue;
     void (*k)(const DecodeArgs, const DevQmsPlan, const QmsArgs) = a.llr_out ? decode_qms_kernel<true> : decode_qms_kernel<false>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       static_cast<int>(Q.region_bytes));
-    if (e != hipSuccess)
-        return e;
-    hipLaunchKernelGGL(k, dim3(static_cast<unsigned>(a.n_frames)), dim3(kQmsThreads), Q.region_bytes, static_cast<hipStream_t>(stream), a, Q, q);
-    return hipGetLastError();
+    return launch_with_lds(k, dim3(static_cast<unsigned>(a.n_frames)), dim3(kQmsThreads), Q.region_bytes, stream, a, Q, q);
 }
 
 } // namespace ldpc_amd

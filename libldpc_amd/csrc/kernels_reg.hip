@@ -22,6 +22,7 @@
 #include "device_cn.hpp"
 #include "device_math.hpp"
 #include "kernels.hpp"
+#include "launch_lds.hpp"
 
 namespace ldpc_amd
 {
@@ -81,14 +82,6 @@ __device__ __forceinline__ void cn_regs(double (&m)[MAXD], int degree, uint32_t 
 #undef LDPC_CASE
 }
 
-__device__ __forceinline__ int wave_sum_i(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-        v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // RATIO: the likelihood-ratio form of the sum-product iteration, exactly as in kernels.hip (v2c = rho, c2v = lambda,
 // input LLRs kept as lambda; frames that leave the representable box go to a.redo_list).
 template <bool MINSUM, bool WANT_LLR, int NT, int KC, int MAXD, bool RATIO, bool SH6 = false>
@@ -140,12 +133,7 @@ int launch_reg(const DecodeArgs &a, const DevRegPlan &r, Stage stage, bool min_s
     if (!k)
         return hipErrorInvalidValue;
     const uint32_t lds = r.mb_doubles * 9u;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       static_cast<int>(lds));
-    if (e != hipSuccess)
-        return e;
-    hipLaunchKernelGGL(k, dim3(static_cast<unsigned>(a.n_frames)), dim3(NT), lds, static_cast<hipStream_t>(stream), a, r);
-    return hipGetLastError();
+    return launch_with_lds(k, dim3(static_cast<unsigned>(a.n_frames)), dim3(NT), lds, stream, a, r);
 }
 
 } // namespace

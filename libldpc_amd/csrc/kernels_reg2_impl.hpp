@@ -33,7 +33,7 @@
 #include "device_cn.hpp"
 #include "device_math.hpp"
 #include "kernels.hpp"
-
+#include "launch_lds.hpp"
 
 namespace ldpc_amd
 {
@@ -84,14 +84,6 @@ __device__ __forceinline__ void cn_regs2(double (&m)[MAXD], int degree, uint32_t
         break;
     }
 #undef LDPC_CASE
-}
-
-__device__ __forceinline__ int wave_sum_i2(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-        v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // LDS access by absolute byte address: the packed edge words hold addresses relative to the start of the workgroup's
@@ -575,7 +567,7 @@ __device__ __forceinline__ bool reg2_frame(const DecodeArgs &a, const DevReg2Pla
             int tx = cw ? static_cast<int>(cw[P.bit_pos[i]]) : 0;
             err += est != tx;
         }
-        err = wave_sum_i2(err);
+        err = wave_sum(err);
         if (lane == 0 && err)
             atomicAdd(&vote[2], static_cast<uint32_t>(err));
         __syncthreads();
@@ -673,12 +665,7 @@ int launch_reg2(const DecodeArgs &a, const DevReg2Plan &r, Stage stage, bool min
     if (!k)
         return hipErrorInvalidValue;
     const uint32_t lds = r.lds_entries * 8u + 16u;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       static_cast<int>(lds));
-    if (e != hipSuccess)
-        return e;
-    hipLaunchKernelGGL(k, dim3(static_cast<unsigned>(a.n_frames)), dim3(NT), lds, static_cast<hipStream_t>(stream), a, r);
-    return hipGetLastError();
+    return launch_with_lds(k, dim3(static_cast<unsigned>(a.n_frames)), dim3(NT), lds, stream, a, r);
 }
 
 } // namespace

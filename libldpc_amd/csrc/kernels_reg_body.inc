@@ -244,7 +244,7 @@
             int tx = cw ? static_cast<int>(cw[P.bit_pos[i]]) : 0;
             err += est != tx;
         }
-        err = wave_sum_i(err);
+        err = wave_sum(err);
         if (lane == 0 && err)
             atomicAdd(&misc[0], err);
         __syncthreads();

@@ -3,6 +3,8 @@
 // instead of against the same header compiled for the host.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 #include "device_cn.hpp"
 #include "device_math.hpp"
 #include "kernels.hpp"
@@ -84,6 +86,38 @@ __global__ __launch_bounds__(256) void math_selftest_kernel(int fn, uint64_t n, 
     }
 }
 
+// operands a = 2^ea * ma, b = 2^eb * mb with ea, eb in [-500, 500] and random mantissas: a, b, a/b inside 2^-+1001
+__global__ __launch_bounds__(256) void division_selftest_kernel(uint64_t n, uint64_t seed, unsigned long long *mismatches)
+{
+    unsigned long long bad = 0;
+    for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += gridDim.x * 256ull)
+    {
+        uint64_t x = (i + 1) * 0x9E3779B97F4A7C15ull ^ seed;
+        auto next = [&] {
+            x ^= x >> 12, x ^= x << 25, x ^= x >> 27;
+            return x * 0x2545F4914F6CDD1Dull;
+        };
+        auto operand = [&] {
+            const uint64_t m = next() >> 12, e = 1023 - 500 + (next() >> 33) % 1001;
+            return dm_from_bits((e << 52) | m);
+        };
+        const double a = operand(), b = operand();
+        volatile double bv = b; // keep the compiler from folding the two forms together
+        bad += dm_bits(dm_ratio_div(a, b)) != dm_bits(a / bv);
+        // dm_div_by (detmath.h): numerators of either sign up to 2^8 over divisors in [2^-7, 2^7] with THEIR correctly rounded
+        // reciprocal (here: the device's own IEEE division, which is correctly rounded) — the channel's 2 y / sigma^2
+        const uint64_t m2 = next() >> 12, e2 = 1023 - 7 + (next() >> 33) % 15;
+        const double d = dm_from_bits((e2 << 52) | m2);
+        volatile double dv = d;
+        const double rcp = 1.0 / dv;
+        const uint64_t m3 = next() >> 12, e3 = 1023 - 60 + (next() >> 33) % 69, s3 = next() >> 63;
+        const double num = dm_from_bits((s3 << 63) | (e3 << 52) | m3);
+        bad += dm_bits(dm_div_by(num, d, rcp)) != dm_bits(num / dv);
+    }
+    if (bad)
+        atomicAdd(mismatches, bad);
+}
+
 } // namespace
 
 int math_selftest_width(int fn)
@@ -105,6 +139,16 @@ int launch_math_selftest(int fn, uint64_t n, const double *a, const double *b, d
         return hipSuccess;
     const unsigned blocks = static_cast<unsigned>((n + 255) / 256);
     hipLaunchKernelGGL(math_selftest_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), fn, n, a, b, out);
+    return hipGetLastError();
+}
+
+int launch_division_selftest(uint64_t n, uint64_t seed, unsigned long long *mismatches, void *stream)
+{
+    if (n == 0)
+        return hipSuccess;
+    const unsigned blocks = static_cast<unsigned>(std::min<uint64_t>((n + 255) / 256, 8192));
+    hipLaunchKernelGGL(division_selftest_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), n, seed,
+                       mismatches);
     return hipGetLastError();
 }
 
