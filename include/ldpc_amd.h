@@ -251,6 +251,47 @@ int ldpc_hip_min_sum_quantization(const ldpc_hip_ctx *ctx, int *bits, double *st
    bytes of the workgroup's vote; behind them the nc quantized channel values. */
 int64_t ldpc_hip_quantized_min_sum_lds_bytes(const ldpc_hip_ctx *ctx);
 
+/* Ternary min-sum (Gallager's Algorithm E): "BP_MS" decoding with messages in {-1, 0, +1} and the channel weight w, the
+   hard-decision message passing of a BSC or of a hard-decision front end.  NON-PARITY (the reference's min-sum is binary64,
+   decoder.cpp:22-76), off by default and never chosen by the library itself.
+   weight 0 = off (the default), 1..7 = on with channel weight w.  The setter is host-only and takes effect at the next
+   decode call.  It returns -1 with ldpc_hip_last_error naming it and the setting unchanged for a weight outside 0..7, for a
+   code it does not take, and while LDPC_HIP_MS_SCHEDULE_LAYERED or quantization is in force; ldpc_hip_set_min_sum_schedule(
+   LAYERED) and ldpc_hip_set_min_sum_quantization(bits > 0) in turn return -1 while it is on: of the three, at most one.
+   Where it applies: whenever a call's decoder_param.type is "BP_MS" in ldpc_hip_decode_batch,
+   ldpc_hip_stream_decode(_sharded) and ldpc_hip_simulate(_sharded).  Sum-product, the BEC decoder and Part 1 never see it.
+   It combines with both noise modes (ldpc_hip_set_noise).  While it is on ldpc_hip_set_min_sum_correction has no effect (there
+   is no magnitude to correct), ldpc_hip_decode_stages reports one `whole` launch for "BP_MS" (unchanged stages for "BP") and
+   ldpc_hip_decoder_choice returns 6.
+   Which codes it takes: at most 65 535 columns (and edges), any check-node degree >= 2, column degree <= 56 (so |A| <= 63);
+   isolated, punctured and shortened columns are fine; the LDS of one 32-frame group (below) within 160 KB.  There is no
+   byte-per-message fallback: a code beyond that is refused.  A code whose every check node sees two or more punctured
+   columns (tests/golden/h.txt) is taken and decodes nothing: every message stays zero.
+   Arithmetic, all integer, so every output bit is determined:
+     1. r[v] = +1 where the frame's decoder input llr[v] > 0, -1 where it is < 0, 0 for +-0 and NaN: punctured columns 0,
+        shortened columns +1, +-infinity +-1.  The llr_in output stays the binary64 value.
+     2. v2c[e] = r[col(e)].
+     3. Check node c, edge j: c2v_j = the product of v2c_k over k != j (0 if any other input is 0).
+     4. Variable node v: A[v] = w r[v] + the sum of its c2v; v2c_e = sgn(A[v] - c2v_e); hard[v] = 1 iff 2 A[v] + r[v] <= 0:
+        a tie A = 0 goes to the received bit (the decoder stays symmetric, all-zero-codeword simulation stays valid), and to 1,
+        the library's convention, where there is none.
+     5. Schedule and stop: flooding, the syndrome early stop and the iteration count of the reference, exactly as for
+        "BP_MS" (decoder.cpp:22-77): iters = the iterations completed before the one whose decisions passed the syndrome
+        check, otherwise iters = iterations.  iterations == 0: hard and llr_out all zero.
+     6. llr_out[v] = (double) A[v] of the last iteration the frame ran.  bit_errors and codeword are as everywhere.
+     7. A frame's results do not depend on which other frames share its group or batch: 32 consecutive frames of a batch are
+        decoded by one workgroup, bit f of every word being frame f, and a frame that stops is frozen while its group goes on. */
+int ldpc_hip_set_min_sum_ternary(ldpc_hip_ctx *ctx, int weight);
+/* the weight in force (0 = off) */
+int ldpc_hip_min_sum_ternary(const ldpc_hip_ctx *ctx);
+/* LDS bytes one 32-frame group of ternary min-sum takes on this context's code (host only), -1 for a code the setter
+   refuses.  In 4-byte words: 64 (the group's votes and error counts) + 2 max(nnz, nc) (the messages' Z and S words, over which
+   the channel prologue first stages one frame's nc binary64 LLRs) + 3 nc (r = +1, r = -1, the decisions) + P nc (the planes
+   of A in two's complement, P = 1 + the bits of (largest column degree + 7): kept for llr_out, left out of a launch that
+   does not want it); then 4 nnz bytes (two u16 per edge: the variable nodes' slot table and slot -> column for the syndrome),
+   all rounded up to 16. */
+int64_t ldpc_hip_ternary_lds_bytes(const ldpc_hip_ctx *ctx);
+
 /* decode n frames of given LLRs llr_in[n][nc] (column order, device or host). 0 on success. */
 int ldpc_hip_decode_batch(ldpc_hip_ctx *ctx, decoder_param dec, uint64_t n, const double *llr_in,
                           const ldpc_hip_out *out, void *hip_stream);
@@ -348,12 +389,12 @@ int ldpc_hip_comm_allgather(ldpc_hip_comm *comm, const void *send, void *recv, u
    instantiation applies, check-node calls per wave + 1, the code has shortened bits, entries of the slot table} */
 void ldpc_hip_fused_plan_info(const ldpc_hip_ctx *ctx, int64_t info[8]);
 /* the launches a batch decoded with `dec` takes on this context, in order (host only; honours ldpc_hip_set_fast_mode,
-   ldpc_hip_set_min_sum_schedule and ldpc_hip_set_min_sum_quantization): stages[i] = 0 whole, 1 ratio-first, 2 ratio-separate, 3 list-chain,
+   ldpc_hip_set_min_sum_schedule, ldpc_hip_set_min_sum_quantization and ldpc_hip_set_min_sum_ternary): stages[i] = 0 whole, 1 ratio-first, 2 ratio-separate, 3 list-chain,
    4 llr-redo, 5 handover-first, 6 handover-resume; returns their number, 1 to 3 */
 int ldpc_hip_decode_stages(const ldpc_hip_ctx *ctx, decoder_param dec, int32_t stages[3]);
 /* the decoder that runs such a batch (host only; the same switches): 0 resident (the library's own choice by the code),
    1 fast32, 2 layered32, 3 layered16 (ldpc_hip_set_fast_mode 1 / 2 / 3, sum-product only), 4 layered min-sum, 5 quantized
-   min-sum ("BP_MS" only).  Anything but 0 is one `whole` launch. */
+   min-sum, 6 ternary min-sum ("BP_MS" only).  Anything but 0 is one `whole` launch. */
 int ldpc_hip_decoder_choice(const ldpc_hip_ctx *ctx, decoder_param dec);
 /* Host arithmetic only. The simulation loop's counters over given per-frame results. Frames [0, n) are presented as
    consecutive ranges; ends[k] is the end of range k (ascending, <= n; ranges may be empty); `world` consecutive ranges form

@@ -73,6 +73,12 @@ def load_library(path=LIB_PATH):
     L.ldpc_hip_min_sum_quantization.argtypes = [vp, ct.POINTER(i32), ct.POINTER(ct.c_double)]
     L.ldpc_hip_quantized_min_sum_lds_bytes.restype = ct.c_int64
     L.ldpc_hip_quantized_min_sum_lds_bytes.argtypes = [vp]
+    L.ldpc_hip_set_min_sum_ternary.restype = i32
+    L.ldpc_hip_set_min_sum_ternary.argtypes = [vp, i32]
+    L.ldpc_hip_min_sum_ternary.restype = i32
+    L.ldpc_hip_min_sum_ternary.argtypes = [vp]
+    L.ldpc_hip_ternary_lds_bytes.restype = ct.c_int64
+    L.ldpc_hip_ternary_lds_bytes.argtypes = [vp]
     L.ldpc_hip_philox.restype = i32
     L.ldpc_hip_philox.argtypes = [vp, u64, ct.c_uint32, u64, ct.c_uint32, u64, vp, vp]
     L.ldpc_hip_decode_batch.restype = i32
@@ -292,7 +298,7 @@ class HipDecoder:
         n = self.lib.ldpc_hip_decode_stages(self.ctx, _dec(early_term, iterations, decoding), stages)
         return [self.STAGES[stages[i]] for i in range(n)]
 
-    DECODERS = ("resident", "fast32", "layered32", "layered16", "layered-min-sum", "quantized-min-sum")
+    DECODERS = ("resident", "fast32", "layered32", "layered16", "layered-min-sum", "quantized-min-sum", "ternary")
 
     def decoder_choice(self, early_term=True, iterations=50, decoding="BP"):
         """The decoder that runs a batch with these parameters under the switches in force (include/ldpc_amd.h,
@@ -356,6 +362,23 @@ class HipDecoder:
     def quantized_min_sum_lds_bytes(self):
         """LDS bytes one frame of quantized min-sum takes (-1: the kernel does not take the code)."""
         return int(self.lib.ldpc_hip_quantized_min_sum_lds_bytes(self.ctx))
+
+    def set_min_sum_ternary(self, weight=0):
+        """Ternary min-sum (Gallager's Algorithm E, messages in {-1, 0, +1}) for every "BP_MS" decode from the next call on,
+        with channel weight `weight` (1..7; 0 = off, the default).  NON-PARITY; include/ldpc_amd.h, ldpc_hip_set_min_sum_ternary.
+        Combines with both noise modes, not with the layered schedule or quantization; set_min_sum_correction has no effect
+        while it is on.  Raises, leaving the setting as it is, for invalid values or a code the kernel does not take.
+        Touches no GPU."""
+        self._check(self.lib.ldpc_hip_set_min_sum_ternary(self.ctx, int(weight)), f"ldpc_hip_set_min_sum_ternary({weight!r})")
+
+    @property
+    def min_sum_ternary(self):
+        """The channel weight of ternary min-sum in force; 0 = off."""
+        return int(self.lib.ldpc_hip_min_sum_ternary(self.ctx))
+
+    def ternary_lds_bytes(self):
+        """LDS bytes one 32-frame group of ternary min-sum takes (-1: the kernel does not take the code)."""
+        return int(self.lib.ldpc_hip_ternary_lds_bytes(self.ctx))
 
     def philox(self, seed, tag, frame, first_block, n_blocks):
         """The counter mode's raw words, [n_blocks][4] uint32: blocks first_block.. of `frame` under `tag` (0 AWGN, 1 BSC /

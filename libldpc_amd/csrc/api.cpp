@@ -337,6 +337,20 @@ int64_t ldpc_hip_quantized_min_sum_lds_bytes(const ldpc_hip_ctx *ctx)
     return bytes;
 }
 
+int ldpc_hip_set_min_sum_ternary(ldpc_hip_ctx *ctx, int weight)
+{
+    return guarded([&] { ctx->eng->set_ms_ternary(weight); });
+}
+
+int ldpc_hip_min_sum_ternary(const ldpc_hip_ctx *ctx) { return ctx->eng->ms_ternary(); }
+
+int64_t ldpc_hip_ternary_lds_bytes(const ldpc_hip_ctx *ctx)
+{
+    int64_t bytes = -1; // (-1 for every code the setter refuses)
+    guarded([&] { bytes = ctx->eng->refusal(Decoder::kTernary).empty() ? ctx->eng->ternary_group_lds_bytes() : -1; });
+    return bytes;
+}
+
 int ldpc_hip_philox(ldpc_hip_ctx *ctx, uint64_t seed, uint32_t tag, uint64_t frame, uint32_t first_block, uint64_t n_blocks,
                     uint32_t *out, void *hip_stream)
 {

@@ -751,6 +751,17 @@ int64_t Engine::qms_lds_bytes()
     return qms_plan().ok ? static_cast<int64_t>(qms_region_bytes(qms_plan().slots, static_cast<size_t>(plan_.nc))) : -1;
 }
 
+// ternary min-sum: the general plan is all it needs.  A u16 holds a slot and a rank, a wave's work list the lanes of a register
+// (blocks / 8 <= 64), seven planes a column's total (degree + 7 <= 63), the message words the error count's (kernels_ternary.hip)
+int64_t Engine::ternary_group_lds_bytes() const
+{
+    const Plan &p = plan_;
+    if (p.nc > 0xFFFF || p.nnz <= 0 || p.nnz > 0xFFFF || p.max_vn_degree > kTernaryMaxVnDegree || p.cn_blocks.size() > 512 ||
+        p.vn_blocks.size() > 512 || static_cast<size_t>(p.n_bitpos) > ternary_message_words(p.nnz, p.nc))
+        return -1;
+    return static_cast<int64_t>(ternary_lds_bytes(p.nnz, p.nc, ternary_planes(p.max_vn_degree), true));
+}
+
 // What each opt-in variant takes, once (engine.hpp).  The texts are what callers see: the two sum-product modes whole, at
 // the first decode; the min-sum ones behind their setter's name, at set time
 std::string Engine::refusal(Decoder d)
@@ -785,6 +796,17 @@ std::string Engine::refusal(Decoder d)
                    std::to_string(bytes) + " bytes of LDS, more than " + std::to_string(kCuLdsBytes);
         break;
     }
+    case Decoder::kTernary:
+    {
+        const int64_t bytes = ternary_group_lds_bytes();
+        if (bytes < 0)
+            return "ternary min-sum takes codes of at most 65535 columns and 65535 edges with column degrees up to " +
+                   std::to_string(kTernaryMaxVnDegree) + " (and at most 512 blocks of 64 equal-degree nodes on either side)";
+        if (bytes > static_cast<int64_t>(kCuLdsBytes))
+            return "a group's messages, decisions and totals (32 frames) take " + std::to_string(bytes) + " bytes of LDS, more than " +
+                   std::to_string(kCuLdsBytes);
+        break;
+    }
     }
     return "";
 }
@@ -799,6 +821,9 @@ void Engine::set_ms_schedule(int schedule)
         if (ms_bits_)
             throw std::runtime_error(who + "the layered schedule does not combine with quantized min-sum "
                                            "(ldpc_hip_set_min_sum_quantization(ctx, 0, 0) first)");
+        if (ms_ternary_)
+            throw std::runtime_error(who + "the layered schedule does not combine with ternary min-sum "
+                                           "(ldpc_hip_set_min_sum_ternary(ctx, 0) first)");
         if (const std::string why = refusal(Decoder::kLayeredMinSum); !why.empty())
             throw std::runtime_error(who + why);
     }
@@ -820,9 +845,33 @@ void Engine::set_ms_quantization(int bits, double step)
     if (ms_schedule_ == 1)
         throw std::runtime_error(who + "quantized min-sum does not combine with the layered schedule "
                                        "(ldpc_hip_set_min_sum_schedule(ctx, LDPC_HIP_MS_SCHEDULE_FLOODING) first)");
+    if (ms_ternary_)
+        throw std::runtime_error(who + "quantized min-sum does not combine with ternary min-sum "
+                                       "(ldpc_hip_set_min_sum_ternary(ctx, 0) first)");
     if (const std::string why = refusal(Decoder::kQuantizedMinSum); !why.empty())
         throw std::runtime_error(who + why);
     ms_bits_ = bits, ms_step_ = step;
+}
+
+void Engine::set_ms_ternary(int weight)
+{
+    const std::string who = "ldpc_hip_set_min_sum_ternary: ";
+    if (weight == 0)
+    {
+        ms_ternary_ = 0;
+        return;
+    }
+    if (weight < 0 || weight > 7)
+        throw std::runtime_error(who + "need weight 0 (off) or 1..7, got " + std::to_string(weight));
+    if (ms_schedule_ == 1)
+        throw std::runtime_error(who + "ternary min-sum does not combine with the layered schedule "
+                                       "(ldpc_hip_set_min_sum_schedule(ctx, LDPC_HIP_MS_SCHEDULE_FLOODING) first)");
+    if (ms_bits_)
+        throw std::runtime_error(who + "ternary min-sum does not combine with quantized min-sum "
+                                       "(ldpc_hip_set_min_sum_quantization(ctx, 0, 0) first)");
+    if (const std::string why = refusal(Decoder::kTernary); !why.empty())
+        throw std::runtime_error(who + why);
+    ms_ternary_ = weight;
 }
 
 // The tables of the layered schedule, as kernels_layered.hip and kernels_layered_ms.hip read them (a code refusal() passed)
@@ -952,6 +1001,9 @@ void Engine::run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, 
         case Decoder::kQuantizedMinSum:
             upload_qms_plan();
             check(launch_decode_qms(a, dev_qms_, qms_args(), s), "decode (quantized min-sum)");
+            return;
+        case Decoder::kTernary:
+            check(launch_decode_ternary(a, TernaryArgs{ms_ternary_, ternary_planes(plan_.max_vn_degree)}, s), "decode (ternary min-sum)");
             return;
         case Decoder::kFast32:
             a.ws_hb = static_cast<uint8_t *>(ws_hb_.reserve(n * nc));

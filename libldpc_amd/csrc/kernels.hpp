@@ -285,6 +285,16 @@ struct QmsArgs
 };
 int launch_decode_qms(const DecodeArgs &a, const DevQmsPlan &Q, const QmsArgs &q, void *stream);
 
+// opt-in non-parity ternary min-sum, bit-sliced over 32 frames per workgroup (kernels_ternary.hip; include/ldpc_amd.h,
+// ldpc_hip_set_min_sum_ternary) on the general plan.  a.ms_* are not read.  With a.llr_out null the planes of A are left out
+// of the group's LDS (plan.hpp, ternary_lds_bytes)
+struct TernaryArgs
+{
+    int32_t weight; // w of A = w r + the sum of the inputs, 1..7
+    int32_t planes; // plan.hpp, ternary_planes(max_vn_degree)
+};
+int launch_decode_ternary(const DecodeArgs &a, const TernaryArgs &t, void *stream);
+
 // ---- mt19937_64 on the device ----
 constexpr int kMtN = 312;
 constexpr uint32_t kBlockTrials = kMtN / 2; // one twist block of 312 words = 156 polar trials

@@ -12,7 +12,8 @@
 // counter-based noise, include/ldpc_amd.h ldpc_hip_set_noise); --ms-scale A / --ms-offset B with --decoding BP_MS
 // (NON-PARITY normalized / offset min-sum, include/ldpc_amd.h ldpc_hip_set_min_sum_correction); --ms-schedule layered with
 // --decoding BP_MS (NON-PARITY layered schedule, include/ldpc_amd.h ldpc_hip_set_min_sum_schedule); --ms-bits Q --ms-step D
-// with --decoding BP_MS (NON-PARITY quantized min-sum, include/ldpc_amd.h ldpc_hip_set_min_sum_quantization); --bec-compat (reproduce
+// with --decoding BP_MS (NON-PARITY quantized min-sum, include/ldpc_amd.h ldpc_hip_set_min_sum_quantization); --ms-ternary W
+// with --decoding BP_MS (NON-PARITY ternary min-sum, include/ldpc_amd.h ldpc_hip_set_min_sum_ternary); --bec-compat (reproduce
 // the reference's out-of-bounds read for erased degree-1 variable nodes).
 #include <fcntl.h>
 #include <signal.h>
@@ -68,7 +69,9 @@ const char *kUsage =
     "                    \tcheck nodes; NON-PARITY: the reference's schedule is flooding).\n"
     "--ms-bits           \tBP_MS only: quantized min-sum with messages of Q bits, 2 <= Q <= 8, on a saturating integer\n"
     "                    \tdatapath (NON-PARITY; not with --ms-schedule layered).\n"
-    "--ms-step           \tBP_MS only, with --ms-bits: the LLR step D of the quantizer, 2^-20 <= D <= 2^20 (Default: 1).\n";
+    "--ms-step           \tBP_MS only, with --ms-bits: the LLR step D of the quantizer, 2^-20 <= D <= 2^20 (Default: 1).\n"
+    "--ms-ternary        \tBP_MS only: ternary min-sum (Gallager E, messages -1, 0, +1) with channel weight W, 1 <= W <= 7\n"
+    "                    \t(NON-PARITY; not with --ms-bits, --ms-schedule layered, --ms-scale or --ms-offset).\n";
 
 std::vector<int> parse_devices(const std::string &spec)
 {
@@ -117,6 +120,8 @@ int main(int argc, char *argv[])
     std::string ms_bits_arg, ms_step_arg; // quantized min-sum: the values as given (empty: not given)
     int ms_bits = 0;
     double ms_step = 1.0;
+    std::string ms_ternary_arg; // ternary min-sum: the weight as given (empty: not given)
+    int ms_ternary = 0;
     try
     {
         for (int i = 1; i < argc; ++i)
@@ -170,6 +175,8 @@ int main(int argc, char *argv[])
                 ms_bits = std::stoi(ms_bits_arg = value());
             else if (a == "--ms-step")
                 ms_step = std::stod(ms_step_arg = value());
+            else if (a == "--ms-ternary")
+                ms_ternary = std::stoi(ms_ternary_arg = value());
             else if (a.size() > 1 && a[0] == '-' && !(std::isdigit(static_cast<unsigned char>(a[1])) || a[1] == '.'))
                 throw std::runtime_error("Unknown argument: " + a);
             else
@@ -211,6 +218,20 @@ int main(int argc, char *argv[])
                 throw std::runtime_error("--ms-step: need 2^-20 <= D <= 2^20");
             if (ms_schedule == "layered")
                 throw std::runtime_error("--ms-bits: quantized min-sum does not combine with --ms-schedule layered");
+        }
+        if (!ms_ternary_arg.empty())
+        {
+            if (decoding != "BP_MS")
+                throw std::runtime_error("--ms-ternary: ternary min-sum, for --decoding BP_MS only");
+            // (include/ldpc_amd.h, ldpc_hip_set_min_sum_ternary)
+            if (ms_ternary < 1 || ms_ternary > 7)
+                throw std::runtime_error("--ms-ternary: need 1 <= W <= 7");
+            if (!ms_bits_arg.empty())
+                throw std::runtime_error("--ms-ternary: ternary min-sum does not combine with --ms-bits");
+            if (ms_schedule == "layered")
+                throw std::runtime_error("--ms-ternary: ternary min-sum does not combine with --ms-schedule layered");
+            if (!ms_scale_arg.empty() || !ms_offset_arg.empty())
+                throw std::runtime_error("--ms-ternary: ternary min-sum has no magnitude to correct (--ms-scale / --ms-offset)");
         }
     }
     catch (const std::exception &e)
@@ -368,6 +389,12 @@ int main(int argc, char *argv[])
         ldpc_hip_destroy(ctx);
         return reap(EXIT_FAILURE);
     }
+    if (ms_ternary && ldpc_hip_set_min_sum_ternary(ctx, ms_ternary) != 0)
+    {
+        std::cout << "Error: " << ldpc_hip_last_error() << std::endl;
+        ldpc_hip_destroy(ctx);
+        return reap(EXIT_FAILURE);
+    }
     int64_t info[10];
     ldpc_hip_code_info(ctx, info);
 
@@ -388,6 +415,8 @@ int main(int argc, char *argv[])
     if (ms_bits)
         std::cout << " Min-Sum Quantization: " << ms_bits << " bits, step " << (ms_step_arg.empty() ? "1" : ms_step_arg)
                   << " (saturating fixed-point messages), NON-PARITY\n";
+    if (ms_ternary)
+        std::cout << " Min-Sum Ternary: weight " << ms_ternary << " (Gallager E: messages -1, 0, +1), NON-PARITY\n";
     std::cout << "== Channel Parameters\n";
     std::cout << " Type: " << channel << "\n Seed: " << seed << "\n Range: Min: " << range[0] << ", Max: " << range[1]
               << ", Step: " << range[2] << "\n";

@@ -228,6 +228,30 @@ QmsPlan build_qms_plan(const LdpcCode &code, const Plan &plan);
 inline size_t qms_work_bytes(size_t slots, size_t nc) { return (std::max(8 * nc, slots + 4 * nc + 144) + 3) & ~size_t(3); }
 inline size_t qms_region_bytes(size_t slots, size_t nc) { return (qms_work_bytes(slots, nc) + nc + 15) & ~size_t(15); }
 
+// ---- ternary min-sum, bit-sliced (kernels_ternary.hip; include/ldpc_amd.h, ldpc_hip_set_min_sum_ternary) ----------------
+// One workgroup = 32 frames, bit f of every word = frame f, on the general plan's blocks and slot table.
+constexpr int kTernaryFrames = 32;
+constexpr int kTernaryMaxVnDegree = 56; // |A| <= 56 + 7 = 63: seven planes
+constexpr size_t kTernaryHeadWords = 64; // the group's votes and error counts
+// planes of A = w r + the sum of a column's inputs in two's complement, for any weight 1..7: |A| <= max_vn_degree + 7
+constexpr int ternary_planes(int max_vn_degree)
+{
+    int bits = 1;
+    for (int x = max_vn_degree + 7; x; x >>= 1)
+        ++bits;
+    return bits;
+}
+// the message words Z[nnz] S[nnz]; at least 8 nc bytes, which the channel prologue stages one frame's binary64 LLRs in
+constexpr size_t ternary_message_words(size_t nnz, size_t nc) { return 2 * std::max(nnz, nc); }
+// The LDS of one 32-frame group: the head, the messages, three words per column (r = +1, r = -1, the decision), the
+// `planes` words per column of A where llr_out is wanted (`totals`), and two u16 per edge (the variable nodes' slot table
+// and the table slot -> variable-node rank the syndrome goes through)
+constexpr size_t ternary_lds_bytes(size_t nnz, size_t nc, int planes, bool totals)
+{
+    const size_t words = kTernaryHeadWords + ternary_message_words(nnz, nc) + 3 * nc + (totals ? static_cast<size_t>(planes) * nc : 0);
+    return (4 * words + 4 * nnz + 15) & ~size_t(15);
+}
+
 // ---- fused form of the likelihood-ratio iteration (kernels_fused.hip; detmath.h "Fused form", fused_rule.h) ----------
 // First launch of sum-product with early termination for codes the rule takes (check nodes of degree 2..4 with at most one
 // leaf each).  One workgroup (4 waves) per frame as in the LDS-resident decoder, but only edges that do NOT end in a leaf
