@@ -16,7 +16,10 @@ int launch_with_lds(void (*kernel)(Params...), dim3 grid, dim3 block, uint32_t l
     const hipError_t e =
         hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes));
     if (e != hipSuccess)
+    {
+        (void)hipGetLastError(); // (reported here: the next launch's check must not find it again)
         return e;
+    }
     hipLaunchKernelGGL(kernel, grid, block, lds_bytes, static_cast<hipStream_t>(stream), args...);
     return hipGetLastError();
 }

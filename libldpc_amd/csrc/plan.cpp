@@ -204,8 +204,8 @@ RegPlan build_reg_plan(const LdpcCode &code, const Plan &plan, int nt, int kc, i
     const int n_cb = static_cast<int>(plan.cn_blocks.size());
     if (code.min_cn_degree() < 2 || plan.max_cn_degree > maxd || n_cb > kc * kRegWaves || plan.nnz >= (1 << 28))
         return r;
-    // mailbox: as many (double + hard-bit byte) entries as one CU's LDS holds
-    const uint32_t cap = ((lds_budget - 256) / 9) & ~63u;
+    // mailbox: as many (double + hard-bit byte) entries as one CU's LDS holds beside the kernels' static LDS (kRegStaticLds)
+    const uint32_t cap = ((lds_budget - kRegStaticLds) / 9) & ~63u;
     // VN blocks (those of the LDS plan: sorted by degree, <= 64 equal-degree VNs) dealt to rounds in order
     std::vector<uint32_t> block_round(plan.vn_blocks.size()), block_off(plan.vn_blocks.size());
     uint32_t fill = 0, round = 0, peak = 0;

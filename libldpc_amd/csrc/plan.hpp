@@ -206,6 +206,11 @@ inline size_t layered_ms_records(const LayerPlan &L, std::vector<uint32_t> *rec_
 // ... and the LDS of one frame: the binary64 totals and the records
 inline size_t layered_ms_region_bytes(const LayerPlan &L, size_t nc) { return (8 * nc + layered_ms_records(L) + 15) & ~size_t(15); }
 constexpr size_t kCuLdsBytes = 160 * 1024; // the LDS of one CU: what a frame of any decoder has to fit
+// what build_reg_plan leaves of it to the static LDS of the messages-form register kernels (kernels_reg.hip: 272 bytes in the
+// compiler's resource report — 16 of misc[] and 256 the compiler adds; tests/test_generator_codes_host.py holds the report to
+// this figure).  It was 256: a code whose mailbox peak reached the last 64-entry step asked for 160 KiB + 16 bytes and every
+// launch failed with "invalid argument"
+constexpr uint32_t kRegStaticLds = 512;
 
 // ---- quantized (fixed-point) min-sum (kernels_qms.hip; include/ldpc_amd.h, ldpc_hip_set_min_sum_quantization) ----------
 // One byte per message.  Check nodes in CSR, in the order of Plan::cn_rank_row (by degree, so neighbouring threads loop
