@@ -177,7 +177,8 @@ int ldpc_hip_set_min_sum_correction(ldpc_hip_ctx *ctx, double scale, double offs
    LDS — 8 nc bytes of totals plus 20 bytes per check node (each step of the schedule rounded up to an even number of check
    nodes), ldpc_hip_layered_min_sum_lds_bytes — within 160 KB.  For any other code, and for an unknown `schedule` value, the
    setter returns -1 with ldpc_hip_last_error set and the setting unchanged.  The check is host-only; the setting takes
-   effect at the next decode call and touches no GPU.
+   effect at the next decode call and touches no GPU.  LAYERED is also refused while quantization, ternary min-sum or
+   ldpc_hip_set_min_sum_layered_fixed (the same schedule in fixed point, a setting of its own) is on.
    Arithmetic: everything is binary64, every operation is rounded once, there is no fused multiply-add.
      1. T[v] := the frame's decoder input (channel LLR; punctured 0, shortened shorten_llr).  Every message m[c][j] := +0.0.
      2. One sweep visits the steps of the layered plan (libldpc_amd/csrc/plan.cpp, build_layer_plan: check nodes in file order
@@ -214,7 +215,8 @@ int64_t ldpc_hip_layered_min_sum_lds_bytes(const ldpc_hip_ctx *ctx);
    bits 0 = off (the default; step ignored), 2..8 = on.  The setter is host-only and takes effect at the next decode call.
    It returns -1 with ldpc_hip_last_error set and the setting unchanged for bits outside {0, 2..8}, for a step that is NaN,
    infinite, <= 0 or outside [2^-20, 2^20], for a code it does not take, and while LDPC_HIP_MS_SCHEDULE_LAYERED is in force
-   (ldpc_hip_set_min_sum_schedule(LAYERED) in turn returns -1 while quantization is on).
+   (ldpc_hip_set_min_sum_schedule(LAYERED) in turn returns -1 while quantization is on), and while
+   ldpc_hip_set_min_sum_layered_fixed is on.
    Where it applies: whenever a call's decoder_param.type is "BP_MS" in ldpc_hip_decode_batch,
    ldpc_hip_stream_decode(_sharded) and ldpc_hip_simulate(_sharded).  Sum-product, the BEC decoder and Part 1 never see it.
    It combines with both noise modes (ldpc_hip_set_noise) and with ldpc_hip_set_min_sum_correction (through the table of
@@ -258,6 +260,7 @@ int64_t ldpc_hip_quantized_min_sum_lds_bytes(const ldpc_hip_ctx *ctx);
    decode call.  It returns -1 with ldpc_hip_last_error naming it and the setting unchanged for a weight outside 0..7, for a
    code it does not take, and while LDPC_HIP_MS_SCHEDULE_LAYERED or quantization is in force; ldpc_hip_set_min_sum_schedule(
    LAYERED) and ldpc_hip_set_min_sum_quantization(bits > 0) in turn return -1 while it is on: of the three, at most one.
+   (ldpc_hip_set_min_sum_layered_fixed is the fourth of the kind: each of the four returns -1 while another is in force.)
    Where it applies: whenever a call's decoder_param.type is "BP_MS" in ldpc_hip_decode_batch,
    ldpc_hip_stream_decode(_sharded) and ldpc_hip_simulate(_sharded).  Sum-product, the BEC decoder and Part 1 never see it.
    It combines with both noise modes (ldpc_hip_set_noise).  While it is on ldpc_hip_set_min_sum_correction has no effect (there
@@ -291,6 +294,57 @@ int ldpc_hip_min_sum_ternary(const ldpc_hip_ctx *ctx);
    does not want it); then 4 nnz bytes (two u16 per edge: the variable nodes' slot table and slot -> column for the syndrome),
    all rounded up to 16. */
 int64_t ldpc_hip_ternary_lds_bytes(const ldpc_hip_ctx *ctx);
+
+/* Fixed-point layered min-sum: "BP_MS" decoding on the layered (row-serial) schedule with messages of `msg_bits` bits, a
+   saturating a-posteriori total (APP) of `app_bits` bits per column and the LLR step `step` — the datapath of hardware
+   decoders (5G NR, 802.11, DVB-S2).  NON-PARITY (the reference's min-sum is flooding and binary64, decoder.cpp:22-76), off
+   by default and never chosen by the library itself.
+   msg_bits 0 = off (the default; the other arguments are then ignored), 2..8 = on; on needs msg_bits <= app_bits <= 16 and
+   2^-20 <= step <= 2^20 (a NaN fails).  The setter is host-only and takes effect at the next decode call.  It returns -1
+   with ldpc_hip_last_error naming ldpc_hip_set_min_sum_layered_fixed and the setting unchanged for invalid values, for a code
+   it does not take, and while LDPC_HIP_MS_SCHEDULE_LAYERED, quantization or ternary min-sum is in force;
+   ldpc_hip_set_min_sum_schedule(LAYERED), ldpc_hip_set_min_sum_quantization(bits > 0) and ldpc_hip_set_min_sum_ternary(weight
+   > 0) in turn return -1 while it is on: of the four, at most one is in force.
+   Where it applies: whenever a call's decoder_param.type is "BP_MS" in ldpc_hip_decode_batch,
+   ldpc_hip_stream_decode(_sharded) and ldpc_hip_simulate(_sharded).  Sum-product, the BEC decoder and Part 1 never see it.
+   It combines with both noise modes (ldpc_hip_set_noise) and with ldpc_hip_set_min_sum_correction (through the table of
+   item 3).  While it is on ldpc_hip_decode_stages reports one `whole` launch for "BP_MS" (unchanged stages for "BP") and
+   ldpc_hip_decoder_choice returns 7.
+   Which codes it takes: those of the layered schedule, on the same plan (libldpc_amd/csrc/plan.cpp, build_layer_plan, built
+   once per context): every check node of degree 2..8, at most 65 535 columns, no isolated variable node, and the frame's LDS
+   (below) within 160 KB.
+   Arithmetic, all integer after the quantizer, so every output bit is determined.  q = msg_bits, p = app_bits, D = step,
+   Qmax = 2^(q-1) - 1, Pmax = 2^(p-1) - 1 (both symmetric), inv = fl(1 / D), computed once on the host in binary64:
+     1. Channel.  L[v] = clamp(rint(fl(llr[v] * inv)), -Qmax, +Qmax), exactly item 1 of ldpc_hip_set_min_sum_quantization:
+        the clamp applied in binary64, a NaN gives 0, punctured columns give 0, shortened columns and infinities saturate at
+        +-Qmax.  The llr_in output stays the unquantized binary64 value.
+     2. Start.  T[v] := L[v].  Every message m[c][j] := 0.
+     3. Correction table.  lut[0..Qmax] is exactly item 3 of ldpc_hip_set_min_sum_quantization, built on the host with the
+        same routine from ldpc_hip_set_min_sum_correction(scale, offset).  The kernel sees the table only, never scale or
+        offset.  The table is non-decreasing.
+     4. One sweep visits the steps of the layered plan in order (ldpc_hip_set_min_sum_schedule, item 2).  For each check node
+        c of the step, with neighbours v_j:
+          t_j = T[v_j] - m[c][j]                  (an exact integer; |t_j| <= Pmax + Qmax)
+          u_j = clamp(t_j, -Qmax, +Qmax)          (the variable-to-check message at message width)
+          a_j = the smallest |u_k| over k != j
+          m[c][j] := +-lut[a_j], negative iff an odd number of the other u_k are < 0 (an integer zero is not negative)
+          T[v_j] := clamp(t_j + m[c][j], -Pmax, +Pmax)
+        The check nodes of a step share no variable node, so the result depends on the step order only.
+     5. After every sweep hard = (T <= 0).  With early termination a zero syndrome stops the frame; iters = sweeps completed
+        before the sweep whose syndrome passed.  Otherwise iters = iterations.  (As layered min-sum does it.)
+     6. llr_out[v] = fl((double) T[v] * D).  bit_errors, codeword and llr_in are as everywhere.
+     7. iterations == 0: hard and llr_out all zero. */
+int ldpc_hip_set_min_sum_layered_fixed(ldpc_hip_ctx *ctx, int msg_bits, int app_bits, double step);
+/* the setting in force: *msg_bits (0 = off), *app_bits and *step (the last ones set; 8 and 1.0 before any); any pointer may
+   be null */
+int ldpc_hip_min_sum_layered_fixed(const ldpc_hip_ctx *ctx, int *msg_bits, int *app_bits, double *step);
+/* LDS bytes one frame of fixed-point layered min-sum takes on this context's code (host only; worked out once per
+   context), -1 for a code it does not take, or on an error (last_error set).  With R = the check-node slots of the layered
+   plan (each step's check nodes rounded up to an even number, summed):
+     bytes = max(8 nc, round4(2 nc) + 4 R) + 128, rounded up to 16
+   — the nc binary64 channel LLRs first; over them the int16 totals and, from the next multiple of 4, one 32-bit record per
+   slot; behind the larger of the two the 128-byte correction table.  tests/golden/h.txt: 9 344 bytes, 17 frames per CU. */
+int64_t ldpc_hip_layered_fixed_lds_bytes(const ldpc_hip_ctx *ctx);
 
 /* decode n frames of given LLRs llr_in[n][nc] (column order, device or host). 0 on success. */
 int ldpc_hip_decode_batch(ldpc_hip_ctx *ctx, decoder_param dec, uint64_t n, const double *llr_in,
@@ -389,12 +443,12 @@ int ldpc_hip_comm_allgather(ldpc_hip_comm *comm, const void *send, void *recv, u
    instantiation applies, check-node calls per wave + 1, the code has shortened bits, entries of the slot table} */
 void ldpc_hip_fused_plan_info(const ldpc_hip_ctx *ctx, int64_t info[8]);
 /* the launches a batch decoded with `dec` takes on this context, in order (host only; honours ldpc_hip_set_fast_mode,
-   ldpc_hip_set_min_sum_schedule, ldpc_hip_set_min_sum_quantization and ldpc_hip_set_min_sum_ternary): stages[i] = 0 whole, 1 ratio-first, 2 ratio-separate, 3 list-chain,
+   ldpc_hip_set_min_sum_schedule, ldpc_hip_set_min_sum_quantization, ldpc_hip_set_min_sum_ternary and ldpc_hip_set_min_sum_layered_fixed): stages[i] = 0 whole, 1 ratio-first, 2 ratio-separate, 3 list-chain,
    4 llr-redo, 5 handover-first, 6 handover-resume; returns their number, 1 to 3 */
 int ldpc_hip_decode_stages(const ldpc_hip_ctx *ctx, decoder_param dec, int32_t stages[3]);
 /* the decoder that runs such a batch (host only; the same switches): 0 resident (the library's own choice by the code),
    1 fast32, 2 layered32, 3 layered16 (ldpc_hip_set_fast_mode 1 / 2 / 3, sum-product only), 4 layered min-sum, 5 quantized
-   min-sum, 6 ternary min-sum ("BP_MS" only).  Anything but 0 is one `whole` launch. */
+   min-sum, 6 ternary min-sum, 7 fixed-point layered min-sum ("BP_MS" only).  Anything but 0 is one `whole` launch. */
 int ldpc_hip_decoder_choice(const ldpc_hip_ctx *ctx, decoder_param dec);
 /* Host arithmetic only. The simulation loop's counters over given per-frame results. Frames [0, n) are presented as
    consecutive ranges; ends[k] is the end of range k (ascending, <= n; ranges may be empty); `world` consecutive ranges form

@@ -79,6 +79,12 @@ def load_library(path=LIB_PATH):
     L.ldpc_hip_min_sum_ternary.argtypes = [vp]
     L.ldpc_hip_ternary_lds_bytes.restype = ct.c_int64
     L.ldpc_hip_ternary_lds_bytes.argtypes = [vp]
+    L.ldpc_hip_set_min_sum_layered_fixed.restype = i32
+    L.ldpc_hip_set_min_sum_layered_fixed.argtypes = [vp, i32, i32, ct.c_double]
+    L.ldpc_hip_min_sum_layered_fixed.restype = i32
+    L.ldpc_hip_min_sum_layered_fixed.argtypes = [vp, ct.POINTER(i32), ct.POINTER(i32), ct.POINTER(ct.c_double)]
+    L.ldpc_hip_layered_fixed_lds_bytes.restype = ct.c_int64
+    L.ldpc_hip_layered_fixed_lds_bytes.argtypes = [vp]
     L.ldpc_hip_philox.restype = i32
     L.ldpc_hip_philox.argtypes = [vp, u64, ct.c_uint32, u64, ct.c_uint32, u64, vp, vp]
     L.ldpc_hip_decode_batch.restype = i32
@@ -298,7 +304,8 @@ class HipDecoder:
         n = self.lib.ldpc_hip_decode_stages(self.ctx, _dec(early_term, iterations, decoding), stages)
         return [self.STAGES[stages[i]] for i in range(n)]
 
-    DECODERS = ("resident", "fast32", "layered32", "layered16", "layered-min-sum", "quantized-min-sum", "ternary")
+    DECODERS = ("resident", "fast32", "layered32", "layered16", "layered-min-sum", "quantized-min-sum", "ternary",
+                "layered-fixed-min-sum")
 
     def decoder_choice(self, early_term=True, iterations=50, decoding="BP"):
         """The decoder that runs a batch with these parameters under the switches in force (include/ldpc_amd.h,
@@ -379,6 +386,26 @@ class HipDecoder:
     def ternary_lds_bytes(self):
         """LDS bytes one 32-frame group of ternary min-sum takes (-1: the kernel does not take the code)."""
         return int(self.lib.ldpc_hip_ternary_lds_bytes(self.ctx))
+
+    def set_min_sum_layered_fixed(self, msg_bits=0, app_bits=8, step=1.0):
+        """Fixed-point layered min-sum for every "BP_MS" decode from the next call on: the layered schedule with messages of
+        `msg_bits` bits (2..8; 0 = off, the default), saturating totals of `app_bits` bits (msg_bits..16) and LLR step `step`
+        (NON-PARITY; include/ldpc_amd.h, ldpc_hip_set_min_sum_layered_fixed).  Combines with set_min_sum_correction and both
+        noise modes, not with the layered schedule, quantization or ternary min-sum; raises, leaving the setting as it is, for
+        invalid values or a code the kernel does not take.  Touches no GPU."""
+        self._check(self.lib.ldpc_hip_set_min_sum_layered_fixed(self.ctx, int(msg_bits), int(app_bits), float(step)),
+                    f"ldpc_hip_set_min_sum_layered_fixed({msg_bits!r}, {app_bits!r}, {step!r})")
+
+    @property
+    def min_sum_layered_fixed(self):
+        """(msg_bits, app_bits, step) of fixed-point layered min-sum in force; msg_bits 0 = off."""
+        q, p, step = ct.c_int32(0), ct.c_int32(0), ct.c_double(0.0)
+        self.lib.ldpc_hip_min_sum_layered_fixed(self.ctx, ct.byref(q), ct.byref(p), ct.byref(step))
+        return int(q.value), int(p.value), float(step.value)
+
+    def layered_fixed_lds_bytes(self):
+        """LDS bytes one frame of fixed-point layered min-sum takes (-1: the kernel does not take the code)."""
+        return int(self.lib.ldpc_hip_layered_fixed_lds_bytes(self.ctx))
 
     def philox(self, seed, tag, frame, first_block, n_blocks):
         """The counter mode's raw words, [n_blocks][4] uint32: blocks first_block.. of `frame` under `tag` (0 AWGN, 1 BSC /

@@ -351,6 +351,29 @@ int64_t ldpc_hip_ternary_lds_bytes(const ldpc_hip_ctx *ctx)
     return bytes;
 }
 
+int ldpc_hip_set_min_sum_layered_fixed(ldpc_hip_ctx *ctx, int msg_bits, int app_bits, double step)
+{
+    return guarded([&] { ctx->eng->set_ms_layered_fixed(msg_bits, app_bits, step); });
+}
+
+int ldpc_hip_min_sum_layered_fixed(const ldpc_hip_ctx *ctx, int *msg_bits, int *app_bits, double *step)
+{
+    if (msg_bits)
+        *msg_bits = ctx->eng->ms_lf_msg_bits();
+    if (app_bits)
+        *app_bits = ctx->eng->ms_lf_app_bits();
+    if (step)
+        *step = ctx->eng->ms_lf_step();
+    return 0;
+}
+
+int64_t ldpc_hip_layered_fixed_lds_bytes(const ldpc_hip_ctx *ctx)
+{
+    int64_t bytes = -1; // (the plan builder allocates; -1 for every code the setter refuses)
+    guarded([&] { bytes = ctx->eng->refusal(Decoder::kLayeredFixedMinSum).empty() ? ctx->eng->layered_fixed_lds_bytes() : -1; });
+    return bytes;
+}
+
 int ldpc_hip_philox(ldpc_hip_ctx *ctx, uint64_t seed, uint32_t tag, uint64_t frame, uint32_t first_block, uint64_t n_blocks,
                     uint32_t *out, void *hip_stream)
 {

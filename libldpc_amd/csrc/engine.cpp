@@ -746,6 +746,14 @@ int64_t Engine::layered_ms_lds_bytes()
     return !L.ok || plan_.has_isolated_vn ? -1 : static_cast<int64_t>(layered_ms_region_bytes(L, static_cast<size_t>(plan_.nc)));
 }
 
+int64_t Engine::layered_fixed_lds_bytes()
+{
+    const LayerPlan &L = layer_plan();
+    return !L.ok || plan_.has_isolated_vn || plan_.nc > 0xFFFF
+               ? -1
+               : static_cast<int64_t>(layered_fixed_region_bytes(layered_ms_records(L) / 20, static_cast<size_t>(plan_.nc)));
+}
+
 int64_t Engine::qms_lds_bytes()
 {
     return qms_plan().ok ? static_cast<int64_t>(qms_region_bytes(qms_plan().slots, static_cast<size_t>(plan_.nc))) : -1;
@@ -796,6 +804,17 @@ std::string Engine::refusal(Decoder d)
                    std::to_string(bytes) + " bytes of LDS, more than " + std::to_string(kCuLdsBytes);
         break;
     }
+    case Decoder::kLayeredFixedMinSum:
+    {
+        const int64_t bytes = layered_fixed_lds_bytes();
+        if (bytes < 0)
+            return "fixed-point layered min-sum takes codes whose check nodes all have degree 2..8, with at most 65535 columns and "
+                   "no isolated variable node";
+        if (bytes > static_cast<int64_t>(kCuLdsBytes))
+            return "a frame's channel values, totals and check-node records take " + std::to_string(bytes) + " bytes of LDS, more than " +
+                   std::to_string(kCuLdsBytes);
+        break;
+    }
     case Decoder::kTernary:
     {
         const int64_t bytes = ternary_group_lds_bytes();
@@ -824,6 +843,9 @@ void Engine::set_ms_schedule(int schedule)
         if (ms_ternary_)
             throw std::runtime_error(who + "the layered schedule does not combine with ternary min-sum "
                                            "(ldpc_hip_set_min_sum_ternary(ctx, 0) first)");
+        if (ms_lf_msg_bits_)
+            throw std::runtime_error(who + "the layered schedule does not combine with fixed-point layered min-sum "
+                                           "(ldpc_hip_set_min_sum_layered_fixed(ctx, 0, 0, 0) first)");
         if (const std::string why = refusal(Decoder::kLayeredMinSum); !why.empty())
             throw std::runtime_error(who + why);
     }
@@ -848,6 +870,9 @@ void Engine::set_ms_quantization(int bits, double step)
     if (ms_ternary_)
         throw std::runtime_error(who + "quantized min-sum does not combine with ternary min-sum "
                                        "(ldpc_hip_set_min_sum_ternary(ctx, 0) first)");
+    if (ms_lf_msg_bits_)
+        throw std::runtime_error(who + "quantized min-sum does not combine with fixed-point layered min-sum "
+                                       "(ldpc_hip_set_min_sum_layered_fixed(ctx, 0, 0, 0) first)");
     if (const std::string why = refusal(Decoder::kQuantizedMinSum); !why.empty())
         throw std::runtime_error(who + why);
     ms_bits_ = bits, ms_step_ = step;
@@ -869,9 +894,38 @@ void Engine::set_ms_ternary(int weight)
     if (ms_bits_)
         throw std::runtime_error(who + "ternary min-sum does not combine with quantized min-sum "
                                        "(ldpc_hip_set_min_sum_quantization(ctx, 0, 0) first)");
+    if (ms_lf_msg_bits_)
+        throw std::runtime_error(who + "ternary min-sum does not combine with fixed-point layered min-sum "
+                                       "(ldpc_hip_set_min_sum_layered_fixed(ctx, 0, 0, 0) first)");
     if (const std::string why = refusal(Decoder::kTernary); !why.empty())
         throw std::runtime_error(who + why);
     ms_ternary_ = weight;
+}
+
+void Engine::set_ms_layered_fixed(int msg_bits, int app_bits, double step)
+{
+    const std::string who = "ldpc_hip_set_min_sum_layered_fixed: ";
+    if (msg_bits == 0) // off: the other arguments are ignored
+    {
+        ms_lf_msg_bits_ = 0;
+        return;
+    }
+    // (the comparisons are false for NaN: a NaN fails them)
+    if (msg_bits < 2 || msg_bits > 8 || app_bits < msg_bits || app_bits > 16 || !(step >= 0x1p-20 && step <= 0x1p20))
+        throw std::runtime_error(who + "need msg_bits 0 (off) or 2..8, msg_bits <= app_bits <= 16 and 2^-20 <= step <= 2^20, got (" +
+                                 std::to_string(msg_bits) + ", " + std::to_string(app_bits) + ", " + std::to_string(step) + ")");
+    if (ms_schedule_ == 1)
+        throw std::runtime_error(who + "fixed-point layered min-sum does not combine with the (binary64) layered schedule "
+                                       "(ldpc_hip_set_min_sum_schedule(ctx, LDPC_HIP_MS_SCHEDULE_FLOODING) first)");
+    if (ms_bits_)
+        throw std::runtime_error(who + "fixed-point layered min-sum does not combine with quantized min-sum "
+                                       "(ldpc_hip_set_min_sum_quantization(ctx, 0, 0) first)");
+    if (ms_ternary_)
+        throw std::runtime_error(who + "fixed-point layered min-sum does not combine with ternary min-sum "
+                                       "(ldpc_hip_set_min_sum_ternary(ctx, 0) first)");
+    if (const std::string why = refusal(Decoder::kLayeredFixedMinSum); !why.empty())
+        throw std::runtime_error(who + why);
+    ms_lf_msg_bits_ = msg_bits, ms_lf_app_bits_ = app_bits, ms_lf_step_ = step;
 }
 
 // The tables of the layered schedule, as kernels_layered.hip and kernels_layered_ms.hip read them (a code refusal() passed)
@@ -920,21 +974,38 @@ void Engine::upload_qms_plan()
     dev_qms_.cn_desc = static_cast<const uint32_t *>(upload_table(q.cn_desc.data(), 4 * q.cn_desc.size(), what)); // last: the mark
 }
 
-// the quantizer and the correction table of one launch (include/ldpc_amd.h, ldpc_hip_set_min_sum_quantization, items 1 and
-// 3): binary64, every operation rounded once (-ffp-contract=off), rint = round-half-to-even
+// The correction table of the two fixed-point min-sum modes (include/ldpc_amd.h, ldpc_hip_set_min_sum_quantization, item 3):
+// lut[m], m = 0..qmax, four per word; binary64, every operation rounded once (-ffp-contract=off), rint = round-half-to-even
+static void correction_lut(double scale, double offset, double inv, int qmax, uint32_t (&lut)[32])
+{
+    const double off = offset * inv;
+    for (int m = 0; m <= qmax; ++m)
+    {
+        const double t = scale * static_cast<double>(m);
+        const double r = std::rint(t - off); // (scale <= 1 and off >= 0: never above m)
+        const uint32_t v = r > 0.0 ? static_cast<uint32_t>(r) : 0u;
+        lut[m >> 2] |= v << (8 * (m & 3));
+    }
+}
+
+// the quantizer (item 1: the step and fl(1 / step), computed here) and the correction table of one launch
 QmsArgs Engine::qms_args() const
 {
     QmsArgs q{};
     q.step = ms_step_, q.inv = 1.0 / ms_step_;
     q.qmax = (1 << (ms_bits_ - 1)) - 1;
-    const double off = ms_offset * q.inv;
-    for (int m = 0; m <= q.qmax; ++m)
-    {
-        const double t = ms_scale * static_cast<double>(m);
-        const double r = std::rint(t - off); // (scale <= 1 and off >= 0: never above m)
-        const uint32_t v = r > 0.0 ? static_cast<uint32_t>(r) : 0u;
-        q.lut[m >> 2] |= v << (8 * (m & 3));
-    }
+    correction_lut(ms_scale, ms_offset, q.inv, q.qmax, q.lut);
+    return q;
+}
+
+// ... and of fixed-point layered min-sum: the same quantizer and table (ldpc_hip_set_min_sum_layered_fixed, items 1 and 3)
+LayeredFixedArgs Engine::layered_fixed_args() const
+{
+    LayeredFixedArgs q{};
+    q.step = ms_lf_step_, q.inv = 1.0 / ms_lf_step_;
+    q.qmax = (1 << (ms_lf_msg_bits_ - 1)) - 1;
+    q.pmax = (1 << (ms_lf_app_bits_ - 1)) - 1;
+    correction_lut(ms_scale, ms_offset, q.inv, q.qmax, q.lut);
     return q;
 }
 
@@ -1001,6 +1072,10 @@ void Engine::run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, 
         case Decoder::kQuantizedMinSum:
             upload_qms_plan();
             check(launch_decode_qms(a, dev_qms_, qms_args(), s), "decode (quantized min-sum)");
+            return;
+        case Decoder::kLayeredFixedMinSum:
+            upload_layer_plan();
+            check(launch_decode_layered_fixed(a, dev_layer_, layered_fixed_args(), s), "decode (fixed-point layered min-sum)");
             return;
         case Decoder::kTernary:
             check(launch_decode_ternary(a, TernaryArgs{ms_ternary_, ternary_planes(plan_.max_vn_degree)}, s), "decode (ternary min-sum)");

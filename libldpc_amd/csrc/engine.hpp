@@ -80,15 +80,20 @@ struct StageSeq
 // Which kernel family decodes a batch: the resident decoders the library picks by the code (Residency), or one of the opt-in
 // NON-PARITY variants the caller switched on — flooding sum-product with binary32 messages (kernels_fast.hip), layered
 // sum-product with binary32 / binary16 messages (kernels_layered.hip), layered min-sum (kernels_layered_ms.hip), quantized
-// min-sum (kernels_qms.hip), ternary min-sum (kernels_ternary.hip).  One value per batch: Engine::stages names its launches from it, run_decode switches on it,
-// Engine::refusal says whether that decoder takes the code.
-enum class Decoder : int { kResident, kFast32, kLayered32, kLayered16, kLayeredMinSum, kQuantizedMinSum, kTernary };
-// min-sum follows its schedule, quantization and ternary weight (the setters let at most one of the three be in force) and
-// ignores the fast mode; sum-product follows the fast mode alone
-constexpr Decoder choose_decoder(bool min_sum, int fast_mode, int ms_schedule, int ms_bits, int ms_ternary)
+// min-sum (kernels_qms.hip), ternary min-sum (kernels_ternary.hip), fixed-point layered min-sum (kernels_layered_fixed.hip).
+// One value per batch: Engine::stages names its launches from it, run_decode switches on it, Engine::refusal says whether
+// that decoder takes the code.
+enum class Decoder : int { kResident, kFast32, kLayered32, kLayered16, kLayeredMinSum, kQuantizedMinSum, kTernary, kLayeredFixedMinSum };
+// min-sum follows its schedule, quantization, ternary weight and fixed-point layered width (the setters let at most one of
+// the four be in force) and ignores the fast mode; sum-product follows the fast mode alone
+constexpr Decoder choose_decoder(bool min_sum, int fast_mode, int ms_schedule, int ms_bits, int ms_ternary, int ms_layered_fixed)
 {
     if (min_sum)
-        return ms_schedule == 1 ? Decoder::kLayeredMinSum : ms_bits ? Decoder::kQuantizedMinSum : ms_ternary ? Decoder::kTernary : Decoder::kResident;
+        return ms_schedule == 1    ? Decoder::kLayeredMinSum
+               : ms_bits           ? Decoder::kQuantizedMinSum
+               : ms_ternary        ? Decoder::kTernary
+               : ms_layered_fixed  ? Decoder::kLayeredFixedMinSum
+                                   : Decoder::kResident;
     return fast_mode == 1 ? Decoder::kFast32 : fast_mode == 2 ? Decoder::kLayered32 : fast_mode == 3 ? Decoder::kLayered16 : Decoder::kResident;
 }
 
@@ -260,7 +265,7 @@ class Engine
     const FusedPlan &fused_plan() const { return fused_plan_; }
     Residency residency() const { return residency_; }
     // the decoder and the launches a batch with these parameters takes (host only)
-    Decoder decoder(const DecParams &p) const { return choose_decoder(p.min_sum, fast_mode, ms_schedule_, ms_bits_, ms_ternary_); }
+    Decoder decoder(const DecParams &p) const { return choose_decoder(p.min_sum, fast_mode, ms_schedule_, ms_bits_, ms_ternary_, ms_lf_msg_bits_); }
     StageSeq stages(const DecParams &p) const
     {
         return decode_stages({.residency = residency_, .decoder = decoder(p), .shared6 = shared6_,
@@ -283,11 +288,17 @@ class Engine
     double ms_scale = 1.0, ms_offset = 0.0;
     // schedule (0 flooding, 1 layered) and quantization (bits 0 = off, 2..8, with LLR step) of BP_MS decoding, NON-PARITY
     // (include/ldpc_amd.h, ldpc_hip_set_min_sum_schedule / _quantization), and the channel weight of ternary min-sum (0 = off,
-    // 1..7; ldpc_hip_set_min_sum_ternary).  The three exclude each other.  Host only; each setter throws, leaving the setting
-    // as it is, for invalid values, another of the three in force, or a code refusal() names
+    // 1..7; ldpc_hip_set_min_sum_ternary).  The three and set_ms_layered_fixed exclude each other.  Host only; each setter
+    // throws, leaving the setting as it is, for invalid values, another of the four in force, or a code refusal() names
     void set_ms_schedule(int schedule);
     void set_ms_quantization(int bits, double step);
     void set_ms_ternary(int weight);
+    // fixed-point layered min-sum (include/ldpc_amd.h, ldpc_hip_set_min_sum_layered_fixed): msg_bits 0 = off, 2..8 with
+    // msg_bits <= app_bits <= 16 and the LLR step; the fourth of the kind, under the same rules as the three above
+    void set_ms_layered_fixed(int msg_bits, int app_bits, double step);
+    int ms_lf_msg_bits() const { return ms_lf_msg_bits_; }
+    int ms_lf_app_bits() const { return ms_lf_app_bits_; }
+    double ms_lf_step() const { return ms_lf_step_; }
     int ms_ternary() const { return ms_ternary_; }
     int ms_schedule() const { return ms_schedule_; }
     int ms_bits() const { return ms_bits_; }
@@ -296,6 +307,7 @@ class Engine
     // take the code (a frame beyond the LDS of a CU still gets its byte count: refusal() judges it)
     int64_t layered_ms_lds_bytes();
     int64_t qms_lds_bytes();
+    int64_t layered_fixed_lds_bytes(); // (plan.hpp, layered_fixed_region_bytes)
     // host only: LDS bytes of one 32-frame group of ternary min-sum with llr_out wanted (plan.hpp, ternary_lds_bytes), -1 for a
     // code outside what the kernel's tables hold (refusal() says which limit)
     int64_t ternary_group_lds_bytes() const;
@@ -367,6 +379,7 @@ class Engine
     void upload_layer_plan();
     void upload_qms_plan();
     QmsArgs qms_args() const; // the quantizer and the correction table of the settings in force
+    LayeredFixedArgs layered_fixed_args() const; // ... and those of fixed-point layered min-sum
     bool register_resident() const { return residency_ == Residency::kRegTotals || residency_ == Residency::kRegMessages; }
     void run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, uint64_t n, void *stream);
     // BSC / BEC: the batch reads the noise stream's raw draws from word `raw_first` on
@@ -426,6 +439,8 @@ class Engine
     DevFusedPlan dev_fused_{};
     int ms_schedule_ = 0, ms_bits_ = 0, ms_ternary_ = 0;
     double ms_step_ = 1.0;
+    int ms_lf_msg_bits_ = 0, ms_lf_app_bits_ = 8;
+    double ms_lf_step_ = 1.0;
     std::optional<LayerPlan> layer_plan_;
     int layer_plan_builds_ = 0;
     DevLayerPlan dev_layer_{}; // (rec_off == nullptr: not uploaded yet)

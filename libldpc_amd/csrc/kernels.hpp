@@ -284,6 +284,18 @@ struct QmsArgs
     uint32_t lut[32];
 };
 int launch_decode_qms(const DecodeArgs &a, const DevQmsPlan &Q, const QmsArgs &q, void *stream);
+// opt-in non-parity fixed-point layered min-sum (kernels_layered_fixed.hip; include/ldpc_amd.h,
+// ldpc_hip_set_min_sum_layered_fixed) on the layered plan's tables (steps, vn4, rec_off / 20 = a step's first record slot).
+// The quantizer, the two saturation limits and the correction table of one launch: as for QmsArgs the kernel never sees the
+// correction's scale and offset, only lut[m] for m = 0..qmax, four per word
+struct LayeredFixedArgs
+{
+    double step, inv; // the LLR step and fl(1 / step)
+    int32_t qmax;     // 2^(msg_bits - 1) - 1, 1..127
+    int32_t pmax;     // 2^(app_bits - 1) - 1, qmax..32767
+    uint32_t lut[32];
+};
+int launch_decode_layered_fixed(const DecodeArgs &a, const DevLayerPlan &L, const LayeredFixedArgs &q, void *stream);
 
 // opt-in non-parity ternary min-sum, bit-sliced over 32 frames per workgroup (kernels_ternary.hip; include/ldpc_amd.h,
 // ldpc_hip_set_min_sum_ternary) on the general plan.  a.ms_* are not read.  With a.llr_out null the planes of A are left out

@@ -13,8 +13,9 @@
 // (NON-PARITY normalized / offset min-sum, include/ldpc_amd.h ldpc_hip_set_min_sum_correction); --ms-schedule layered with
 // --decoding BP_MS (NON-PARITY layered schedule, include/ldpc_amd.h ldpc_hip_set_min_sum_schedule); --ms-bits Q --ms-step D
 // with --decoding BP_MS (NON-PARITY quantized min-sum, include/ldpc_amd.h ldpc_hip_set_min_sum_quantization); --ms-ternary W
-// with --decoding BP_MS (NON-PARITY ternary min-sum, include/ldpc_amd.h ldpc_hip_set_min_sum_ternary); --bec-compat (reproduce
-// the reference's out-of-bounds read for erased degree-1 variable nodes).
+// with --decoding BP_MS (NON-PARITY ternary min-sum, include/ldpc_amd.h ldpc_hip_set_min_sum_ternary); --ms-layered-fixed Q,P,D
+// with --decoding BP_MS (NON-PARITY fixed-point layered min-sum, include/ldpc_amd.h ldpc_hip_set_min_sum_layered_fixed);
+// --bec-compat (reproduce the reference's out-of-bounds read for erased degree-1 variable nodes).
 #include <fcntl.h>
 #include <signal.h>
 #include <sys/prctl.h>
@@ -71,7 +72,10 @@ const char *kUsage =
     "                    \tdatapath (NON-PARITY; not with --ms-schedule layered).\n"
     "--ms-step           \tBP_MS only, with --ms-bits: the LLR step D of the quantizer, 2^-20 <= D <= 2^20 (Default: 1).\n"
     "--ms-ternary        \tBP_MS only: ternary min-sum (Gallager E, messages -1, 0, +1) with channel weight W, 1 <= W <= 7\n"
-    "                    \t(NON-PARITY; not with --ms-bits, --ms-schedule layered, --ms-scale or --ms-offset).\n";
+    "                    \t(NON-PARITY; not with --ms-bits, --ms-schedule layered, --ms-scale or --ms-offset).\n"
+    "--ms-layered-fixed  \tBP_MS only: fixed-point layered min-sum Q,P,D (e.g. 6,8,0.25): messages of Q bits, 2 <= Q <= 8,\n"
+    "                    \tsaturating totals of P bits, Q <= P <= 16, LLR step D, 2^-20 <= D <= 2^20 (NON-PARITY; not with\n"
+    "                    \t--ms-bits, --ms-schedule layered or --ms-ternary).\n";
 
 std::vector<int> parse_devices(const std::string &spec)
 {
@@ -122,6 +126,9 @@ int main(int argc, char *argv[])
     double ms_step = 1.0;
     std::string ms_ternary_arg; // ternary min-sum: the weight as given (empty: not given)
     int ms_ternary = 0;
+    std::string ms_lf_arg, ms_lf_step_arg; // fixed-point layered min-sum: Q,P,D as given (empty: not given) and its D
+    int ms_lf_q = 0, ms_lf_p = 0;
+    double ms_lf_step = 1.0;
     try
     {
         for (int i = 1; i < argc; ++i)
@@ -177,6 +184,8 @@ int main(int argc, char *argv[])
                 ms_step = std::stod(ms_step_arg = value());
             else if (a == "--ms-ternary")
                 ms_ternary = std::stoi(ms_ternary_arg = value());
+            else if (a == "--ms-layered-fixed")
+                ms_lf_arg = value();
             else if (a.size() > 1 && a[0] == '-' && !(std::isdigit(static_cast<unsigned char>(a[1])) || a[1] == '.'))
                 throw std::runtime_error("Unknown argument: " + a);
             else
@@ -232,6 +241,37 @@ int main(int argc, char *argv[])
                 throw std::runtime_error("--ms-ternary: ternary min-sum does not combine with --ms-schedule layered");
             if (!ms_scale_arg.empty() || !ms_offset_arg.empty())
                 throw std::runtime_error("--ms-ternary: ternary min-sum has no magnitude to correct (--ms-scale / --ms-offset)");
+        }
+        if (!ms_lf_arg.empty())
+        {
+            if (decoding != "BP_MS")
+                throw std::runtime_error("--ms-layered-fixed: fixed-point layered min-sum, for --decoding BP_MS only");
+            const size_t c1 = ms_lf_arg.find(','), c2 = c1 == std::string::npos ? c1 : ms_lf_arg.find(',', c1 + 1);
+            if (c2 == std::string::npos || ms_lf_arg.find(',', c2 + 1) != std::string::npos)
+                throw std::runtime_error("--ms-layered-fixed: expected Q,P,D such as 6,8,0.25");
+            try
+            {
+                ms_lf_q = std::stoi(ms_lf_arg.substr(0, c1));
+                ms_lf_p = std::stoi(ms_lf_arg.substr(c1 + 1, c2 - c1 - 1));
+                ms_lf_step = std::stod(ms_lf_step_arg = ms_lf_arg.substr(c2 + 1));
+            }
+            catch (const std::exception &)
+            {
+                throw std::runtime_error("--ms-layered-fixed: expected Q,P,D such as 6,8,0.25");
+            }
+            // (include/ldpc_amd.h, ldpc_hip_set_min_sum_layered_fixed; the comparisons are false for NaN)
+            if (ms_lf_q < 2 || ms_lf_q > 8)
+                throw std::runtime_error("--ms-layered-fixed: need 2 <= Q <= 8");
+            if (ms_lf_p < ms_lf_q || ms_lf_p > 16)
+                throw std::runtime_error("--ms-layered-fixed: need Q <= P <= 16");
+            if (!(ms_lf_step >= 0x1p-20 && ms_lf_step <= 0x1p20))
+                throw std::runtime_error("--ms-layered-fixed: need 2^-20 <= D <= 2^20");
+            if (!ms_bits_arg.empty())
+                throw std::runtime_error("--ms-layered-fixed: fixed-point layered min-sum does not combine with --ms-bits");
+            if (ms_schedule == "layered")
+                throw std::runtime_error("--ms-layered-fixed: fixed-point layered min-sum does not combine with --ms-schedule layered");
+            if (!ms_ternary_arg.empty())
+                throw std::runtime_error("--ms-layered-fixed: fixed-point layered min-sum does not combine with --ms-ternary");
         }
     }
     catch (const std::exception &e)
@@ -395,6 +435,12 @@ int main(int argc, char *argv[])
         ldpc_hip_destroy(ctx);
         return reap(EXIT_FAILURE);
     }
+    if (ms_lf_q && ldpc_hip_set_min_sum_layered_fixed(ctx, ms_lf_q, ms_lf_p, ms_lf_step) != 0)
+    {
+        std::cout << "Error: " << ldpc_hip_last_error() << std::endl;
+        ldpc_hip_destroy(ctx);
+        return reap(EXIT_FAILURE);
+    }
     int64_t info[10];
     ldpc_hip_code_info(ctx, info);
 
@@ -417,6 +463,9 @@ int main(int argc, char *argv[])
                   << " (saturating fixed-point messages), NON-PARITY\n";
     if (ms_ternary)
         std::cout << " Min-Sum Ternary: weight " << ms_ternary << " (Gallager E: messages -1, 0, +1), NON-PARITY\n";
+    if (ms_lf_q)
+        std::cout << " Min-Sum Layered Fixed-Point: " << ms_lf_q << "-bit messages, " << ms_lf_p << "-bit totals, step " << ms_lf_step_arg
+                  << ", NON-PARITY\n";
     std::cout << "== Channel Parameters\n";
     std::cout << " Type: " << channel << "\n Seed: " << seed << "\n Range: Min: " << range[0] << ", Max: " << range[1]
               << ", Step: " << range[2] << "\n";

@@ -205,6 +205,17 @@ inline size_t layered_ms_records(const LayerPlan &L, std::vector<uint32_t> *rec_
 }
 // ... and the LDS of one frame: the binary64 totals and the records
 inline size_t layered_ms_region_bytes(const LayerPlan &L, size_t nc) { return (8 * nc + layered_ms_records(L) + 15) & ~size_t(15); }
+// Fixed-point layered min-sum (kernels_layered_fixed.hip; include/ldpc_amd.h, ldpc_hip_set_min_sum_layered_fixed) keeps the
+// totals as int16 and ONE 32-bit record per check-node slot (`slots` = layered_ms_records / 20: each step's check nodes
+// rounded up to an even number).  The channel first writes nc binary64 LLRs; the totals (2 nc bytes) and, from the next
+// multiple of 4, the records overlay them; the 128-byte correction table sits behind the larger of the two:
+//   bytes = max(8 nc, round4(2 nc) + 4 slots) + 128, rounded up to 16
+constexpr size_t layered_fixed_records_off(size_t nc) { return (2 * nc + 3) & ~size_t(3); }
+constexpr size_t layered_fixed_lut_off(size_t slots, size_t nc)
+{
+    return 8 * nc > layered_fixed_records_off(nc) + 4 * slots ? 8 * nc : layered_fixed_records_off(nc) + 4 * slots;
+}
+constexpr size_t layered_fixed_region_bytes(size_t slots, size_t nc) { return (layered_fixed_lut_off(slots, nc) + 128 + 15) & ~size_t(15); }
 constexpr size_t kCuLdsBytes = 160 * 1024; // the LDS of one CU: what a frame of any decoder has to fit
 // what build_reg_plan leaves of it to the static LDS of the messages-form register kernels (kernels_reg.hip: 272 bytes in the
 // compiler's resource report — 16 of misc[] and 256 the compiler adds; tests/test_generator_codes_host.py holds the report to
