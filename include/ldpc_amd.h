@@ -350,6 +350,48 @@ int64_t ldpc_hip_layered_fixed_lds_bytes(const ldpc_hip_ctx *ctx);
 int ldpc_hip_decode_batch(ldpc_hip_ctx *ctx, decoder_param dec, uint64_t n, const double *llr_in,
                           const ldpc_hip_out *out, void *hip_stream);
 
+/* ldpc_hip_decode_batch for LLRs of another element type, and decisions packed 32 to a word.  llr_in[n][nc] is in column
+   order, in device or host memory, its elements of llr_type; host input is staged to the device in its own type (inputs of up
+   to 1 MB through page-locked memory, as for ldpc_hip_decode_batch).
+   The call decodes the WIDENED array W[n][nc], binary64:
+     LDPC_HIP_LLR_F64  W = the value itself;
+     LDPC_HIP_LLR_F32, LDPC_HIP_LLR_F16 (IEEE binary16)  W = the value widened to binary64, which is exact: NaN stays NaN,
+                       infinities and signed zeros are kept, binary16 subnormals become exact doubles;
+     LDPC_HIP_LLR_I8   an element k stands for W = fl((double) k * D), D = the `step` of the fixed-point mode in force: what a
+                       demapper with q-bit outputs delivers.  Accepted only when dec.type is "BP_MS" and
+                       ldpc_hip_set_min_sum_quantization or ldpc_hip_set_min_sum_layered_fixed is on; otherwise (sum-product,
+                       plain, layered or ternary min-sum) the call returns -1 and ldpc_hip_last_error names
+                       ldpc_hip_decode_batch_typed.  Values beyond +-Qmax saturate in the quantizer like any other LLR.
+   An unknown llr_type returns -1 in the same way.  These checks run before anything touches the GPU; after them n == 0
+   returns 0.
+   Every output in *out equals, bit for bit, what ldpc_hip_decode_batch returns for W under the same settings — iters,
+   bit_errors, hard, llr_out, llr_in (which is W) and codeword, for every decoder, mode and combination that call takes — and
+   the typed call fails wherever that call fails.  LDPC_HIP_LLR_F64 is ldpc_hip_decode_batch itself.
+   hard_bits[n][ceil(nc / 32)] (device or host memory, NULL = not wanted; independent of out->hard, which may be NULL): bit
+   c & 31 of word c >> 5 of a frame's row is hard[c]; the unused high bits of a row's last word are 0; iterations == 0 gives
+   rows of zeros.
+   The call changes nothing about later calls: no setting, no state.
+   How it runs: fixed-point layered min-sum (ldpc_hip_decoder_choice returns 7) reads F32, F16 and I8 input itself and stages
+   no binary64 value in LDS (ldpc_hip_layered_fixed_direct_lds_bytes; I8 is clamp(k, -Qmax, +Qmax), which equals item 1 of
+   ldpc_hip_set_min_sum_layered_fixed applied to W for every int8 k and every valid step); every other decoder gets W from
+   one conversion launch in front of its own.  hard_bits comes from one small launch behind the decoder's. */
+enum
+{
+    LDPC_HIP_LLR_F64 = 0,
+    LDPC_HIP_LLR_F32 = 1,
+    LDPC_HIP_LLR_F16 = 2,
+    LDPC_HIP_LLR_I8 = 3
+};
+int ldpc_hip_decode_batch_typed(ldpc_hip_ctx *ctx, decoder_param dec, uint64_t n, const void *llr_in, int llr_type,
+                                const ldpc_hip_out *out, uint32_t *hard_bits, void *hip_stream);
+/* LDS bytes one frame of fixed-point layered min-sum takes when ldpc_hip_decode_batch_typed feeds it F32, F16 or I8 input
+   (host only; worked out once per context), -1 for a code the layered plan refuses, or on an error (last_error set).  With R
+   as for ldpc_hip_layered_fixed_lds_bytes:
+     bytes = round4(2 nc) + 4 R + 128, rounded up to 16
+   — the int16 totals, from the next multiple of 4 one 32-bit record per slot, behind them the 128-byte correction table; no
+   binary64 channel LLRs.  tests/golden/h.txt: 6 528 bytes, 25 frames per CU. */
+int64_t ldpc_hip_layered_fixed_direct_lds_bytes(const ldpc_hip_ctx *ctx);
+
 /* channel point x of stream mt19937_64(seed): set_channel_param semantics, frame position := 0 */
 int ldpc_hip_stream_begin(ldpc_hip_ctx *ctx, int channel, uint64_t seed, double x);
 /* advance the stream by n frames without decoding them */

@@ -89,6 +89,10 @@ def load_library(path=LIB_PATH):
     L.ldpc_hip_philox.argtypes = [vp, u64, ct.c_uint32, u64, ct.c_uint32, u64, vp, vp]
     L.ldpc_hip_decode_batch.restype = i32
     L.ldpc_hip_decode_batch.argtypes = [vp, decoder_param, u64, vp, ct.POINTER(ldpc_hip_out), vp]
+    L.ldpc_hip_decode_batch_typed.restype = i32
+    L.ldpc_hip_decode_batch_typed.argtypes = [vp, decoder_param, u64, vp, i32, ct.POINTER(ldpc_hip_out), vp, vp]
+    L.ldpc_hip_layered_fixed_direct_lds_bytes.restype = ct.c_int64
+    L.ldpc_hip_layered_fixed_direct_lds_bytes.argtypes = [vp]
     L.ldpc_hip_stream_begin.restype = i32
     L.ldpc_hip_stream_begin.argtypes = [vp, i32, u64, ct.c_double]
     L.ldpc_hip_stream_skip.restype = i32
@@ -407,6 +411,11 @@ class HipDecoder:
         """LDS bytes one frame of fixed-point layered min-sum takes (-1: the kernel does not take the code)."""
         return int(self.lib.ldpc_hip_layered_fixed_lds_bytes(self.ctx))
 
+    def layered_fixed_direct_lds_bytes(self):
+        """LDS bytes one frame of fixed-point layered min-sum takes on float32, float16 or int8 input of decode_batch_typed: no
+        binary64 LLRs are staged (-1: the layered plan does not take the code)."""
+        return int(self.lib.ldpc_hip_layered_fixed_direct_lds_bytes(self.ctx))
+
     def philox(self, seed, tag, frame, first_block, n_blocks):
         """The counter mode's raw words, [n_blocks][4] uint32: blocks first_block.. of `frame` under `tag` (0 AWGN, 1 BSC /
         BEC, 2 encoder info bits), from the device generator."""
@@ -422,6 +431,27 @@ class HipDecoder:
         s, bufs = self._outs(n, want, out)
         self._check(self.lib.ldpc_hip_decode_batch(self.ctx, _dec(early_term, iterations, decoding), n, _ptr(llr_in),
                                                    ct.byref(s), stream), "ldpc_hip_decode_batch")
+        return bufs
+
+    LLR_TYPES = {"float64": 0, "float32": 1, "float16": 2, "int8": 3}
+
+    def decode_batch_typed(self, llr_in, early_term=True, iterations=50, decoding="BP",
+                           want=("iters", "hard", "llr_out"), out=None, stream=None):
+        """decode_batch for llr_in[n][nc] of dtype float64, float32, float16 or int8 (a numpy array or a torch tensor, host or
+        device; anything else raises TypeError): the outputs are those of decode_batch on the widened values, an int8 k standing
+        for k * step of the fixed-point mode in force (include/ldpc_amd.h, ldpc_hip_decode_batch_typed).  "hard_bits" in `want`
+        (or a buffer in out["hard_bits"]) gives the decisions packed 32 to a word, uint32 [n][ceil(nc / 32)]."""
+        name = str(llr_in.dtype).replace("torch.", "")
+        if name not in self.LLR_TYPES:
+            raise TypeError(f"decode_batch_typed takes float64, float32, float16 or int8 LLRs, not {llr_in.dtype}")
+        n = int(llr_in.shape[0])
+        bufs = dict(out or {})
+        if "hard_bits" in want and "hard_bits" not in bufs:
+            bufs["hard_bits"] = np.zeros((n, (self.nc + 31) // 32), np.uint32)
+        s, bufs = self._outs(n, [k for k in want if k != "hard_bits"], bufs)
+        self._check(self.lib.ldpc_hip_decode_batch_typed(self.ctx, _dec(early_term, iterations, decoding), n, _ptr(llr_in),
+                                                         self.LLR_TYPES[name], ct.byref(s), _ptr(bufs.get("hard_bits")), stream),
+                    "ldpc_hip_decode_batch_typed")
         return bufs
 
     def stream_begin(self, channel, seed, x):

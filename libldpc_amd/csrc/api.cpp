@@ -414,6 +414,27 @@ int ldpc_hip_decode_batch(ldpc_hip_ctx *ctx, decoder_param dec, uint64_t n, cons
     return guarded([&] { ctx->eng->decode_llr(to_params(dec), n, llr_in, to_out(out), hip_stream); });
 }
 
+int ldpc_hip_decode_batch_typed(ldpc_hip_ctx *ctx, decoder_param dec, uint64_t n, const void *llr_in, int llr_type,
+                                const ldpc_hip_out *out, uint32_t *hard_bits, void *hip_stream)
+{
+    return guarded([&] {
+        // (the checks first, host only: a call that is refused has touched no GPU, and n == 0 returns after them)
+        const DecParams p = to_params(dec);
+        if (const std::string why = ctx->eng->typed_refusal(p, llr_type); !why.empty())
+            throw std::runtime_error(why);
+        if (n && !llr_in)
+            throw std::runtime_error("ldpc_hip_decode_batch_typed: null llr_in");
+        ctx->eng->decode_typed(p, n, llr_in, llr_type, to_out(out), hard_bits, hip_stream);
+    });
+}
+
+int64_t ldpc_hip_layered_fixed_direct_lds_bytes(const ldpc_hip_ctx *ctx)
+{
+    int64_t bytes = -1; // (the plan builder allocates; -1 for every code the layered plan refuses)
+    guarded([&] { bytes = ctx->eng->layered_fixed_direct_lds_bytes(); });
+    return bytes;
+}
+
 int ldpc_hip_stream_begin(ldpc_hip_ctx *ctx, int channel, uint64_t seed, double x)
 {
     return guarded([&] { ctx->eng->stream_begin(channel, seed, x, true); });

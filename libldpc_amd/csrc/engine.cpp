@@ -754,6 +754,14 @@ int64_t Engine::layered_fixed_lds_bytes()
                : static_cast<int64_t>(layered_fixed_region_bytes(layered_ms_records(L) / 20, static_cast<size_t>(plan_.nc)));
 }
 
+int64_t Engine::layered_fixed_direct_lds_bytes()
+{
+    const LayerPlan &L = layer_plan();
+    return !L.ok || plan_.has_isolated_vn || plan_.nc > 0xFFFF
+               ? -1
+               : static_cast<int64_t>(layered_fixed_direct_region_bytes(layered_ms_records(L) / 20, static_cast<size_t>(plan_.nc)));
+}
+
 int64_t Engine::qms_lds_bytes()
 {
     return qms_plan().ok ? static_cast<int64_t>(qms_region_bytes(qms_plan().slots, static_cast<size_t>(plan_.nc))) : -1;
@@ -1040,7 +1048,7 @@ static void set_stage_lists(DecodeArgs &a, Stage st, uint32_t *in, uint32_t *out
     a.redo_iter = st == Stage::kHandoverFirst ? out + 1 + n : nullptr;
 }
 
-void Engine::run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, uint64_t n, void *stream)
+void Engine::run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, uint64_t n, void *stream, const TypedIo *typed)
 {
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t nc = plan_.nc, nnz = plan_.nnz;
@@ -1058,10 +1066,26 @@ void Engine::run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, 
     a.hard = st.route(out.hard, stage_hard_, n * nc);
     a.llr_out = st.route(out.llr_out, stage_llr_out_, 8 * n * nc);
     a.llr_in_dump = st.route(out.llr_in, stage_llr_in_, 8 * n * nc);
+    // typed batch call: the packed decisions come from the decision bytes, the staged ones where the caller wants none
+    uint32_t *const hard_bits = typed ? st.route(typed->hard_bits, stage_bits_, 4 * n * ((nc + 31) / 32)) : nullptr;
+    if (hard_bits && !a.hard)
+        a.hard = static_cast<uint8_t *>(stage_hard_.reserve(n * nc));
+    const auto pack = [&] {
+        if (hard_bits)
+            check(launch_pack_hard(a.hard, n, plan_.nc, hard_bits, s), "pack decisions");
+    };
+    // ... and its input: fixed-point layered min-sum reads it as it is, every other decoder its binary64 image
+    const bool direct = typed && typed->llr && dec == Decoder::kLayeredFixedMinSum;
     // (1, 0) is plain min-sum: the launches of today, not corrected instantiations that would compute the same
     a.ms_correct = p.min_sum && !(ms_scale == 1.0 && ms_offset == 0.0);
     a.ms_scale = ms_scale, a.ms_offset = ms_offset;
     prof_mark(0, s);
+    if (typed && typed->llr && !direct)
+    {
+        double *w = static_cast<double *>(stage_in_.reserve(8 * n * nc));
+        check(launch_widen_llr(typed->llr, typed->type, typed->step, n * nc, w, s), "widen typed LLRs");
+        a.llr_in = w;
+    }
     const auto launch = [&](Stage stage) {
         switch (dec)
         {
@@ -1075,7 +1099,11 @@ void Engine::run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, 
             return;
         case Decoder::kLayeredFixedMinSum:
             upload_layer_plan();
-            check(launch_decode_layered_fixed(a, dev_layer_, layered_fixed_args(), s), "decode (fixed-point layered min-sum)");
+            if (direct)
+                check(launch_decode_layered_fixed_direct(a, dev_layer_, layered_fixed_args(), TypedLlrArgs{typed->llr, typed->type, 0}, s),
+                      "decode (fixed-point layered min-sum, typed LLRs)");
+            else
+                check(launch_decode_layered_fixed(a, dev_layer_, layered_fixed_args(), s), "decode (fixed-point layered min-sum)");
             return;
         case Decoder::kTernary:
             check(launch_decode_ternary(a, TernaryArgs{ms_ternary_, ternary_planes(plan_.max_vn_degree)}, s), "decode (ternary min-sum)");
@@ -1179,8 +1207,10 @@ void Engine::run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, 
         // launches — two more dispatches and a memset, a fifth of such a call's latency, for lists that are almost always
         // empty — are issued only when that number is not zero, and the results delivered again.
         const size_t pinned = st.pinned_bytes();
-        if (i == 0 && stage == Stage::kRatioFirst && n <= 16 && pinned && pinned <= OutStage::kPinnedLimit && a.mode == kModeLlr &&
-            st.flush(s, &pin_out_, list_out) == 0)
+        const bool deliver_now = i == 0 && stage == Stage::kRatioFirst && n <= 16 && pinned && pinned <= OutStage::kPinnedLimit && a.mode == kModeLlr;
+        if (deliver_now)
+            pack(); // (of this launch's decisions: they travel now)
+        if (deliver_now && st.flush(s, &pin_out_, list_out) == 0)
         {
             st.items.clear(); // (delivered)
             break;
@@ -1189,6 +1219,7 @@ void Engine::run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, 
     }
     set_stage_lists(a, Stage::kWhole, nullptr, nullptr, n);
     a.ws_handover = nullptr, a.handover_llr = 0;
+    pack();
     finish_batch(st, out, n, a.codeword, a.mode == kModeAwgn ? a.pairs_buffer : -1, stream);
 }
 
@@ -1407,23 +1438,47 @@ void Engine::run_counter(const DecParams &p, const BatchOut &out, uint64_t frame
 
 void Engine::decode_llr(const DecParams &p, uint64_t n, const double *llr_in, const BatchOut &out, void *stream)
 {
+    decode_typed(p, n, llr_in, kLlrF64, out, nullptr, stream);
+}
+
+// int8 LLRs are multiples of a fixed-point mode's step: they need "BP_MS" with quantized or fixed-point layered min-sum on
+std::string Engine::typed_refusal(const DecParams &p, int type) const
+{
+    const std::string who = "ldpc_hip_decode_batch_typed: ";
+    if (llr_type_bytes(type) == 0)
+        return who + "unknown LLR type " + std::to_string(type) + " (0 = binary64, 1 = binary32, 2 = binary16, 3 = int8)";
+    const Decoder d = decoder(p);
+    if (type == kLlrI8 && d != Decoder::kQuantizedMinSum && d != Decoder::kLayeredFixedMinSum)
+        return who + "int8 LLRs count steps of a fixed-point mode: they need \"BP_MS\" decoding with "
+                     "ldpc_hip_set_min_sum_quantization or ldpc_hip_set_min_sum_layered_fixed on";
+    return "";
+}
+
+void Engine::decode_typed(const DecParams &p, uint64_t n, const void *llr_in, int type, const BatchOut &out, uint32_t *hard_bits, void *stream)
+{
+    if (const std::string why = typed_refusal(p, type); !why.empty())
+        throw std::runtime_error(why);
     if (n == 0)
         return;
     upload_plan();
     hipStream_t s = static_cast<hipStream_t>(stream);
     const uint64_t nc = static_cast<uint64_t>(plan_.nc), sub = max_sub_batch();
+    const size_t elem = llr_type_bytes(type); // the typed source advances in units of its own element size
+    const uint64_t words = (nc + 31) / 32;    // ... and the packed decisions in words per frame
+    TypedIo io;
+    io.type = type;
+    io.step = decoder(p) == Decoder::kQuantizedMinSum ? ms_step_ : ms_lf_step_;
     for (uint64_t done = 0; done < n; done += sub)
     {
         const uint64_t m = std::min(sub, n - done);
-        const size_t bytes = 8 * m * nc;
+        const size_t bytes = elem * m * nc;
         DecodeArgs a{};
         a.mode = kModeLlr;
-        const double *src = llr_in + done * nc;
-        if (is_device_ptr(src))
-            a.llr_in = src;
-        else
+        const void *src = static_cast<const char *>(llr_in) + elem * done * nc;
+        if (!is_device_ptr(src))
         {
-            void *d = stage_in_.reserve(bytes);
+            // staged in its own type (binary64 where the decoder reads it; the widened image of the others goes there)
+            void *d = (type == kLlrF64 ? stage_in_ : stage_typed_).reserve(bytes);
             const void *from = src;
             if (bytes <= (1u << 20)) // small inputs through page-locked memory (see OutStage::flush)
             {
@@ -1442,9 +1497,14 @@ void Engine::decode_llr(const DecParams &p, uint64_t n, const double *llr_in, co
             check(hipMemcpyAsync(d, from, bytes, hipMemcpyHostToDevice, s), "copy in");
             if (from != src)
                 check(hipEventRecord(static_cast<hipEvent_t>(pin_in_ev_), s), "event");
-            a.llr_in = static_cast<const double *>(d);
+            src = d;
         }
-        run_decode(a, p, out.at(done, nc), m, stream);
+        if (type == kLlrF64)
+            a.llr_in = static_cast<const double *>(src);
+        else
+            io.llr = src;
+        io.hard_bits = hard_bits ? hard_bits + done * words : nullptr;
+        run_decode(a, p, out.at(done, nc), m, stream, type == kLlrF64 && !hard_bits ? nullptr : &io);
     }
 }
 

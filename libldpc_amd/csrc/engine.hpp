@@ -308,6 +308,7 @@ class Engine
     int64_t layered_ms_lds_bytes();
     int64_t qms_lds_bytes();
     int64_t layered_fixed_lds_bytes(); // (plan.hpp, layered_fixed_region_bytes)
+    int64_t layered_fixed_direct_lds_bytes(); // (plan.hpp, layered_fixed_direct_region_bytes: typed LLRs, nothing staged)
     // host only: LDS bytes of one 32-frame group of ternary min-sum with llr_out wanted (plan.hpp, ternary_lds_bytes), -1 for a
     // code outside what the kernel's tables hold (refusal() says which limit)
     int64_t ternary_group_lds_bytes() const;
@@ -318,6 +319,11 @@ class Engine
 
     // ---- decode given LLRs (C-ABI decode(), shared.cpp:47-65, batched) ----
     void decode_llr(const DecParams &p, uint64_t n, const double *llr_in, const BatchOut &out, void *stream);
+    // ... of element type `type` (kernels.hpp, LlrType), and the decisions packed 32 to a word as well (hard_bits [n][ceil(nc /
+    // 32)], device or host, nullptr = not wanted; include/ldpc_amd.h, ldpc_hip_decode_batch_typed).  kLlrF64 without
+    // hard_bits is decode_llr.  Host only: what the call refuses before anything touches the GPU, empty when it is taken
+    std::string typed_refusal(const DecParams &p, int type) const;
+    void decode_typed(const DecParams &p, uint64_t n, const void *llr_in, int type, const BatchOut &out, uint32_t *hard_bits, void *stream);
 
     // ---- fused channel + decode on the reference's noise stream ----
     // set_channel_param semantics (channel.cpp:37-42): the stream restarts at frame 0.
@@ -381,7 +387,16 @@ class Engine
     QmsArgs qms_args() const; // the quantizer and the correction table of the settings in force
     LayeredFixedArgs layered_fixed_args() const; // ... and those of fixed-point layered min-sum
     bool register_resident() const { return residency_ == Residency::kRegTotals || residency_ == Residency::kRegMessages; }
-    void run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, uint64_t n, void *stream);
+    // what a typed batch call adds to a launch of given LLRs: the typed input on the device (llr null: a.llr_in holds binary64
+    // values already) with the step an int8 stands for, and where the packed decisions go (null: not wanted)
+    struct TypedIo
+    {
+        const void *llr = nullptr;
+        int type = kLlrF64;
+        double step = 1.0;
+        uint32_t *hard_bits = nullptr;
+    };
+    void run_decode(DecodeArgs &a, const DecParams &p, const BatchOut &out, uint64_t n, void *stream, const TypedIo *typed = nullptr);
     // BSC / BEC: the batch reads the noise stream's raw draws from word `raw_first` on
     void run_bsc(DecodeArgs &a, const DecParams &p, const BatchOut &out, uint64_t n, uint64_t raw_first, void *stream);
     // (ctr_frame0: counter-based noise, the stream index of the batch's frame 0; raw_first is then unused)
@@ -483,6 +498,7 @@ class Engine
     int pp_ = 0;
     DeviceBuffer enc_base_; // sharded encoding: the other ranks' info-word sums (two rows of `words`)
     DeviceBuffer stage_in_, stage_iters_, stage_be_, stage_hard_, stage_llr_out_, stage_llr_in_, stage_cw_;
+    DeviceBuffer stage_typed_, stage_bits_; // typed batch call: host input in its own type, packed decisions for a host buffer
     DeviceBuffer ws_msg_, ws_llr_, ws_hb_, ws_scr_;
     PinnedBuffer pin_in_, pin_out_;
     void *pin_in_ev_ = nullptr; // hipEvent_t: the last host-to-device copy out of pin_in_

@@ -296,6 +296,31 @@ struct LayeredFixedArgs
     uint32_t lut[32];
 };
 int launch_decode_layered_fixed(const DecodeArgs &a, const DevLayerPlan &L, const LayeredFixedArgs &q, void *stream);
+// typed LLRs of the batch call (include/ldpc_amd.h, ldpc_hip_decode_batch_typed: LDPC_HIP_LLR_*)
+enum LlrType : int
+{
+    kLlrF64 = 0,
+    kLlrF32 = 1,
+    kLlrF16 = 2, // IEEE binary16
+    kLlrI8 = 3,  // k stands for fl(k * step) of the fixed-point mode in force
+};
+constexpr size_t llr_type_bytes(int type) { return type == kLlrF64 ? 8 : type == kLlrF32 ? 4 : type == kLlrF16 ? 2 : type == kLlrI8 ? 1 : 0; }
+// the typed input of a launch, beside DecodeArgs (whose layout does not move): [n_frames][nc] elements of `type`, column order
+struct TypedLlrArgs
+{
+    const void *llr;
+    int32_t type; // kLlrF32, kLlrF16 or kLlrI8
+    int32_t pad;
+};
+// fixed-point layered min-sum reading typed LLRs itself (kernels_layered_fixed_direct.hip): a.llr_in is not read, no binary64
+// LLRs are staged in LDS (plan.hpp, layered_fixed_direct_region_bytes); the outputs are those of launch_decode_layered_fixed
+// on the widened values, a.llr_in_dump included
+int launch_decode_layered_fixed_direct(const DecodeArgs &a, const DevLayerPlan &L, const LayeredFixedArgs &q, const TypedLlrArgs &t,
+                                       void *stream);
+// kernels_convert.hip: dst[i] = src[i] widened to binary64 (kLlrF32, kLlrF16: exact) or fl((double) src[i] * step) (kLlrI8),
+// i < count; bits[f][ceil(nc / 32)] = the decision bytes hard[f][nc] packed, bit c & 31 of word c >> 5, unused bits zero
+int launch_widen_llr(const void *src, int type, double step, uint64_t count, double *dst, void *stream);
+int launch_pack_hard(const uint8_t *hard, uint64_t n, int nc, uint32_t *bits, void *stream);
 
 // opt-in non-parity ternary min-sum, bit-sliced over 32 frames per workgroup (kernels_ternary.hip; include/ldpc_amd.h,
 // ldpc_hip_set_min_sum_ternary) on the general plan.  a.ms_* are not read.  With a.llr_out null the planes of A are left out

@@ -22,107 +22,19 @@
 //   * behind the larger of the two, the correction table, 128 bytes.
 // h.txt: 9 344 bytes per frame, 17 frames per CU; the n = 8192 (3,6) code 65 664, two.
 //
+// The typed batch call (ldpc_hip_decode_batch_typed) has a form of its own without the binary64 area: h.txt 6 528 bytes and 25
+// frames per CU (kernels_layered_fixed_direct.hip).  What the two share is kernels_layered_fixed_impl.hpp and
+// kernels_layered_fixed_body.inc.
+//
 // Iteration count returned: sweeps completed before the sweep whose syndrome check passed (the reference's convention,
 // decoder.cpp:21-22,74-77); the syndrome of the current decisions is taken after every sweep.
-#include <hip/hip_runtime.h>
-
-#include "device_channel.hpp"
-#include "device_math.hpp"
-#include "kernels.hpp"
-#include "launch_lds.hpp"
+#include "kernels_layered_fixed_impl.hpp" // the quantizer and the check node (shared with the direct form)
 
 namespace ldpc_amd
 {
 
 namespace
 {
-constexpr int kLfThreads = 64; // one wave per workgroup, so that a CU takes as many frames as its LDS holds
-
-// the frame's LDS is written as binary64 and read back as int16 and 32-bit words: these types alias everything
-typedef int16_t __attribute__((may_alias)) lds_i16;
-typedef uint32_t __attribute__((may_alias)) lds_u32;
-typedef double __attribute__((may_alias)) lds_f64;
-
-// clamp(rint(fl(llr * inv)), -qmax, +qmax), the clamp in binary64 (an infinity or 99999.9 saturates); rint is round-half-
-// to-even; a NaN gives 0 (kernels_qms.hip, qms_quantize: the same quantizer)
-__device__ __forceinline__ int lf_quantize(double llr, double inv, int qmax)
-{
-#pragma clang fp contract(off)
-    const double x = __builtin_rint(llr * inv);
-    const double q = static_cast<double>(qmax);
-    return x >= q ? qmax : (x <= -q ? -qmax : (x == x ? static_cast<int>(x) : 0));
-}
-
-__device__ __forceinline__ int lf_clamp(int x, int m) // (a maximum and a minimum)
-{
-    const int lo = x < -m ? -m : x;
-    return lo > m ? m : lo;
-}
-// -1 where bit j of x is set, else 0 (one signed one-bit field extract)
-__device__ __forceinline__ int lf_bit_mask(uint32_t x, int j) { return -static_cast<int>((x >> j) & 1u); }
-// a where mask is -1, b where it is 0
-__device__ __forceinline__ int lf_sel(int mask, int a, int b) { return (a & mask) | (b & ~mask); }
-
-__device__ __forceinline__ uint32_t vn_of(const uint32_t (&pk)[4], int j) { return (j & 1) ? pk[j >> 1] >> 16 : pk[j >> 1] & 0xFFFFu; }
-
-// one check node of degree D on this lane: T = the frame's totals, pk = its neighbours' VN ranks (two per word), rec = its
-// record
-template <int D>
-__device__ __forceinline__ void cn_layered_fixed(lds_i16 *T, lds_u32 *rec, const uint8_t *lut, const uint32_t (&pk)[4], int qmax, int pmax)
-{
-    // Written without a comparison per edge: a compare that feeds a select costs the pair and the wait between them, and the
-    // kernel is bound by the instructions it issues (17 waves on a CU keep the LDS latency covered).  Masks are 0 or -1:
-    // (x ^ mask) - mask negates under the mask, sel() picks by it; the minimum, the runner-up and the argmin come from
-    // KEYS |u| << 3 | j (the smallest key holds the smallest |u| and an edge that has it).
-    const uint32_t o = *rec;
-    const int o_rest = static_cast<int>(o & 127u), o_arg = static_cast<int>((o >> 7) & 127u);
-    const uint32_t o_hot = 1u << ((o >> 14) & 7u); // bit argmin
-    const int o_neg = static_cast<int>(o >> 17);
-    uint32_t n[D];
-    int t[D];
-#pragma unroll
-    for (int j = 0; j < D; ++j)
-        n[j] = vn_of(pk, j);
-    uint32_t key1 = 127u << 3, key2 = 127u << 3; // (|u| <= qmax <= 127)
-    int signs = 0, sx = 0;
-#pragma unroll
-    for (int j = 0; j < D; ++j)
-    {
-        const int mo = lf_sel(lf_bit_mask(o_hot, j), o_arg, o_rest);
-        const int neg = lf_bit_mask(o_neg, j);
-        const int m = (mo ^ neg) - neg;
-        t[j] = static_cast<int>(T[n[j]]) - m; // what the neighbour says without this node's last message: exact
-        const int u = lf_clamp(t[j], qmax); // ... at message width
-        const int s = u >> 31;              // -1 where u < 0 (an integer zero is not negative)
-        const uint32_t key = static_cast<uint32_t>((u ^ s) - s) << 3 | static_cast<uint32_t>(j);
-        signs |= s & (1 << j), sx ^= s;
-        const uint32_t hi = key > key1 ? key : key1;
-        key1 = key < key1 ? key : key1;
-        key2 = hi < key2 ? hi : key2;
-    }
-    const int r_rest = lut[key1 >> 3], r_arg = lut[key2 >> 3];
-    const uint32_t k = key1 & 7u, hot = 1u << k;
-    const int out_signs = (signs ^ sx) & ((1 << D) - 1); // edge j: negative iff an odd number of the others is
-#pragma unroll
-    for (int j = 0; j < D; ++j)
-    {
-        const int mo = lf_sel(lf_bit_mask(hot, j), r_arg, r_rest);
-        const int neg = lf_bit_mask(out_signs, j);
-        T[n[j]] = static_cast<int16_t>(lf_clamp(t[j] + ((mo ^ neg) - neg), pmax));
-    }
-    *rec = static_cast<uint32_t>(r_rest) | static_cast<uint32_t>(r_arg) << 7 | k << 14 | static_cast<uint32_t>(out_signs) << 17;
-}
-
-template <int D>
-__device__ __forceinline__ uint32_t cn_parity_fixed(const lds_i16 *T, const uint32_t (&pk)[4])
-{
-    uint32_t p = 0;
-#pragma unroll
-    for (int j = 0; j < D; ++j)
-        p ^= static_cast<uint32_t>(T[vn_of(pk, j)] <= 0); // decoder.cpp:58: out <= 0 decides 1
-    return p;
-}
-
 template <bool WANT_LLR>
 __global__ __launch_bounds__(kLfThreads) void decode_layered_fixed_kernel(const DecodeArgs a, const DevLayerPlan L, const LayeredFixedArgs q)
 {
@@ -169,104 +81,7 @@ __global__ __launch_bounds__(kLfThreads) void decode_layered_fixed_kernel(const 
         }
     }
     __syncthreads(); // the binary64 area is free
-    for (uint32_t i = lane; i < rec_slots; i += 64)
-        records[i] = 0; // every message 0: magnitudes 0, argmin 0, no sign bit
-    __syncthreads();
-
-    // the step's neighbour table one step AHEAD (kernels_layered.hip)
-    const auto steps = uniform_table(reinterpret_cast<const uint32_t *>(L.steps));
-    const auto rec_off = uniform_table(L.rec_off);
-    const uint32_t *table = L.vn4 + lane;
-    auto fetch = [&](uint32_t s, uint32_t (&pk)[4]) {
-#pragma unroll
-        for (int w = 0; w < 4; ++w)
-            pk[w] = table[(s * 4 + w) * 64];
-    };
-    uint32_t I = 0;
-    uint32_t nxt[4];
-    fetch(0, nxt);
-    while (I < a.iterations)
-    {
-        for (uint32_t s = 0; s < L.n_steps; ++s)
-        {
-            uint32_t cur[4] = {nxt[0], nxt[1], nxt[2], nxt[3]};
-            fetch(s + 1 < L.n_steps ? s + 1 : 0, nxt); // (the sweep's last step fetches the first one's)
-            const uint32_t cd = steps[2 * s + 1], ro = rec_off[s] / 20;
-            const int count = cd & 0xFFFF, degree = cd >> 16;
-            if (lane < count)
-            {
-                lds_u32 *rec = records + ro + lane;
-                switch (degree) // wave-uniform
-                {
-                case 2: cn_layered_fixed<2>(T, rec, lut, cur, qmax, pmax); break;
-                case 3: cn_layered_fixed<3>(T, rec, lut, cur, qmax, pmax); break;
-                case 4: cn_layered_fixed<4>(T, rec, lut, cur, qmax, pmax); break;
-                case 5: cn_layered_fixed<5>(T, rec, lut, cur, qmax, pmax); break;
-                case 6: cn_layered_fixed<6>(T, rec, lut, cur, qmax, pmax); break;
-                case 7: cn_layered_fixed<7>(T, rec, lut, cur, qmax, pmax); break;
-                case 8: cn_layered_fixed<8>(T, rec, lut, cur, qmax, pmax); break;
-                default: break;
-                }
-            }
-            __builtin_amdgcn_wave_barrier(); // (LDS operations of a wave execute in order; this only stops the compiler)
-        }
-        // syndrome of the decisions after this sweep (decoder.cpp:66-72)
-        if (a.early_term)
-        {
-            uint32_t bad = 0;
-            for (uint32_t s = 0; s < L.n_steps; ++s)
-            {
-                uint32_t cur[4] = {nxt[0], nxt[1], nxt[2], nxt[3]};
-                fetch(s + 1 < L.n_steps ? s + 1 : 0, nxt);
-                const uint32_t cd = steps[2 * s + 1];
-                const int count = cd & 0xFFFF, degree = cd >> 16;
-                if (lane < count)
-                {
-                    switch (degree)
-                    {
-                    case 2: bad |= cn_parity_fixed<2>(T, cur); break;
-                    case 3: bad |= cn_parity_fixed<3>(T, cur); break;
-                    case 4: bad |= cn_parity_fixed<4>(T, cur); break;
-                    case 5: bad |= cn_parity_fixed<5>(T, cur); break;
-                    case 6: bad |= cn_parity_fixed<6>(T, cur); break;
-                    case 7: bad |= cn_parity_fixed<7>(T, cur); break;
-                    case 8: bad |= cn_parity_fixed<8>(T, cur); break;
-                    default: break;
-                    }
-                }
-            }
-            if (__ballot(bad != 0) == 0)
-                break;
-        }
-        ++I;
-    }
-    if (lane == 0 && a.iters)
-        a.iters[frame] = I;
-    const bool ran = a.iterations > 0;
-    uint8_t *h = a.hard ? a.hard + frame * nc : nullptr;
-    for (int r = lane; r < nc; r += 64)
-    {
-        const int x = T[r];
-        if (h)
-            h[P.rank_col[r]] = ran ? static_cast<uint8_t>(x <= 0) : 0; // mCO is still zero-initialised when no iteration ran
-        if constexpr (WANT_LLR)
-            a.llr_out[frame * nc + P.rank_col[r]] = ran ? static_cast<double>(x) * q.step : 0.0;
-    }
-    if (a.bit_errors)
-    {
-        int err = 0;
-        for (int i = lane; i < P.n_bitpos; i += 64)
-        {
-            const int est = ran ? static_cast<int>(T[P.tx_rank[i]] <= 0) : 0;
-            const int tx = cw ? static_cast<int>(cw[P.bit_pos[i]]) : 0;
-            err += est != tx;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1)
-            err += __shfl_xor(err, o, 64);
-        if (lane == 0)
-            a.bit_errors[frame] = static_cast<uint32_t>(err);
-    }
+#include "kernels_layered_fixed_body.inc"
 }
 } // namespace
 

@@ -216,6 +216,13 @@ constexpr size_t layered_fixed_lut_off(size_t slots, size_t nc)
     return 8 * nc > layered_fixed_records_off(nc) + 4 * slots ? 8 * nc : layered_fixed_records_off(nc) + 4 * slots;
 }
 constexpr size_t layered_fixed_region_bytes(size_t slots, size_t nc) { return (layered_fixed_lut_off(slots, nc) + 128 + 15) & ~size_t(15); }
+// ... and where typed LLRs are quantized straight from memory (kernels_layered_fixed_direct.hip) no binary64 value is staged:
+// the totals, the records, the table
+//   bytes = round4(2 nc) + 4 slots + 128, rounded up to 16
+constexpr size_t layered_fixed_direct_region_bytes(size_t slots, size_t nc)
+{
+    return (layered_fixed_records_off(nc) + 4 * slots + 128 + 15) & ~size_t(15);
+}
 constexpr size_t kCuLdsBytes = 160 * 1024; // the LDS of one CU: what a frame of any decoder has to fit
 // what build_reg_plan leaves of it to the static LDS of the messages-form register kernels (kernels_reg.hip: 272 bytes in the
 // compiler's resource report — 16 of misc[] and 256 the compiler adds; tests/test_generator_codes_host.py holds the report to
