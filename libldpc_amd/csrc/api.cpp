@@ -312,7 +312,7 @@ int ldpc_hip_min_sum_schedule(const ldpc_hip_ctx *ctx) { return ctx->eng->ms_sch
 int64_t ldpc_hip_layered_min_sum_lds_bytes(const ldpc_hip_ctx *ctx)
 {
     int64_t bytes = -1;
-    guarded([&] { bytes = ctx->eng->layered_ms_lds_bytes(); }); // (the plan builder allocates)
+    guarded([&] { bytes = ctx->eng->lds_bytes(Decoder::kLayeredMinSum); }); // (the plan builder allocates)
     return bytes;
 }
 
@@ -333,7 +333,7 @@ int ldpc_hip_min_sum_quantization(const ldpc_hip_ctx *ctx, int *bits, double *st
 int64_t ldpc_hip_quantized_min_sum_lds_bytes(const ldpc_hip_ctx *ctx)
 {
     int64_t bytes = -1; // (the plan builder allocates; -1 for every code the setter refuses)
-    guarded([&] { bytes = ctx->eng->refusal(Decoder::kQuantizedMinSum).empty() ? ctx->eng->qms_lds_bytes() : -1; });
+    guarded([&] { bytes = ctx->eng->lds_bytes_if_taken(Decoder::kQuantizedMinSum); });
     return bytes;
 }
 
@@ -347,7 +347,7 @@ int ldpc_hip_min_sum_ternary(const ldpc_hip_ctx *ctx) { return ctx->eng->ms_tern
 int64_t ldpc_hip_ternary_lds_bytes(const ldpc_hip_ctx *ctx)
 {
     int64_t bytes = -1; // (-1 for every code the setter refuses)
-    guarded([&] { bytes = ctx->eng->refusal(Decoder::kTernary).empty() ? ctx->eng->ternary_group_lds_bytes() : -1; });
+    guarded([&] { bytes = ctx->eng->lds_bytes_if_taken(Decoder::kTernary); });
     return bytes;
 }
 
@@ -370,7 +370,7 @@ int ldpc_hip_min_sum_layered_fixed(const ldpc_hip_ctx *ctx, int *msg_bits, int *
 int64_t ldpc_hip_layered_fixed_lds_bytes(const ldpc_hip_ctx *ctx)
 {
     int64_t bytes = -1; // (the plan builder allocates; -1 for every code the setter refuses)
-    guarded([&] { bytes = ctx->eng->refusal(Decoder::kLayeredFixedMinSum).empty() ? ctx->eng->layered_fixed_lds_bytes() : -1; });
+    guarded([&] { bytes = ctx->eng->lds_bytes_if_taken(Decoder::kLayeredFixedMinSum); });
     return bytes;
 }
 

@@ -740,18 +740,34 @@ static size_t layered_region_bytes(const LayerPlan &L, size_t nc, size_t msg_byt
     return (std::max(8 * nc, 4 * ((nc + 3) & ~size_t(3)) + msg_bytes * L.slots) + 15) & ~size_t(15);
 }
 
-int64_t Engine::layered_ms_lds_bytes()
+int64_t Engine::lds_bytes(Decoder d)
 {
-    const LayerPlan &L = layer_plan();
-    return !L.ok || plan_.has_isolated_vn ? -1 : static_cast<int64_t>(layered_ms_region_bytes(L, static_cast<size_t>(plan_.nc)));
-}
-
-int64_t Engine::layered_fixed_lds_bytes()
-{
-    const LayerPlan &L = layer_plan();
-    return !L.ok || plan_.has_isolated_vn || plan_.nc > 0xFFFF
-               ? -1
-               : static_cast<int64_t>(layered_fixed_region_bytes(layered_ms_records(L) / 20, static_cast<size_t>(plan_.nc)));
+    const Plan &p = plan_;
+    const size_t nc = static_cast<size_t>(p.nc);
+    switch (d)
+    {
+    case Decoder::kLayeredMinSum:
+    case Decoder::kLayeredFixedMinSum:
+    {
+        const LayerPlan &L = layer_plan();
+        if (!L.ok || p.has_isolated_vn)
+            return -1;
+        if (d == Decoder::kLayeredMinSum)
+            return static_cast<int64_t>(layered_ms_region_bytes(L, nc));
+        return p.nc > 0xFFFF ? -1 : static_cast<int64_t>(layered_fixed_region_bytes(layered_ms_records(L) / 20, nc));
+    }
+    case Decoder::kQuantizedMinSum:
+        return qms_plan().ok ? static_cast<int64_t>(qms_region_bytes(qms_plan().slots, nc)) : -1;
+    case Decoder::kTernary:
+        // the general plan is all it needs.  A u16 holds a slot and a rank, a wave's work list the lanes of a register (blocks
+        // / 8 <= 64), seven planes a column's total (degree + 7 <= 63), the message words the error count's (kernels_ternary.hip)
+        if (p.nc > 0xFFFF || p.nnz <= 0 || p.nnz > 0xFFFF || p.max_vn_degree > kTernaryMaxVnDegree || p.cn_blocks.size() > 512 ||
+            p.vn_blocks.size() > 512 || static_cast<size_t>(p.n_bitpos) > ternary_message_words(p.nnz, p.nc))
+            return -1;
+        return static_cast<int64_t>(ternary_lds_bytes(p.nnz, p.nc, ternary_planes(p.max_vn_degree), true));
+    default: // the resident decoders and the sum-product modes have no figure of this kind
+        return -1;
+    }
 }
 
 int64_t Engine::layered_fixed_direct_lds_bytes()
@@ -762,20 +778,14 @@ int64_t Engine::layered_fixed_direct_lds_bytes()
                : static_cast<int64_t>(layered_fixed_direct_region_bytes(layered_ms_records(L) / 20, static_cast<size_t>(plan_.nc)));
 }
 
-int64_t Engine::qms_lds_bytes()
+// a min-sum variant: its plan takes the code (bytes >= 0, else `outside` says what it takes) and `unit` fits the LDS of a CU
+static std::string lds_refusal(int64_t bytes, const std::string &outside, const char *unit)
 {
-    return qms_plan().ok ? static_cast<int64_t>(qms_region_bytes(qms_plan().slots, static_cast<size_t>(plan_.nc))) : -1;
-}
-
-// ternary min-sum: the general plan is all it needs.  A u16 holds a slot and a rank, a wave's work list the lanes of a register
-// (blocks / 8 <= 64), seven planes a column's total (degree + 7 <= 63), the message words the error count's (kernels_ternary.hip)
-int64_t Engine::ternary_group_lds_bytes() const
-{
-    const Plan &p = plan_;
-    if (p.nc > 0xFFFF || p.nnz <= 0 || p.nnz > 0xFFFF || p.max_vn_degree > kTernaryMaxVnDegree || p.cn_blocks.size() > 512 ||
-        p.vn_blocks.size() > 512 || static_cast<size_t>(p.n_bitpos) > ternary_message_words(p.nnz, p.nc))
-        return -1;
-    return static_cast<int64_t>(ternary_lds_bytes(p.nnz, p.nc, ternary_planes(p.max_vn_degree), true));
+    if (bytes < 0)
+        return outside;
+    if (bytes > static_cast<int64_t>(kCuLdsBytes))
+        return std::string(unit) + " take " + std::to_string(bytes) + " bytes of LDS, more than " + std::to_string(kCuLdsBytes);
+    return "";
 }
 
 // What each opt-in variant takes, once (engine.hpp).  The texts are what callers see: the two sum-product modes whole, at
@@ -799,140 +809,88 @@ std::string Engine::refusal(Decoder d)
                    "most 65535 columns, totals and messages of one frame within 160 KB of LDS, no isolated variable node)";
         break;
     case Decoder::kLayeredMinSum:
+        return lds_refusal(lds_bytes(d),
+                           "the layered schedule takes codes whose check nodes all have degree 2..8, with at most 65535 columns and no "
+                           "isolated variable node",
+                           "a frame's totals and check-node records");
     case Decoder::kQuantizedMinSum:
-    {
-        const bool q = d == Decoder::kQuantizedMinSum;
-        const int64_t bytes = q ? qms_lds_bytes() : layered_ms_lds_bytes();
-        if (bytes < 0)
-            return q ? "quantized min-sum takes codes of at most 65535 columns"
-                     : "the layered schedule takes codes whose check nodes all have degree 2..8, with at most 65535 columns and no "
-                       "isolated variable node";
-        if (bytes > static_cast<int64_t>(kCuLdsBytes))
-            return std::string("a frame's ") + (q ? "messages, totals and channel values" : "totals and check-node records") + " take " +
-                   std::to_string(bytes) + " bytes of LDS, more than " + std::to_string(kCuLdsBytes);
-        break;
-    }
+        return lds_refusal(lds_bytes(d), "quantized min-sum takes codes of at most 65535 columns", "a frame's messages, totals and channel values");
     case Decoder::kLayeredFixedMinSum:
-    {
-        const int64_t bytes = layered_fixed_lds_bytes();
-        if (bytes < 0)
-            return "fixed-point layered min-sum takes codes whose check nodes all have degree 2..8, with at most 65535 columns and "
-                   "no isolated variable node";
-        if (bytes > static_cast<int64_t>(kCuLdsBytes))
-            return "a frame's channel values, totals and check-node records take " + std::to_string(bytes) + " bytes of LDS, more than " +
-                   std::to_string(kCuLdsBytes);
-        break;
-    }
+        return lds_refusal(lds_bytes(d),
+                           "fixed-point layered min-sum takes codes whose check nodes all have degree 2..8, with at most 65535 columns and "
+                           "no isolated variable node",
+                           "a frame's channel values, totals and check-node records");
     case Decoder::kTernary:
-    {
-        const int64_t bytes = ternary_group_lds_bytes();
-        if (bytes < 0)
-            return "ternary min-sum takes codes of at most 65535 columns and 65535 edges with column degrees up to " +
-                   std::to_string(kTernaryMaxVnDegree) + " (and at most 512 blocks of 64 equal-degree nodes on either side)";
-        if (bytes > static_cast<int64_t>(kCuLdsBytes))
-            return "a group's messages, decisions and totals (32 frames) take " + std::to_string(bytes) + " bytes of LDS, more than " +
-                   std::to_string(kCuLdsBytes);
-        break;
-    }
+        return lds_refusal(lds_bytes(d),
+                           "ternary min-sum takes codes of at most 65535 columns and 65535 edges with column degrees up to " +
+                               std::to_string(kTernaryMaxVnDegree) + " (and at most 512 blocks of 64 equal-degree nodes on either side)",
+                           "a group's messages, decisions and totals (32 frames)");
     }
     return "";
 }
 
+// What the four setters share, once each has checked its own arguments: at most one variant is in force, on a code its
+// decoder takes.  Throws behind the setter's name and changes nothing, or puts v in force
+void Engine::enter_ms_variant(MsVariant v)
+{
+    const std::string who = std::string(ms_info(v).setter) + ": ";
+    if (ms_variant_ != v && ms_variant_ != MsVariant::kFlooding)
+    {
+        // (fixed-point layered min-sum tells the other layered decoder from itself)
+        const bool two_layered = v == MsVariant::kLayeredFixed && ms_variant_ == MsVariant::kLayered;
+        throw std::runtime_error(who + ms_info(v).subject + " does not combine with " +
+                                 (two_layered ? "the (binary64) layered schedule" : ms_info(ms_variant_).obstacle) + " (" +
+                                 ms_info(ms_variant_).off_first + " first)");
+    }
+    if (const std::string why = refusal(ms_info(v).decoder); !why.empty())
+        throw std::runtime_error(who + why);
+    ms_variant_ = v;
+}
+
 void Engine::set_ms_schedule(int schedule)
 {
-    const std::string who = "ldpc_hip_set_min_sum_schedule: ";
     if (schedule != 0 && schedule != 1)
-        throw std::runtime_error(who + "unknown schedule " + std::to_string(schedule) + " (0 = flooding, 1 = layered)");
-    if (schedule == 1)
-    {
-        if (ms_bits_)
-            throw std::runtime_error(who + "the layered schedule does not combine with quantized min-sum "
-                                           "(ldpc_hip_set_min_sum_quantization(ctx, 0, 0) first)");
-        if (ms_ternary_)
-            throw std::runtime_error(who + "the layered schedule does not combine with ternary min-sum "
-                                           "(ldpc_hip_set_min_sum_ternary(ctx, 0) first)");
-        if (ms_lf_msg_bits_)
-            throw std::runtime_error(who + "the layered schedule does not combine with fixed-point layered min-sum "
-                                           "(ldpc_hip_set_min_sum_layered_fixed(ctx, 0, 0, 0) first)");
-        if (const std::string why = refusal(Decoder::kLayeredMinSum); !why.empty())
-            throw std::runtime_error(who + why);
-    }
-    ms_schedule_ = schedule;
+        throw std::runtime_error(std::string(ms_info(MsVariant::kLayered).setter) + ": unknown schedule " + std::to_string(schedule) +
+                                 " (0 = flooding, 1 = layered)");
+    if (schedule == 0)
+        return leave_ms_variant(MsVariant::kLayered);
+    enter_ms_variant(MsVariant::kLayered);
 }
 
 void Engine::set_ms_quantization(int bits, double step)
 {
-    const std::string who = "ldpc_hip_set_min_sum_quantization: ";
     if (bits == 0) // off: the step is ignored
-    {
-        ms_bits_ = 0;
-        return;
-    }
+        return leave_ms_variant(MsVariant::kQuantized);
     // (the comparisons are false for NaN: a NaN fails them)
     if (bits < 2 || bits > 8 || !(step >= 0x1p-20 && step <= 0x1p20))
-        throw std::runtime_error(who + "need bits 0 (off) or 2..8 and 2^-20 <= step <= 2^20, got (" + std::to_string(bits) + ", " +
+        throw std::runtime_error(std::string(ms_info(MsVariant::kQuantized).setter) +
+                                 ": need bits 0 (off) or 2..8 and 2^-20 <= step <= 2^20, got (" + std::to_string(bits) + ", " +
                                  std::to_string(step) + ")");
-    if (ms_schedule_ == 1)
-        throw std::runtime_error(who + "quantized min-sum does not combine with the layered schedule "
-                                       "(ldpc_hip_set_min_sum_schedule(ctx, LDPC_HIP_MS_SCHEDULE_FLOODING) first)");
-    if (ms_ternary_)
-        throw std::runtime_error(who + "quantized min-sum does not combine with ternary min-sum "
-                                       "(ldpc_hip_set_min_sum_ternary(ctx, 0) first)");
-    if (ms_lf_msg_bits_)
-        throw std::runtime_error(who + "quantized min-sum does not combine with fixed-point layered min-sum "
-                                       "(ldpc_hip_set_min_sum_layered_fixed(ctx, 0, 0, 0) first)");
-    if (const std::string why = refusal(Decoder::kQuantizedMinSum); !why.empty())
-        throw std::runtime_error(who + why);
+    enter_ms_variant(MsVariant::kQuantized);
     ms_bits_ = bits, ms_step_ = step;
 }
 
 void Engine::set_ms_ternary(int weight)
 {
-    const std::string who = "ldpc_hip_set_min_sum_ternary: ";
     if (weight == 0)
-    {
-        ms_ternary_ = 0;
-        return;
-    }
+        return leave_ms_variant(MsVariant::kTernary);
     if (weight < 0 || weight > 7)
-        throw std::runtime_error(who + "need weight 0 (off) or 1..7, got " + std::to_string(weight));
-    if (ms_schedule_ == 1)
-        throw std::runtime_error(who + "ternary min-sum does not combine with the layered schedule "
-                                       "(ldpc_hip_set_min_sum_schedule(ctx, LDPC_HIP_MS_SCHEDULE_FLOODING) first)");
-    if (ms_bits_)
-        throw std::runtime_error(who + "ternary min-sum does not combine with quantized min-sum "
-                                       "(ldpc_hip_set_min_sum_quantization(ctx, 0, 0) first)");
-    if (ms_lf_msg_bits_)
-        throw std::runtime_error(who + "ternary min-sum does not combine with fixed-point layered min-sum "
-                                       "(ldpc_hip_set_min_sum_layered_fixed(ctx, 0, 0, 0) first)");
-    if (const std::string why = refusal(Decoder::kTernary); !why.empty())
-        throw std::runtime_error(who + why);
+        throw std::runtime_error(std::string(ms_info(MsVariant::kTernary).setter) + ": need weight 0 (off) or 1..7, got " +
+                                 std::to_string(weight));
+    enter_ms_variant(MsVariant::kTernary);
     ms_ternary_ = weight;
 }
 
 void Engine::set_ms_layered_fixed(int msg_bits, int app_bits, double step)
 {
-    const std::string who = "ldpc_hip_set_min_sum_layered_fixed: ";
     if (msg_bits == 0) // off: the other arguments are ignored
-    {
-        ms_lf_msg_bits_ = 0;
-        return;
-    }
+        return leave_ms_variant(MsVariant::kLayeredFixed);
     // (the comparisons are false for NaN: a NaN fails them)
     if (msg_bits < 2 || msg_bits > 8 || app_bits < msg_bits || app_bits > 16 || !(step >= 0x1p-20 && step <= 0x1p20))
-        throw std::runtime_error(who + "need msg_bits 0 (off) or 2..8, msg_bits <= app_bits <= 16 and 2^-20 <= step <= 2^20, got (" +
+        throw std::runtime_error(std::string(ms_info(MsVariant::kLayeredFixed).setter) +
+                                 ": need msg_bits 0 (off) or 2..8, msg_bits <= app_bits <= 16 and 2^-20 <= step <= 2^20, got (" +
                                  std::to_string(msg_bits) + ", " + std::to_string(app_bits) + ", " + std::to_string(step) + ")");
-    if (ms_schedule_ == 1)
-        throw std::runtime_error(who + "fixed-point layered min-sum does not combine with the (binary64) layered schedule "
-                                       "(ldpc_hip_set_min_sum_schedule(ctx, LDPC_HIP_MS_SCHEDULE_FLOODING) first)");
-    if (ms_bits_)
-        throw std::runtime_error(who + "fixed-point layered min-sum does not combine with quantized min-sum "
-                                       "(ldpc_hip_set_min_sum_quantization(ctx, 0, 0) first)");
-    if (ms_ternary_)
-        throw std::runtime_error(who + "fixed-point layered min-sum does not combine with ternary min-sum "
-                                       "(ldpc_hip_set_min_sum_ternary(ctx, 0) first)");
-    if (const std::string why = refusal(Decoder::kLayeredFixedMinSum); !why.empty())
-        throw std::runtime_error(who + why);
+    enter_ms_variant(MsVariant::kLayeredFixed);
     ms_lf_msg_bits_ = msg_bits, ms_lf_app_bits_ = app_bits, ms_lf_step_ = step;
 }
 
@@ -996,24 +954,24 @@ static void correction_lut(double scale, double offset, double inv, int qmax, ui
     }
 }
 
-// the quantizer (item 1: the step and fl(1 / step), computed here) and the correction table of one launch
-QmsArgs Engine::qms_args() const
+// the quantizer (item 1: the step and fl(1 / step), computed here), the largest message magnitude and the correction table
+// of one launch: what the arguments of the two fixed-point modes share (ldpc_hip_set_min_sum_layered_fixed, items 1 and 3)
+template <class Args>
+static Args quantizer_args(double step, int msg_bits, double scale, double offset)
 {
-    QmsArgs q{};
-    q.step = ms_step_, q.inv = 1.0 / ms_step_;
-    q.qmax = (1 << (ms_bits_ - 1)) - 1;
-    correction_lut(ms_scale, ms_offset, q.inv, q.qmax, q.lut);
+    Args q{};
+    q.step = step, q.inv = 1.0 / step;
+    q.qmax = (1 << (msg_bits - 1)) - 1;
+    correction_lut(scale, offset, q.inv, q.qmax, q.lut);
     return q;
 }
 
-// ... and of fixed-point layered min-sum: the same quantizer and table (ldpc_hip_set_min_sum_layered_fixed, items 1 and 3)
+QmsArgs Engine::qms_args() const { return quantizer_args<QmsArgs>(ms_step_, ms_bits_, ms_scale, ms_offset); }
+
 LayeredFixedArgs Engine::layered_fixed_args() const
 {
-    LayeredFixedArgs q{};
-    q.step = ms_lf_step_, q.inv = 1.0 / ms_lf_step_;
-    q.qmax = (1 << (ms_lf_msg_bits_ - 1)) - 1;
+    LayeredFixedArgs q = quantizer_args<LayeredFixedArgs>(ms_lf_step_, ms_lf_msg_bits_, ms_scale, ms_offset);
     q.pmax = (1 << (ms_lf_app_bits_ - 1)) - 1;
-    correction_lut(ms_scale, ms_offset, q.inv, q.qmax, q.lut);
     return q;
 }
 
@@ -1467,7 +1425,19 @@ void Engine::decode_typed(const DecParams &p, uint64_t n, const void *llr_in, in
     const uint64_t words = (nc + 31) / 32;    // ... and the packed decisions in words per frame
     TypedIo io;
     io.type = type;
-    io.step = decoder(p) == Decoder::kQuantizedMinSum ? ms_step_ : ms_lf_step_;
+    switch (ms_variant_) // the step an int8 counts: the fixed-point variant's in force (typed_refusal takes int8 for those alone)
+    {
+    case MsVariant::kQuantized:
+        io.step = ms_step_;
+        break;
+    case MsVariant::kLayeredFixed:
+        io.step = ms_lf_step_;
+        break;
+    case MsVariant::kFlooding:
+    case MsVariant::kLayered:
+    case MsVariant::kTernary:
+        break;
+    }
     for (uint64_t done = 0; done < n; done += sub)
     {
         const uint64_t m = std::min(sub, n - done);

@@ -84,16 +84,32 @@ struct StageSeq
 // One value per batch: Engine::stages names its launches from it, run_decode switches on it, Engine::refusal says whether
 // that decoder takes the code.
 enum class Decoder : int { kResident, kFast32, kLayered32, kLayered16, kLayeredMinSum, kQuantizedMinSum, kTernary, kLayeredFixedMinSum };
-// min-sum follows its schedule, quantization, ternary weight and fixed-point layered width (the setters let at most one of
-// the four be in force) and ignores the fast mode; sum-product follows the fast mode alone
-constexpr Decoder choose_decoder(bool min_sum, int fast_mode, int ms_schedule, int ms_bits, int ms_ternary, int ms_layered_fixed)
+// The variant of "BP_MS" decoding the caller switched on: at most one is in force (Engine::enter_ms_variant is where the
+// setters agree on that), kFlooding = none of them, the resident decoder
+enum class MsVariant : int { kFlooding, kLayered, kQuantized, kTernary, kLayeredFixed };
+// One row per variant, in the enum's order: the decoder it selects, and what the setters' messages call it — its setter, the
+// noun when it is what the caller asked for, the noun when it stands in another's way, and how to switch it off first
+struct MsVariantInfo
+{
+    Decoder decoder;
+    const char *setter, *subject, *obstacle, *off_first;
+};
+inline constexpr MsVariantInfo kMsVariants[] = {
+    {Decoder::kResident, "", "", "", ""},
+    {Decoder::kLayeredMinSum, "ldpc_hip_set_min_sum_schedule", "the layered schedule", "the layered schedule",
+     "ldpc_hip_set_min_sum_schedule(ctx, LDPC_HIP_MS_SCHEDULE_FLOODING)"},
+    {Decoder::kQuantizedMinSum, "ldpc_hip_set_min_sum_quantization", "quantized min-sum", "quantized min-sum",
+     "ldpc_hip_set_min_sum_quantization(ctx, 0, 0)"},
+    {Decoder::kTernary, "ldpc_hip_set_min_sum_ternary", "ternary min-sum", "ternary min-sum", "ldpc_hip_set_min_sum_ternary(ctx, 0)"},
+    {Decoder::kLayeredFixedMinSum, "ldpc_hip_set_min_sum_layered_fixed", "fixed-point layered min-sum", "fixed-point layered min-sum",
+     "ldpc_hip_set_min_sum_layered_fixed(ctx, 0, 0, 0)"},
+};
+constexpr const MsVariantInfo &ms_info(MsVariant v) { return kMsVariants[static_cast<int>(v)]; }
+// min-sum follows its variant and ignores the fast mode; sum-product follows the fast mode alone
+constexpr Decoder choose_decoder(bool min_sum, int fast_mode, MsVariant ms_variant)
 {
     if (min_sum)
-        return ms_schedule == 1    ? Decoder::kLayeredMinSum
-               : ms_bits           ? Decoder::kQuantizedMinSum
-               : ms_ternary        ? Decoder::kTernary
-               : ms_layered_fixed  ? Decoder::kLayeredFixedMinSum
-                                   : Decoder::kResident;
+        return ms_info(ms_variant).decoder;
     return fast_mode == 1 ? Decoder::kFast32 : fast_mode == 2 ? Decoder::kLayered32 : fast_mode == 3 ? Decoder::kLayered16 : Decoder::kResident;
 }
 
@@ -265,7 +281,7 @@ class Engine
     const FusedPlan &fused_plan() const { return fused_plan_; }
     Residency residency() const { return residency_; }
     // the decoder and the launches a batch with these parameters takes (host only)
-    Decoder decoder(const DecParams &p) const { return choose_decoder(p.min_sum, fast_mode, ms_schedule_, ms_bits_, ms_ternary_, ms_lf_msg_bits_); }
+    Decoder decoder(const DecParams &p) const { return choose_decoder(p.min_sum, fast_mode, ms_variant_); }
     StageSeq stages(const DecParams &p) const
     {
         return decode_stages({.residency = residency_, .decoder = decoder(p), .shared6 = shared6_,
@@ -286,32 +302,29 @@ class Engine
     // corrected min-sum of BP_MS decoding (include/ldpc_amd.h, ldpc_hip_set_min_sum_correction), NON-PARITY unless (1, 0):
     // check-node output magnitudes max(fl(fl(ms_scale * m) - ms_offset), +0.0) (device_cn.hpp, MsCorr); read at every decode
     double ms_scale = 1.0, ms_offset = 0.0;
-    // schedule (0 flooding, 1 layered) and quantization (bits 0 = off, 2..8, with LLR step) of BP_MS decoding, NON-PARITY
-    // (include/ldpc_amd.h, ldpc_hip_set_min_sum_schedule / _quantization), and the channel weight of ternary min-sum (0 = off,
-    // 1..7; ldpc_hip_set_min_sum_ternary).  The three and set_ms_layered_fixed exclude each other.  Host only; each setter
-    // throws, leaving the setting as it is, for invalid values, another of the four in force, or a code refusal() names
+    // The variants of BP_MS decoding, NON-PARITY (include/ldpc_amd.h): the schedule (0 flooding, 1 layered;
+    // ldpc_hip_set_min_sum_schedule), quantization (bits 0 = off, 2..8, with LLR step; _quantization), ternary min-sum with its
+    // channel weight (0 = off, 1..7; _ternary) and fixed-point layered min-sum (msg_bits 0 = off, 2..8 with msg_bits <= app_bits
+    // <= 16 and the LLR step; _layered_fixed).  The four exclude each other.  Host only; each setter throws, leaving everything
+    // as it is, for invalid values, another of the four in force, or a code refusal() names; "off" is always taken and
+    // clears that variant alone.  A variant remembers its other parameters when it goes off: the getters report them
     void set_ms_schedule(int schedule);
     void set_ms_quantization(int bits, double step);
     void set_ms_ternary(int weight);
-    // fixed-point layered min-sum (include/ldpc_amd.h, ldpc_hip_set_min_sum_layered_fixed): msg_bits 0 = off, 2..8 with
-    // msg_bits <= app_bits <= 16 and the LLR step; the fourth of the kind, under the same rules as the three above
     void set_ms_layered_fixed(int msg_bits, int app_bits, double step);
-    int ms_lf_msg_bits() const { return ms_lf_msg_bits_; }
+    int ms_schedule() const { return ms_variant_ == MsVariant::kLayered; }
+    int ms_bits() const { return ms_variant_ == MsVariant::kQuantized ? ms_bits_ : 0; }
+    double ms_step() const { return ms_step_; }
+    int ms_ternary() const { return ms_variant_ == MsVariant::kTernary ? ms_ternary_ : 0; }
+    int ms_lf_msg_bits() const { return ms_variant_ == MsVariant::kLayeredFixed ? ms_lf_msg_bits_ : 0; }
     int ms_lf_app_bits() const { return ms_lf_app_bits_; }
     double ms_lf_step() const { return ms_lf_step_; }
-    int ms_ternary() const { return ms_ternary_; }
-    int ms_schedule() const { return ms_schedule_; }
-    int ms_bits() const { return ms_bits_; }
-    double ms_step() const { return ms_step_; }
-    // host only: LDS bytes of one frame (plan.hpp, layered_ms_region_bytes / qms_region_bytes), -1 where the plan does not
-    // take the code (a frame beyond the LDS of a CU still gets its byte count: refusal() judges it)
-    int64_t layered_ms_lds_bytes();
-    int64_t qms_lds_bytes();
-    int64_t layered_fixed_lds_bytes(); // (plan.hpp, layered_fixed_region_bytes)
+    // host only: LDS bytes of one frame of a min-sum variant's decoder (plan.hpp, layered_ms_region_bytes / qms_region_bytes /
+    // layered_fixed_region_bytes; ternary: of one 32-frame group with llr_out wanted, ternary_lds_bytes), -1 where its plan or
+    // the kernel's tables do not take the code (a frame beyond the LDS of a CU still gets its byte count: refusal() judges it)
+    int64_t lds_bytes(Decoder d);
+    int64_t lds_bytes_if_taken(Decoder d) { return refusal(d).empty() ? lds_bytes(d) : -1; } // ... -1 for every code refusal() names
     int64_t layered_fixed_direct_lds_bytes(); // (plan.hpp, layered_fixed_direct_region_bytes: typed LLRs, nothing staged)
-    // host only: LDS bytes of one 32-frame group of ternary min-sum with llr_out wanted (plan.hpp, ternary_lds_bytes), -1 for a
-    // code outside what the kernel's tables hold (refusal() says which limit)
-    int64_t ternary_group_lds_bytes() const;
     // host only, built at the first call, once per engine
     const LayerPlan &layer_plan();
     const QmsPlan &qms_plan();
@@ -384,6 +397,9 @@ class Engine
     // the device halves of layer_plan() and qms_plan(): at the first launch that needs them
     void upload_layer_plan();
     void upload_qms_plan();
+    // after a setter has checked its own arguments: throws if another variant is in force or the code is refused, else v is in force
+    void enter_ms_variant(MsVariant v);
+    void leave_ms_variant(MsVariant v) { ms_variant_ = ms_variant_ == v ? MsVariant::kFlooding : ms_variant_; }
     QmsArgs qms_args() const; // the quantizer and the correction table of the settings in force
     LayeredFixedArgs layered_fixed_args() const; // ... and those of fixed-point layered min-sum
     bool register_resident() const { return residency_ == Residency::kRegTotals || residency_ == Residency::kRegMessages; }
@@ -452,7 +468,8 @@ class Engine
     int lds_llr_mode_ = 0;     // LDS-resident: the input LLRs in LDS (0) or in registers (2), kernels.hpp launch_decode_lds
     uint32_t mem_occ_lds_ = 0; // memory-resident: the dummy LDS request that bounds the resident frames per CU
     DevFusedPlan dev_fused_{};
-    int ms_schedule_ = 0, ms_bits_ = 0, ms_ternary_ = 0;
+    MsVariant ms_variant_ = MsVariant::kFlooding;
+    int ms_bits_ = 0, ms_ternary_ = 0; // each variant's parameters as last set (they mean something while it is in force)
     double ms_step_ = 1.0;
     int ms_lf_msg_bits_ = 0, ms_lf_app_bits_ = 8;
     double ms_lf_step_ = 1.0;

@@ -28,6 +28,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <iostream>
 #include <mutex>
 #include <stdexcept>
@@ -100,6 +101,18 @@ std::vector<int> parse_devices(const std::string &spec)
     return out;
 }
 
+// One variant of BP_MS decoding on the command line: the flag that names it in a message and what a later variant's message
+// calls it, its noun, what its flags are told without --decoding BP_MS, why it refuses --ms-scale / --ms-offset (null: it
+// takes them), whether any of its flags was given, the check of their values (throws; true: the variant is on), its setter
+// and its line of the banner
+struct MsVariantFlags
+{
+    const char *flag, *as_other, *noun, *bp_ms_only, *uncorrected;
+    std::function<bool()> given, check;
+    std::function<int(ldpc_hip_ctx *)> apply;
+    std::function<void()> banner;
+};
+
 [[noreturn]] void fail(const std::string &msg)
 {
     std::cout << msg << std::endl << kUsage;
@@ -129,6 +142,75 @@ int main(int argc, char *argv[])
     std::string ms_lf_arg, ms_lf_step_arg; // fixed-point layered min-sum: Q,P,D as given (empty: not given) and its D
     int ms_lf_q = 0, ms_lf_p = 0;
     double ms_lf_step = 1.0;
+    // The variants of BP_MS decoding, of which at most one is given (include/ldpc_amd.h, ldpc_hip_set_min_sum_schedule /
+    // _quantization / _ternary / _layered_fixed; the comparisons are false for NaN), checked in this order: a later one
+    // names itself when two are given
+    const MsVariantFlags ms_variants[] = {
+        {"--ms-schedule", "--ms-schedule layered", "the layered schedule", "--ms-schedule: the schedule of min-sum, for --decoding BP_MS only",
+         nullptr, [&] { return !ms_schedule.empty(); },
+         [&] {
+             if (ms_schedule != "flooding" && ms_schedule != "layered")
+                 throw std::runtime_error("--ms-schedule: flooding or layered");
+             return ms_schedule == "layered";
+         },
+         [&](ldpc_hip_ctx *ctx) { return ldpc_hip_set_min_sum_schedule(ctx, LDPC_HIP_MS_SCHEDULE_LAYERED); },
+         [&] { std::cout << " Min-Sum Schedule: layered (row-serial sweeps; the reference's is flooding), NON-PARITY\n"; }},
+        {"--ms-bits", "--ms-bits", "quantized min-sum", "--ms-bits / --ms-step: quantized min-sum, for --decoding BP_MS only", nullptr,
+         [&] { return !ms_bits_arg.empty() || !ms_step_arg.empty(); },
+         [&] {
+             if (ms_bits_arg.empty())
+                 throw std::runtime_error("--ms-step: the step of quantized min-sum, with --ms-bits only");
+             if (ms_bits < 2 || ms_bits > 8)
+                 throw std::runtime_error("--ms-bits: need 2 <= Q <= 8");
+             if (!(ms_step >= 0x1p-20 && ms_step <= 0x1p20))
+                 throw std::runtime_error("--ms-step: need 2^-20 <= D <= 2^20");
+             return true;
+         },
+         [&](ldpc_hip_ctx *ctx) { return ldpc_hip_set_min_sum_quantization(ctx, ms_bits, ms_step); },
+         [&] {
+             std::cout << " Min-Sum Quantization: " << ms_bits << " bits, step " << (ms_step_arg.empty() ? "1" : ms_step_arg)
+                       << " (saturating fixed-point messages), NON-PARITY\n";
+         }},
+        {"--ms-ternary", "--ms-ternary", "ternary min-sum", "--ms-ternary: ternary min-sum, for --decoding BP_MS only",
+         "has no magnitude to correct", [&] { return !ms_ternary_arg.empty(); },
+         [&] {
+             if (ms_ternary < 1 || ms_ternary > 7)
+                 throw std::runtime_error("--ms-ternary: need 1 <= W <= 7");
+             return true;
+         },
+         [&](ldpc_hip_ctx *ctx) { return ldpc_hip_set_min_sum_ternary(ctx, ms_ternary); },
+         [&] { std::cout << " Min-Sum Ternary: weight " << ms_ternary << " (Gallager E: messages -1, 0, +1), NON-PARITY\n"; }},
+        {"--ms-layered-fixed", "--ms-layered-fixed", "fixed-point layered min-sum",
+         "--ms-layered-fixed: fixed-point layered min-sum, for --decoding BP_MS only", nullptr, [&] { return !ms_lf_arg.empty(); },
+         [&] {
+             const size_t c1 = ms_lf_arg.find(','), c2 = c1 == std::string::npos ? c1 : ms_lf_arg.find(',', c1 + 1);
+             if (c2 == std::string::npos || ms_lf_arg.find(',', c2 + 1) != std::string::npos)
+                 throw std::runtime_error("--ms-layered-fixed: expected Q,P,D such as 6,8,0.25");
+             try
+             {
+                 ms_lf_q = std::stoi(ms_lf_arg.substr(0, c1));
+                 ms_lf_p = std::stoi(ms_lf_arg.substr(c1 + 1, c2 - c1 - 1));
+                 ms_lf_step = std::stod(ms_lf_step_arg = ms_lf_arg.substr(c2 + 1));
+             }
+             catch (const std::exception &)
+             {
+                 throw std::runtime_error("--ms-layered-fixed: expected Q,P,D such as 6,8,0.25");
+             }
+             if (ms_lf_q < 2 || ms_lf_q > 8)
+                 throw std::runtime_error("--ms-layered-fixed: need 2 <= Q <= 8");
+             if (ms_lf_p < ms_lf_q || ms_lf_p > 16)
+                 throw std::runtime_error("--ms-layered-fixed: need Q <= P <= 16");
+             if (!(ms_lf_step >= 0x1p-20 && ms_lf_step <= 0x1p20))
+                 throw std::runtime_error("--ms-layered-fixed: need 2^-20 <= D <= 2^20");
+             return true;
+         },
+         [&](ldpc_hip_ctx *ctx) { return ldpc_hip_set_min_sum_layered_fixed(ctx, ms_lf_q, ms_lf_p, ms_lf_step); },
+         [&] {
+             std::cout << " Min-Sum Layered Fixed-Point: " << ms_lf_q << "-bit messages, " << ms_lf_p << "-bit totals, step "
+                       << ms_lf_step_arg << ", NON-PARITY\n";
+         }},
+    };
+    const MsVariantFlags *ms_variant = nullptr; // the one in force
     try
     {
         for (int i = 1; i < argc; ++i)
@@ -207,71 +289,21 @@ int main(int argc, char *argv[])
             if (!(ms_offset >= 0.0 && ms_offset <= 1e6))
                 throw std::runtime_error("--ms-offset: need 0 <= B <= 1e6");
         }
-        if (!ms_schedule.empty())
+        const bool corrected = !ms_scale_arg.empty() || !ms_offset_arg.empty();
+        for (const MsVariantFlags &v : ms_variants)
         {
+            if (!v.given())
+                continue;
             if (decoding != "BP_MS")
-                throw std::runtime_error("--ms-schedule: the schedule of min-sum, for --decoding BP_MS only");
-            if (ms_schedule != "flooding" && ms_schedule != "layered")
-                throw std::runtime_error("--ms-schedule: flooding or layered");
-        }
-        if (!ms_bits_arg.empty() || !ms_step_arg.empty())
-        {
-            if (decoding != "BP_MS")
-                throw std::runtime_error("--ms-bits / --ms-step: quantized min-sum, for --decoding BP_MS only");
-            if (ms_bits_arg.empty())
-                throw std::runtime_error("--ms-step: the step of quantized min-sum, with --ms-bits only");
-            // (include/ldpc_amd.h, ldpc_hip_set_min_sum_quantization; the comparisons are false for NaN)
-            if (ms_bits < 2 || ms_bits > 8)
-                throw std::runtime_error("--ms-bits: need 2 <= Q <= 8");
-            if (!(ms_step >= 0x1p-20 && ms_step <= 0x1p20))
-                throw std::runtime_error("--ms-step: need 2^-20 <= D <= 2^20");
-            if (ms_schedule == "layered")
-                throw std::runtime_error("--ms-bits: quantized min-sum does not combine with --ms-schedule layered");
-        }
-        if (!ms_ternary_arg.empty())
-        {
-            if (decoding != "BP_MS")
-                throw std::runtime_error("--ms-ternary: ternary min-sum, for --decoding BP_MS only");
-            // (include/ldpc_amd.h, ldpc_hip_set_min_sum_ternary)
-            if (ms_ternary < 1 || ms_ternary > 7)
-                throw std::runtime_error("--ms-ternary: need 1 <= W <= 7");
-            if (!ms_bits_arg.empty())
-                throw std::runtime_error("--ms-ternary: ternary min-sum does not combine with --ms-bits");
-            if (ms_schedule == "layered")
-                throw std::runtime_error("--ms-ternary: ternary min-sum does not combine with --ms-schedule layered");
-            if (!ms_scale_arg.empty() || !ms_offset_arg.empty())
-                throw std::runtime_error("--ms-ternary: ternary min-sum has no magnitude to correct (--ms-scale / --ms-offset)");
-        }
-        if (!ms_lf_arg.empty())
-        {
-            if (decoding != "BP_MS")
-                throw std::runtime_error("--ms-layered-fixed: fixed-point layered min-sum, for --decoding BP_MS only");
-            const size_t c1 = ms_lf_arg.find(','), c2 = c1 == std::string::npos ? c1 : ms_lf_arg.find(',', c1 + 1);
-            if (c2 == std::string::npos || ms_lf_arg.find(',', c2 + 1) != std::string::npos)
-                throw std::runtime_error("--ms-layered-fixed: expected Q,P,D such as 6,8,0.25");
-            try
-            {
-                ms_lf_q = std::stoi(ms_lf_arg.substr(0, c1));
-                ms_lf_p = std::stoi(ms_lf_arg.substr(c1 + 1, c2 - c1 - 1));
-                ms_lf_step = std::stod(ms_lf_step_arg = ms_lf_arg.substr(c2 + 1));
-            }
-            catch (const std::exception &)
-            {
-                throw std::runtime_error("--ms-layered-fixed: expected Q,P,D such as 6,8,0.25");
-            }
-            // (include/ldpc_amd.h, ldpc_hip_set_min_sum_layered_fixed; the comparisons are false for NaN)
-            if (ms_lf_q < 2 || ms_lf_q > 8)
-                throw std::runtime_error("--ms-layered-fixed: need 2 <= Q <= 8");
-            if (ms_lf_p < ms_lf_q || ms_lf_p > 16)
-                throw std::runtime_error("--ms-layered-fixed: need Q <= P <= 16");
-            if (!(ms_lf_step >= 0x1p-20 && ms_lf_step <= 0x1p20))
-                throw std::runtime_error("--ms-layered-fixed: need 2^-20 <= D <= 2^20");
-            if (!ms_bits_arg.empty())
-                throw std::runtime_error("--ms-layered-fixed: fixed-point layered min-sum does not combine with --ms-bits");
-            if (ms_schedule == "layered")
-                throw std::runtime_error("--ms-layered-fixed: fixed-point layered min-sum does not combine with --ms-schedule layered");
-            if (!ms_ternary_arg.empty())
-                throw std::runtime_error("--ms-layered-fixed: fixed-point layered min-sum does not combine with --ms-ternary");
+                throw std::runtime_error(v.bp_ms_only);
+            if (!v.check())
+                continue;
+            const std::string who = std::string(v.flag) + ": " + v.noun;
+            if (ms_variant)
+                throw std::runtime_error(who + " does not combine with " + ms_variant->as_other);
+            if (v.uncorrected && corrected)
+                throw std::runtime_error(who + " " + v.uncorrected + " (--ms-scale / --ms-offset)");
+            ms_variant = &v;
         }
     }
     catch (const std::exception &e)
@@ -417,25 +449,7 @@ int main(int argc, char *argv[])
         ldpc_hip_destroy(ctx);
         return reap(EXIT_FAILURE);
     }
-    if (ms_schedule == "layered" && ldpc_hip_set_min_sum_schedule(ctx, LDPC_HIP_MS_SCHEDULE_LAYERED) != 0)
-    {
-        std::cout << "Error: " << ldpc_hip_last_error() << std::endl;
-        ldpc_hip_destroy(ctx);
-        return reap(EXIT_FAILURE);
-    }
-    if (ms_bits && ldpc_hip_set_min_sum_quantization(ctx, ms_bits, ms_step) != 0)
-    {
-        std::cout << "Error: " << ldpc_hip_last_error() << std::endl;
-        ldpc_hip_destroy(ctx);
-        return reap(EXIT_FAILURE);
-    }
-    if (ms_ternary && ldpc_hip_set_min_sum_ternary(ctx, ms_ternary) != 0)
-    {
-        std::cout << "Error: " << ldpc_hip_last_error() << std::endl;
-        ldpc_hip_destroy(ctx);
-        return reap(EXIT_FAILURE);
-    }
-    if (ms_lf_q && ldpc_hip_set_min_sum_layered_fixed(ctx, ms_lf_q, ms_lf_p, ms_lf_step) != 0)
+    if (ms_variant && ms_variant->apply(ctx) != 0)
     {
         std::cout << "Error: " << ldpc_hip_last_error() << std::endl;
         ldpc_hip_destroy(ctx);
@@ -456,16 +470,8 @@ int main(int argc, char *argv[])
         std::cout << " Min-Sum Correction: scale " << (ms_scale_arg.empty() ? "1" : ms_scale_arg) << ", offset "
                   << (ms_offset_arg.empty() ? "0" : ms_offset_arg)
                   << " (c2v magnitude max(scale * min - offset, 0)), NON-PARITY\n";
-    if (ms_schedule == "layered")
-        std::cout << " Min-Sum Schedule: layered (row-serial sweeps; the reference's is flooding), NON-PARITY\n";
-    if (ms_bits)
-        std::cout << " Min-Sum Quantization: " << ms_bits << " bits, step " << (ms_step_arg.empty() ? "1" : ms_step_arg)
-                  << " (saturating fixed-point messages), NON-PARITY\n";
-    if (ms_ternary)
-        std::cout << " Min-Sum Ternary: weight " << ms_ternary << " (Gallager E: messages -1, 0, +1), NON-PARITY\n";
-    if (ms_lf_q)
-        std::cout << " Min-Sum Layered Fixed-Point: " << ms_lf_q << "-bit messages, " << ms_lf_p << "-bit totals, step " << ms_lf_step_arg
-                  << ", NON-PARITY\n";
+    if (ms_variant)
+        ms_variant->banner();
     std::cout << "== Channel Parameters\n";
     std::cout << " Type: " << channel << "\n Seed: " << seed << "\n Range: Min: " << range[0] << ", Max: " << range[1]
               << ", Step: " << range[2] << "\n";

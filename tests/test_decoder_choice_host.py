@@ -3,8 +3,9 @@ launch stages that follow from it, without a GPU, over every combination of the 
 
 tests/golden/decode_stages.json holds the stage lists that the library reported for the same combinations before the choice
 became one enum (recorded on the CPU from a build of that commit: HipDecoder.decode_stages under every combination below,
-keyed "fast<mode>/<variant>/<decoding>/<early|full>/<iterations>"): the stages are compared against that record, not only
-against the rule the test shares with the code."""
+keyed "fast<mode>/<variant>/<decoding>/<early|full>/<iterations>"; the keys of "ternary" and "layered-fixed" from a build of
+the commit before the variant in force became one value, tests/golden/make_min_sum_variants.py): the stages are compared
+against that record, not only against the rule the test shares with the code."""
 import itertools
 import json
 import os
@@ -13,8 +14,11 @@ import numpy as np
 import pytest
 
 import orc
+from minsum_common import EXCLUSIVE, VARIANTS as MS
 
-VARIANTS = ("flooding", "layered", "quantized")
+VARIANTS = ("flooding",) + tuple(EXCLUSIVE)
+# (ternary min-sum with weight 1, as the record was taken; its decoder does not take the 8k code: the setter refuses)
+ON = {**{k: MS[k].on for k in EXCLUSIVE}, "ternary": lambda d: d.set_min_sum_ternary(1)}
 COMBOS = list(itertools.product(range(4), VARIANTS, ("BP", "BP_MS"), (True, False), (50, 0)))
 
 
@@ -31,18 +35,25 @@ def recorded():
     return json.load(open(os.path.join(os.path.dirname(__file__), "golden", "decode_stages.json")))
 
 
-def _rule(fast, variant, dec):
+def _rule(fast, variant, dec, taken):
     if dec == "BP_MS":  # min-sum ignores the fast mode
-        return {"flooding": "resident", "layered": "layered-min-sum", "quantized": "quantized-min-sum"}[variant]
+        return MS[variant].choice if variant != "flooding" and taken else "resident"
     return ("resident", "fast32", "layered32", "layered16")[fast]  # sum-product ignores the min-sum settings
 
 
-def _set(d, fast, variant):
+def _set(d, fast, variant, refused=False):
+    """The fast mode and at most one min-sum variant; False if the variant's setter refuses the code (nothing is then on)."""
     d.set_fast_mode(fast)
-    d.set_min_sum_quantization(0)
-    d.set_min_sum_schedule("layered" if variant == "layered" else "flooding")
-    if variant == "quantized":
-        d.set_min_sum_quantization(6, 0.25)
+    for k in EXCLUSIVE:
+        MS[k].off(d)
+    if variant == "flooding":
+        return True
+    if refused:
+        with pytest.raises(RuntimeError, match=MS[variant].setter):
+            ON[variant](d)
+        return False
+    ON[variant](d)
+    return True
 
 
 @pytest.mark.parametrize("name", ["h.txt", "h8k"])
@@ -54,9 +65,9 @@ def test_choice_and_stages(lib, recorded, h8k_file, name):
     assert len(recorded[name]) == len(COMBOS)
     for fast, variant, dec, early, it in COMBOS:
         what = (name, fast, variant, dec, early, it)
-        _set(d, fast, variant)
+        taken = _set(d, fast, variant, refused=(name, variant) == ("h8k", "ternary"))
         choice = d.decoder_choice(early, it, dec)
-        assert choice == _rule(fast, variant, dec), what
+        assert choice == _rule(fast, variant, dec, taken), what
         stages = d.decode_stages(early, it, dec)
         assert stages == recorded[name][f"fast{fast}/{variant}/{dec}/{'early' if early else 'full'}/{it}"], what
         if choice != "resident" or off[(dec, early, it)] == ["whole"]:

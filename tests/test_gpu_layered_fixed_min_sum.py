@@ -1,19 +1,16 @@
 """Fixed-point layered min-sum on the GPU (include/ldpc_amd.h, ldpc_hip_set_min_sum_layered_fixed;
 kernels_layered_fixed.hip) against the numpy mirror (tests/layered_fixed_minsum_ref.py), bit for bit: iters, hard, bit_errors,
 and llr_out as uint64.  Then the fused channel paths, the paths that must not move, the simulation loop and the CLI."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import orc
 from layered_fixed_minsum_ref import LayeredFixedMinSumMirror
-from minsum_common import WANT, against_mirror, check_no_iteration, check_split_batch, dumped, same
+from minsum_common import (VARIANTS, WANT, against_mirror, check_fused_channel, check_no_iteration, check_nothing_else_moves,
+                           check_simulation_and_cli, check_split_batch, dumped, same)
 from test_gpu_layered_min_sum import irregular_code
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # (msg_bits, app_bits, step, scale, offset)
 H_SETTINGS = [(6, 8, 0.25, 1.0, 0.0), (6, 8, 0.25, 0.8125, 0.0), (6, 6, 0.25, 0.8125, 0.0), (5, 7, 0.5, 0.75, 0.5),
               (4, 6, 1.0, 1.0, 0.0), (2, 2, 2.0, 1.0, 0.0), (8, 16, 0.0625, 0.8125, 0.1)]
@@ -138,16 +135,7 @@ def test_fused_channel_equals_decode_of_its_llrs():
     d = libldpc_amd.HipDecoder(orc.H_TXT)
     d.set_min_sum_layered_fixed(5, 7, 0.5)
     d.set_min_sum_correction(0.8125, 0.25)
-    for noise in ("reference", "counter"):
-        d.set_noise(noise)
-        for ch, x in (("AWGN", -5.0), ("BSC", 0.2)):
-            for early in (True, False):
-                d.stream_begin(ch, 6, x)
-                r = d.stream_decode(64, early_term=early, iterations=30, decoding="BP_MS", want=WANT + ("llr_in",))
-                b = d.decode_batch(r["llr_in"], early_term=early, iterations=30, decoding="BP_MS", want=WANT)
-                same(b, r, (noise, ch, x, early))
-                assert r["iters"].max() > 0
-    d.set_noise("reference")
+    r = check_fused_channel(d)
     # ... and it is the fixed-point layered decoder that ran: the mirror on the last frames
     mir = LayeredFixedMinSumMirror(orc.Code(orc.H_TXT))
     m = mir.decode(r["llr_in"][:8], 5, 7, 0.5, 0.8125, 0.25, early_term=False, iterations=30)
@@ -166,57 +154,7 @@ def test_fused_channel_equals_decode_of_its_llrs():
 def test_nothing_else_moves():
     """With the mode on, BP (AWGN, BSC) and BEC outputs equal a fresh context's; with it off again, BP_MS — flooding,
     layered binary64 and quantized — equals a fresh context's."""
-    import libldpc_amd
-    want = ("iters", "hard", "llr_out", "bit_errors", "llr_in")
-    lf = libldpc_amd.HipDecoder(orc.H_TXT, orc.G_TXT)
-    fresh = libldpc_amd.HipDecoder(orc.H_TXT, orc.G_TXT)
-    lf.set_min_sum_layered_fixed(6, 8, 0.25)
-    for ch, x, dec, early in (("AWGN", -4.0, "BP", True), ("AWGN", -4.0, "BP", False), ("BSC", 0.24, "BP", True),
-                              ("BEC", 0.7, "BP", True), ("BEC", 0.7, "BP_MS", True)):
-        rs = []
-        for d in (lf, fresh):
-            d.stream_begin(ch, 2, x)
-            rs.append(d.stream_decode(64, early_term=early, iterations=50, decoding=dec, want=want))
-        for k in want:
-            assert np.array_equal(rs[0][k], rs[1][k]), (ch, dec, early, k)
-        if ch != "BEC":
-            a = lf.decode_batch(rs[1]["llr_in"], early_term=early, decoding=dec, want=WANT)
-            b = fresh.decode_batch(rs[1]["llr_in"], early_term=early, decoding=dec, want=WANT)
-            for k in WANT:
-                assert np.array_equal(a[k], b[k]), (ch, dec, k)
-    # the mode does change BP_MS ...
-    rs = []
-    for d in (lf, fresh):
-        d.stream_begin("AWGN", 4, -4.5)
-        rs.append(d.stream_decode(32, iterations=50, decoding="BP_MS", want=want))
-    assert np.array_equal(rs[0]["llr_in"], rs[1]["llr_in"])
-    assert not np.array_equal(rs[0]["llr_out"].view(np.uint64), rs[1]["llr_out"].view(np.uint64))
-    # ... and the other min-sum decoders are back when it is off: flooding, layered binary64, quantized
-    lf.set_min_sum_layered_fixed(0)
-    variants = ((lambda d: None, lambda d: None), (lambda d: d.set_min_sum_schedule("layered"), lambda d: d.set_min_sum_schedule("flooding")),
-                (lambda d: d.set_min_sum_quantization(6, 0.25), lambda d: d.set_min_sum_quantization(0)))
-    for on, off in variants:
-        for d in (lf, fresh):
-            on(d)
-        for early in (True, False):
-            rs = []
-            for d in (lf, fresh):
-                d.stream_begin("AWGN", 4, -4.5)
-                rs.append(d.stream_decode(32, early_term=early, iterations=50, decoding="BP_MS", want=want))
-            for k in want:
-                assert np.array_equal(rs[0][k], rs[1][k]), (early, k)
-        for d in (lf, fresh):
-            off(d)
-
-
-def _fold(d, x, frames, seed):
-    d.stream_begin("AWGN", seed, x)
-    r = d.stream_decode(frames, early_term=True, iterations=50, decoding="BP_MS", want=("iters", "bit_errors"))
-    return frames, int((r["bit_errors"] > 0).sum()), int(r["bit_errors"].sum()), int(r["iters"].sum())
-
-
-def _file_rows(path):
-    return [ln.split()[:5] for ln in open(path).read().splitlines()]
+    check_nothing_else_moves(VARIANTS["layered-fixed"])
 
 
 def test_simulation_and_cli(tmp_path):
@@ -224,40 +162,4 @@ def test_simulation_and_cli(tmp_path):
     CLI with --ms-layered-fixed 6,8,0.25 --noise counter writes the same result file as the Python run, alone and as two
     ranks over shared memory; the flag is refused with BP, with each of the other three variants' flags and with 6,5,0.25."""
     import libldpc_amd
-    d = libldpc_amd.HipDecoder(orc.H_TXT)
-    d.set_noise("counter")
-    d.set_min_sum_layered_fixed(6, 8, 0.25)
-    frames, xr, seed = 6000, (-4.5, -3.5, 0.5), 5
-    py_file = str(tmp_path / "py.txt")
-    res = d.simulate("AWGN", xr, seed=seed, decoding="BP_MS", max_frames=frames, fec=10**9, result_file=py_file,
-                     cli_output=True)  # (the result file is written with the console table)
-    assert res["totals"].shape == (2, 4)
-    for i, x in enumerate((-4.5, -4.0)):
-        n, fe, be, it = _fold(d, x, frames, seed)
-        assert res["totals"][i].tolist() == [n, fe, be, it], (x, res["totals"][i], (n, fe, be, it))
-        assert 0 < fe < n
-    exe = os.path.join(ROOT, "libldpc_amd", "ldpcsim")
-    head = [exe, orc.H_TXT]
-    tail = ["-4.5", "-3.5", "0.5", "-s", str(seed), "--decoding", "BP_MS", "--max-frames", str(frames),
-            "--frame-error-count", str(10**9), "--noise", "counter"]
-    flags = ["--ms-layered-fixed", "6,8,0.25"]
-    one, two = str(tmp_path / "one.txt"), str(tmp_path / "two.txt")
-    p = subprocess.run(head + [one] + tail + flags, stdout=subprocess.PIPE, text=True, timeout=120, check=True)
-    assert " Min-Sum Layered Fixed-Point: 6-bit messages, 8-bit totals, step 0.25, NON-PARITY" in p.stdout
-    subprocess.run(head + [two] + tail + flags + ["--devices", "0,0", "--comm", "shm"], stdout=subprocess.PIPE, text=True,
-                   timeout=120, check=True)
-    assert _file_rows(one) == _file_rows(py_file) == _file_rows(two)
-    # without the flag: binary64 min-sum, another file and no such line
-    plain = str(tmp_path / "plain.txt")
-    p = subprocess.run(head + [plain] + tail, stdout=subprocess.PIPE, text=True, timeout=120, check=True)
-    assert "Min-Sum Layered Fixed-Point" not in p.stdout and _file_rows(plain) != _file_rows(one)
-    # BP_MS only; not with the other variants; P >= Q
-    other = str(tmp_path / "other.txt")
-    p = subprocess.run(head + [other] + tail[:5] + flags, stdout=subprocess.PIPE, text=True, timeout=120)
-    assert p.returncode != 0 and "--ms-layered-fixed" in p.stdout
-    for extra in (["--ms-bits", "6"], ["--ms-schedule", "layered"], ["--ms-ternary", "2"]):
-        p = subprocess.run(head + [other] + tail + flags + extra, stdout=subprocess.PIPE, text=True, timeout=120)
-        assert p.returncode != 0 and "--ms-layered-fixed" in p.stdout and extra[0] in p.stdout, extra
-    p = subprocess.run(head + [other] + tail + ["--ms-layered-fixed", "6,5,0.25"], stdout=subprocess.PIPE, text=True, timeout=120)
-    assert p.returncode != 0 and "--ms-layered-fixed" in p.stdout
-    assert not os.path.exists(other)
+    check_simulation_and_cli(VARIANTS["layered-fixed"], libldpc_amd.HipDecoder(orc.H_TXT), tmp_path)

@@ -3,13 +3,13 @@
 paths that must not move, the simulation loop and the CLI."""
 import importlib.util
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import orc
-from minsum_common import WANT, check_no_iteration, check_split_batch, dumped, same
+from minsum_common import (VARIANTS, WANT, check_fused_channel, check_no_iteration, check_nothing_else_moves, check_simulation_and_cli,
+                           check_split_batch, dumped, same)
 from ternary_ref import CASES, TernaryMirror, flipped_llrs
 from test_gpu_quantized_min_sum import wide_irregular_code
 
@@ -133,21 +133,16 @@ def test_fused_channel_equals_decode_of_its_llrs(cases):
     c = cases["r36"]
     d = c["d"]
     d.set_min_sum_ternary(1)
-    for noise in ("reference", "counter"):
-        d.set_noise(noise)
-        for ch, x in (("AWGN", 4.5), ("BSC", 0.04)):
-            for early in (True, False):
-                d.stream_begin(ch, 6, x)
-                r = d.stream_decode(N, early_term=early, iterations=30, decoding="BP_MS", want=WANT + ("llr_in",))
-                b = d.decode_batch(r["llr_in"], early_term=early, iterations=30, decoding="BP_MS", want=WANT)
-                same(b, r, (noise, ch, x, early))
-                assert r["iters"].max() > 0 and (r["iters"] < 30).any() == early
-                for want in (("iters", "bit_errors"), WANT):
-                    d.stream_begin(ch, 6, x)
-                    q = d.stream_decode(N, early_term=early, iterations=30, decoding="BP_MS", want=want)
-                    for k in want:
-                        assert np.array_equal(q[k], r[k]), (noise, ch, early, k)
-    d.set_noise("reference")
+
+    def each(r, noise, ch, x, early):
+        assert r["iters"].max() > 0 and (r["iters"] < 30).any() == early
+        for want in (("iters", "bit_errors"), WANT):
+            d.stream_begin(ch, 6, x)
+            q = d.stream_decode(N, early_term=early, iterations=30, decoding="BP_MS", want=want)
+            for k in want:
+                assert np.array_equal(q[k], r[k]), (noise, ch, early, k)
+
+    r = check_fused_channel(d, points=(("AWGN", 4.5), ("BSC", 0.04)), n=N, each=each)
     # ... and it is the ternary decoder that ran: the mirror on the last frames
     same({k: r[k] for k in WANT}, c["mir"].decode(r["llr_in"], 1, early_term=False, iterations=30), "mirror")
     _off(d)
@@ -164,55 +159,7 @@ def test_correction_has_no_effect(cases):
 def test_nothing_else_moves():
     """With the mode on, BP (AWGN, BSC) and BEC outputs equal a fresh context's; with it off again, BP_MS — flooding, layered
     and quantized — equals a fresh context's."""
-    import libldpc_amd
-    want = ("iters", "hard", "llr_out", "bit_errors", "llr_in")
-    ter = libldpc_amd.HipDecoder(orc.H_TXT, orc.G_TXT)
-    fresh = libldpc_amd.HipDecoder(orc.H_TXT, orc.G_TXT)
-    ter.set_min_sum_ternary(2)
-    for ch, x, dec, early in (("AWGN", -4.0, "BP", True), ("AWGN", -4.0, "BP", False), ("BSC", 0.24, "BP", True),
-                              ("BEC", 0.7, "BP", True), ("BEC", 0.7, "BP_MS", True)):
-        rs = []
-        for d in (ter, fresh):
-            d.stream_begin(ch, 2, x)
-            rs.append(d.stream_decode(64, early_term=early, iterations=50, decoding=dec, want=want))
-        for k in want:
-            assert np.array_equal(rs[0][k], rs[1][k]), (ch, dec, early, k)
-        if ch != "BEC":
-            a = ter.decode_batch(rs[1]["llr_in"], early_term=early, decoding=dec, want=WANT)
-            b = fresh.decode_batch(rs[1]["llr_in"], early_term=early, decoding=dec, want=WANT)
-            for k in WANT:
-                assert np.array_equal(a[k], b[k]), (ch, dec, k)
-    # the mode does change BP_MS ...
-    rs = []
-    for d in (ter, fresh):
-        d.stream_begin("AWGN", 4, -4.5)
-        rs.append(d.stream_decode(32, iterations=50, decoding="BP_MS", want=want))
-    assert np.array_equal(rs[0]["llr_in"], rs[1]["llr_in"])
-    assert not np.array_equal(rs[0]["llr_out"].view(np.uint64), rs[1]["llr_out"].view(np.uint64))
-    # ... and binary64 min-sum is back when it is off: flooding, layered, quantized
-    ter.set_min_sum_ternary(0)
-    variants = (lambda d: None, lambda d: d.set_min_sum_schedule("layered"),
-                lambda d: (d.set_min_sum_schedule("flooding"), d.set_min_sum_quantization(6, 0.25)))
-    for i, switch in enumerate(variants):
-        for d in (ter, fresh):
-            switch(d)
-        for early in (True, False):
-            rs = []
-            for d in (ter, fresh):
-                d.stream_begin("AWGN", 4, -4.5)
-                rs.append(d.stream_decode(32, early_term=early, iterations=50, decoding="BP_MS", want=want))
-            for k in want:
-                assert np.array_equal(rs[0][k], rs[1][k]), (i, early, k)
-
-
-def _fold(d, x, frames, seed):
-    d.stream_begin("BSC", seed, x)
-    r = d.stream_decode(frames, early_term=True, iterations=50, decoding="BP_MS", want=("iters", "bit_errors"))
-    return frames, int((r["bit_errors"] > 0).sum()), int(r["bit_errors"].sum()), int(r["iters"].sum())
-
-
-def _file_rows(path):
-    return [ln.split()[:5] for ln in open(path).read().splitlines()]
+    check_nothing_else_moves(VARIANTS["ternary"])
 
 
 def test_simulation_and_cli(cases, tmp_path):
@@ -220,38 +167,6 @@ def test_simulation_and_cli(cases, tmp_path):
     the CLI with --ms-ternary 1 --noise counter writes the same result file as the Python run, alone and as two ranks over
     shared memory; --ms-ternary is refused with BP, --ms-bits, --ms-schedule layered and --ms-scale."""
     c = cases["r36"]
-    d, code_file = c["d"], c["path"]
-    d.set_noise("counter")
-    d.set_min_sum_ternary(1)
-    frames, xr, seed = 6000, (0.03, 0.045, 0.01), 5
-    py_file = str(tmp_path / "py.txt")
-    res = d.simulate("BSC", xr, seed=seed, decoding="BP_MS", max_frames=frames, fec=10**9, result_file=py_file,
-                     cli_output=True)  # (the result file is written with the console table)
-    assert res["totals"].shape == (2, 4)
-    for i, x in enumerate((0.03 + 0.01, 0.03)):  # (the loop walks an eps axis from its far end, adding the step up from MIN)
-        n, fe, be, it = _fold(d, x, frames, seed)
-        assert res["totals"][i].tolist() == [n, fe, be, it], (x, res["totals"][i], (n, fe, be, it))
-        assert 0 < fe < n
-    d.set_noise("reference")
-    _off(d)
-    exe = os.path.join(ROOT, "libldpc_amd", "ldpcsim")
-    head = [exe, code_file]
-    tail = ["0.03", "0.045", "0.01", "-s", str(seed), "--decoding", "BP_MS", "--max-frames", str(frames),
-            "--frame-error-count", str(10**9), "--noise", "counter", "--channel", "BSC"]
-    flags = ["--ms-ternary", "1"]
-    one, two = str(tmp_path / "one.txt"), str(tmp_path / "two.txt")
-    p = subprocess.run(head + [one] + tail + flags, stdout=subprocess.PIPE, text=True, timeout=120, check=True)
-    assert "Min-Sum Ternary: weight 1" in p.stdout and "NON-PARITY" in p.stdout
-    subprocess.run(head + [two] + tail + flags + ["--devices", "0,0", "--comm", "shm"], stdout=subprocess.PIPE, text=True,
-                   timeout=120, check=True)
-    assert _file_rows(one) == _file_rows(py_file) == _file_rows(two)
-    # the four refused combinations: non-zero exit, no file
-    other = str(tmp_path / "other.txt")
-    for extra in (["--ms-bits", "6"], ["--ms-schedule", "layered"], ["--ms-scale", "0.75"], ["--ms-offset", "0.5"]):
-        p = subprocess.run(head + [other] + tail + flags + extra, stdout=subprocess.PIPE, text=True, timeout=120)
-        assert p.returncode != 0 and "--ms-ternary" in p.stdout, extra
-    p = subprocess.run(head + [other] + tail[:5] + flags, stdout=subprocess.PIPE, text=True, timeout=120)  # BP
-    assert p.returncode != 0 and "--ms-ternary" in p.stdout
-    p = subprocess.run(head + [other] + tail + ["--ms-ternary", "8"], stdout=subprocess.PIPE, text=True, timeout=120)
-    assert p.returncode != 0 and "--ms-ternary" in p.stdout
-    assert not os.path.exists(other)
+    check_simulation_and_cli(VARIANTS["ternary"], c["d"], tmp_path, c["path"])
+    c["d"].set_noise("reference")
+    _off(c["d"])

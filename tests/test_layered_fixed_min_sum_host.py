@@ -1,5 +1,5 @@
 """Fixed-point layered min-sum (include/ldpc_amd.h, ldpc_hip_set_min_sum_layered_fixed) without a GPU: the setter's validity
-check, the codes it takes, how it excludes the other three min-sum variants, the launch stages and decoder it reports, the
+check, the codes it takes and how the four min-sum variants exclude each other, the launch stages and decoder it reports, the
 LDS figure and the kernel's resources, and the numpy mirror (tests/layered_fixed_minsum_ref.py) by itself — its own
 properties and what the mode is for: how many total (APP) bits a code needs."""
 import itertools
@@ -9,7 +9,7 @@ import pytest
 
 import orc
 from layered_fixed_minsum_ref import LayeredFixedMinSumMirror
-from minsum_common import check_decode_stages, write
+from minsum_common import EXCLUSIVE, VARIANTS, check_decode_stages, write
 from quantized_minsum_ref import QuantizedMinSumMirror
 
 NAME = "ldpc_hip_set_min_sum_layered_fixed"
@@ -96,36 +96,41 @@ def test_codes_and_lds(lib, tmp_path, h8k_file):
     assert NAME.encode() in lib.ldpc_hip_last_error() and big.min_sum_layered_fixed[0] == 0
 
 
-VARIANTS = {
-    "layered": (lambda d: d.set_min_sum_schedule("layered"), lambda d: d.set_min_sum_schedule("flooding"),
-                lambda d: d.min_sum_schedule == "layered", "ldpc_hip_set_min_sum_schedule", "layered-min-sum"),
-    "quantized": (lambda d: d.set_min_sum_quantization(6, 0.25), lambda d: d.set_min_sum_quantization(0),
-                  lambda d: d.min_sum_quantization[0] == 6, "ldpc_hip_set_min_sum_quantization", "quantized-min-sum"),
-    "ternary": (lambda d: d.set_min_sum_ternary(2), lambda d: d.set_min_sum_ternary(0), lambda d: d.min_sum_ternary == 2,
-                "ldpc_hip_set_min_sum_ternary", "ternary"),
-    "fixed": (lambda d: d.set_min_sum_layered_fixed(6, 8, 0.25), lambda d: d.set_min_sum_layered_fixed(0),
-              lambda d: d.min_sum_layered_fixed == (6, 8, 0.25), NAME, "layered-fixed-min-sum"),
-}
+def _state(d):
+    return d.min_sum_schedule, d.min_sum_quantization[0], d.min_sum_ternary, d.min_sum_layered_fixed[0]
 
 
-@pytest.mark.parametrize("first,second", [p for p in itertools.permutations(VARIANTS, 2) if "fixed" in p])
+OFF = ("flooding", 0, 0, 0)
+PAIRS = list(itertools.permutations(EXCLUSIVE, 2))
+
+
+# (the ids this test had when it walked the pairs with the fixed-point mode alone: that mode is "fixed" in them)
+@pytest.mark.parametrize("first,second", PAIRS, ids=["-".join(p).replace("layered-fixed", "fixed") for p in PAIRS])
 def test_excludes_the_other_variants(lib, first, second):
-    """Each ordered pair of the new mode with layered, quantized and ternary: the second setter returns -1 naming itself,
-    both settings stay as they were, and once the first is off the second is taken."""
+    """Every ordered pair of the four variants (layered, quantized, ternary, fixed-point layered): with the first in force,
+    switching the second on returns -1 naming that setter and changes nothing; switching the first off lets the second in,
+    and then the first is refused."""
     import libldpc_amd
     d = libldpc_amd.HipDecoder(orc.H_TXT)
-    on1, off1, is1, _, choice1 = VARIANTS[first]
-    on2, off2, is2, name2, choice2 = VARIANTS[second]
-    on1(d)
-    with pytest.raises(RuntimeError, match=name2):
-        on2(d)
-    assert name2.encode() in lib.ldpc_hip_last_error()
-    assert is1(d) and not is2(d) and d.decoder_choice(decoding="BP_MS") == choice1
-    off2(d)  # switching off is always taken
-    assert is1(d)
-    off1(d)
-    on2(d)
-    assert is2(d) and not is1(d) and d.decoder_choice(decoding="BP_MS") == choice2
+    v1, v2 = VARIANTS[first], VARIANTS[second]
+    v1.on(d)
+    before = _state(d)
+    assert before != OFF and v1.state(d) and not v2.state(d) and d.decoder_choice(decoding="BP_MS") == v1.choice
+    with pytest.raises(RuntimeError, match=v2.setter):
+        v2.on(d)
+    assert v2.setter.encode() in lib.ldpc_hip_last_error()
+    assert _state(d) == before and v1.state(d) and not v2.state(d) and d.decoder_choice(decoding="BP_MS") == v1.choice
+    v2.off(d)  # switching off what is off is always taken
+    v1.on(d)   # and the setting in force may be set again
+    assert _state(d) == before and v1.state(d)
+    v1.off(d)
+    assert _state(d) == OFF and d.decoder_choice(decoding="BP_MS") == "resident"
+    v2.on(d)
+    assert _state(d) != before and _state(d) != OFF
+    assert v2.state(d) and not v1.state(d) and d.decoder_choice(decoding="BP_MS") == v2.choice
+    with pytest.raises(RuntimeError, match=v1.setter):
+        v1.on(d)
+    assert v1.setter.encode() in lib.ldpc_hip_last_error()
 
 
 def test_choice_stages_and_plan(lib, h8k_file):

@@ -1,7 +1,6 @@
-"""Ternary min-sum (include/ldpc_amd.h, ldpc_hip_set_min_sum_ternary) without a GPU: the setter and what it refuses, the
-exclusion between the layered schedule, quantization and the ternary mode, the decoder choice and launch stages it reports,
-and the numpy mirror (tests/ternary_ref.py) by itself — its symmetry, what it decodes, and h.txt, where it cannot start."""
-import itertools
+"""Ternary min-sum (include/ldpc_amd.h, ldpc_hip_set_min_sum_ternary) without a GPU: the setter and what it refuses (how it
+excludes the other variants: test_layered_fixed_min_sum_host.py), the decoder choice and launch stages it reports, and the
+numpy mirror (tests/ternary_ref.py) by itself — its symmetry, what it decodes, and h.txt, where it cannot start."""
 import os
 import sys
 
@@ -73,42 +72,6 @@ def test_setter_and_codes(lib, tmp_path, h8k_file):
         assert lib.ldpc_hip_set_min_sum_ternary(dd.ctx, 1) == -1 and len(lib.ldpc_hip_last_error()) > 0
         assert dd.min_sum_ternary == 0
         assert dd.decoder_choice(True, 50, "BP_MS") == "resident"
-
-
-SETTERS = {
-    "schedule": ("ldpc_hip_set_min_sum_schedule", lambda d: d.set_min_sum_schedule("layered"), lambda d: d.set_min_sum_schedule("flooding")),
-    "quantization": ("ldpc_hip_set_min_sum_quantization", lambda d: d.set_min_sum_quantization(6, 0.25), lambda d: d.set_min_sum_quantization(0)),
-    "ternary": ("ldpc_hip_set_min_sum_ternary", lambda d: d.set_min_sum_ternary(2), lambda d: d.set_min_sum_ternary(0)),
-}
-
-
-def _state(d):
-    return d.min_sum_schedule, d.min_sum_quantization[0], d.min_sum_ternary
-
-
-@pytest.mark.parametrize("first,second", list(itertools.permutations(SETTERS, 2)), ids="-then-".join)
-def test_the_three_exclude_each_other(lib, first, second):
-    """With one of the three in force, switching another on returns -1 naming that setter and changes nothing; switching
-    the first off lets the second in."""
-    import libldpc_amd
-    d = libldpc_amd.HipDecoder(orc.H_TXT)
-    _, on1, off1 = SETTERS[first]
-    name2, on2, off2 = SETTERS[second]
-    on1(d)
-    before = _state(d)
-    assert before != ("flooding", 0, 0)
-    with pytest.raises(RuntimeError, match=name2):
-        on2(d)
-    assert name2.encode() in lib.ldpc_hip_last_error()
-    assert _state(d) == before
-    off2(d)  # switching off what is off is always taken
-    on1(d)   # and the setting in force may be set again
-    assert _state(d) == before
-    off1(d)
-    on2(d)
-    assert _state(d) != before and _state(d) != ("flooding", 0, 0)
-    with pytest.raises(RuntimeError, match=SETTERS[first][0]):
-        on1(d)
 
 
 def test_choice_and_stages(lib, tmp_path):
