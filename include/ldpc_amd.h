@@ -392,6 +392,51 @@ int ldpc_hip_decode_batch_typed(ldpc_hip_ctx *ctx, decoder_param dec, uint64_t n
    binary64 channel LLRs.  tests/golden/h.txt: 6 528 bytes, 25 frames per CU. */
 int64_t ldpc_hip_layered_fixed_direct_lds_bytes(const ldpc_hip_ctx *ctx);
 
+/* Frames of bits that stay on the device: the transmit side of ldpc_hip_decode_batch_typed and its check,
+     ldpc_hip_encode_batch -> (the caller's modulation and channel) -> ldpc_hip_decode_batch_typed -> ldpc_hip_syndrome_batch,
+     ldpc_hip_bit_errors_batch
+   with packed words passing from one call to the next.  Pure GF(2): every output bit is determined.
+   Common rules.  Every buffer is device or host memory (host buffers are staged; inputs and results of up to 1 MB through
+   page-locked memory; device buffers are used in place).  An output pointer may be NULL = not wanted.  A row of L bits is
+     LDPC_HIP_BITS_U8        L bytes, a non-zero byte is 1 (as encode() reads its input); outputs are 0 / 1;
+     LDPC_HIP_BITS_PACKED32  ceil(L / 32) words, the layout of hard_bits: bit i & 31 of word i >> 5.  On input the bits of a
+                             row's last word from L on are ignored, on output they are 0.
+   The argument checks (an unknown format value, a missing input, and what each entry names below) run before anything
+   touches the GPU: they return -1 and ldpc_hip_last_error names the entry.  After them n == 0 returns 0.  Work is ordered on
+   hip_stream; with host outputs the call returns after they are written.  No call reads or changes a setting or any state of
+   the stream interface: a running ldpc_hip_stream_* sequence gives the same frames with or without these calls in between. */
+enum
+{
+    LDPC_HIP_BITS_U8 = 0,
+    LDPC_HIP_BITS_PACKED32 = 1
+};
+/* info[n][kc] (kc = info[6] of ldpc_hip_code_info) -> codeword[n][nc] bytes and / or codeword_bits[n][ceil(nc / 32)], both in
+   COLUMN order: the layout of ldpc_hip_out.codeword, not the transmitted-positions order of Part 1.
+   codeword[f][j] = XOR of info[f][i] over the entries (i, j) of the generator file: an entry listed twice cancels (as in the
+   stream encoder's masks and its walk), columns from G.cols up to nc are 0, rows of G the file leaves out contribute nothing,
+   and there is no running sum over the frames.  Two identities:
+     - for info whose bits from kct on are 0, encode() of Part 1 returns codeword[f][bit_pos[i]] at transmitted position i;
+     - with LDPC_HIP_NOISE_COUNTER the stream's frame f has codeword = ldpc_hip_encode_batch(u_f), u_f its information bits of
+       Philox tag 2 as specified above.
+   Fails (host only) when the context has no generator matrix, when G.rows > kc (the stream encoder's rule), and when the
+   column-mask table below would exceed 256 MiB.
+   How it runs: the columns of G as bit masks over the information word, nc x ceil(kc / 32) words, are built on the host at
+   the context's first encode call (a context that never encodes pays nothing); byte information is packed by one small
+   launch in front; the product is one launch per 2^20 frames at most (libldpc_amd/csrc/kernels_gf2.hip). */
+int ldpc_hip_encode_batch(ldpc_hip_ctx *ctx, uint64_t n, const void *info, int info_format, uint8_t *codeword,
+                          uint32_t *codeword_bits, void *hip_stream);
+/* word[n][nc] (column order) -> syndrome[n][mc] bytes 0 / 1, syndrome_bits[n][ceil(mc / 32)] and weight[n], the number of
+   unsatisfied check nodes of the frame.  syndrome[f][r] = XOR of word[f][c] over the entries (r, c) of H as the library
+   loaded it (an entry listed twice counts twice); for 0 / 1 input that is what syndrome() of Part 1 returns.  Works on every
+   code the library loads up to 524 288 columns (a frame's packed word is staged in LDS; beyond, -1) and needs no generator. */
+int ldpc_hip_syndrome_batch(ldpc_hip_ctx *ctx, uint64_t n, const void *word, int word_format, uint8_t *syndrome,
+                            uint32_t *syndrome_bits, uint32_t *weight, void *hip_stream);
+/* bit_errors[f] = the number of transmitted positions (the bit_pos set: punctured and shortened columns left out) at which
+   rows f of a[n][nc] and b[n][nc] differ, each operand in its own format: the count of ldpcsim.cpp:184-188.  Fed out->hard
+   and out->codeword of a stream decode it returns that call's out->bit_errors. */
+int ldpc_hip_bit_errors_batch(ldpc_hip_ctx *ctx, uint64_t n, const void *a, int a_format, const void *b, int b_format,
+                              uint32_t *bit_errors, void *hip_stream);
+
 /* channel point x of stream mt19937_64(seed): set_channel_param semantics, frame position := 0 */
 int ldpc_hip_stream_begin(ldpc_hip_ctx *ctx, int channel, uint64_t seed, double x);
 /* advance the stream by n frames without decoding them */

@@ -93,6 +93,12 @@ def load_library(path=LIB_PATH):
     L.ldpc_hip_decode_batch_typed.argtypes = [vp, decoder_param, u64, vp, i32, ct.POINTER(ldpc_hip_out), vp, vp]
     L.ldpc_hip_layered_fixed_direct_lds_bytes.restype = ct.c_int64
     L.ldpc_hip_layered_fixed_direct_lds_bytes.argtypes = [vp]
+    L.ldpc_hip_encode_batch.restype = i32
+    L.ldpc_hip_encode_batch.argtypes = [vp, u64, vp, i32, vp, vp, vp]
+    L.ldpc_hip_syndrome_batch.restype = i32
+    L.ldpc_hip_syndrome_batch.argtypes = [vp, u64, vp, i32, vp, vp, vp, vp]
+    L.ldpc_hip_bit_errors_batch.restype = i32
+    L.ldpc_hip_bit_errors_batch.argtypes = [vp, u64, vp, i32, vp, i32, vp, vp]
     L.ldpc_hip_stream_begin.restype = i32
     L.ldpc_hip_stream_begin.argtypes = [vp, i32, u64, ct.c_double]
     L.ldpc_hip_stream_skip.restype = i32
@@ -453,6 +459,63 @@ class HipDecoder:
                                                          self.LLR_TYPES[name], ct.byref(s), _ptr(bufs.get("hard_bits")), stream),
                     "ldpc_hip_decode_batch_typed")
         return bufs
+
+    BITS_FORMATS = {"uint8": 0, "uint32": 1}
+
+    def _bits(self, rows, length, what):
+        """(frames, format) of rows[n][length bits]: uint8 = a byte per bit, uint32 = packed 32 to a word."""
+        name = str(rows.dtype).replace("torch.", "")
+        if name not in self.BITS_FORMATS:
+            raise TypeError(f"{what} takes uint8 (a byte per bit) or uint32 (packed) rows, not {rows.dtype}")
+        width = length if name == "uint8" else (length + 31) // 32
+        if len(rows.shape) != 2 or int(rows.shape[1]) != width:
+            raise ValueError(f"{what}: rows of {length} bits as {name} are [n][{width}], not {tuple(rows.shape)}")
+        return int(rows.shape[0]), self.BITS_FORMATS[name]
+
+    @staticmethod
+    def _wanted(want, out, spec):
+        """Buffers of the outputs named in `want` (numpy, allocated here) or passed in `out`; spec: name -> (shape, dtype)."""
+        bufs = dict(out or {})
+        for name in list(want) + list(bufs):
+            if name not in spec:
+                raise KeyError(f"unknown output {name!r} (one of {sorted(spec)})")
+        for name in want:
+            if name not in bufs:
+                bufs[name] = np.zeros(*spec[name])
+        return bufs
+
+    def encode_batch(self, info, want=("codeword",), out=None, stream=None):
+        """info[n][kc] -> "codeword" (uint8 [n][nc]) and / or "codeword_bits" (uint32 [n][ceil(nc / 32)]), column order, frame
+        by frame u G with no running sum (include/ldpc_amd.h, ldpc_hip_encode_batch).  info is a numpy array or a torch tensor,
+        host or device; its dtype tells the format: uint8 = a byte per bit, uint32 = packed (anything else raises TypeError)."""
+        n, fmt = self._bits(info, self.kc, "encode_batch")
+        bufs = self._wanted(want, out, {"codeword": ((n, self.nc), np.uint8), "codeword_bits": ((n, (self.nc + 31) // 32), np.uint32)})
+        self._check(self.lib.ldpc_hip_encode_batch(self.ctx, n, _ptr(info), fmt, _ptr(bufs.get("codeword")),
+                                                   _ptr(bufs.get("codeword_bits")), stream), "ldpc_hip_encode_batch")
+        return bufs
+
+    def syndrome_batch(self, word, want=("weight",), out=None, stream=None):
+        """word[n][nc] (uint8 or packed uint32, column order) -> "syndrome" (uint8 [n][mc]), "syndrome_bits" (uint32
+        [n][ceil(mc / 32)]) and "weight" (uint32 [n], the unsatisfied check nodes); include/ldpc_amd.h, ldpc_hip_syndrome_batch."""
+        n, fmt = self._bits(word, self.nc, "syndrome_batch")
+        bufs = self._wanted(want, out, {"syndrome": ((n, self.mc), np.uint8), "syndrome_bits": ((n, (self.mc + 31) // 32), np.uint32),
+                                        "weight": ((n,), np.uint32)})
+        self._check(self.lib.ldpc_hip_syndrome_batch(self.ctx, n, _ptr(word), fmt, _ptr(bufs.get("syndrome")),
+                                                     _ptr(bufs.get("syndrome_bits")), _ptr(bufs.get("weight")), stream),
+                    "ldpc_hip_syndrome_batch")
+        return bufs
+
+    def bit_errors_batch(self, a, b, out=None, stream=None):
+        """The transmitted positions at which rows f of a[n][nc] and b[n][nc] differ, uint32 [n]; each operand uint8 or packed
+        uint32 (include/ldpc_amd.h, ldpc_hip_bit_errors_batch).  `out`: a buffer for the counts (else a numpy array)."""
+        n, fa = self._bits(a, self.nc, "bit_errors_batch")
+        nb, fb = self._bits(b, self.nc, "bit_errors_batch")
+        if n != nb:
+            raise ValueError(f"bit_errors_batch: {n} rows against {nb}")
+        res = np.zeros(n, np.uint32) if out is None else out
+        self._check(self.lib.ldpc_hip_bit_errors_batch(self.ctx, n, _ptr(a), fa, _ptr(b), fb, _ptr(res), stream),
+                    "ldpc_hip_bit_errors_batch")
+        return res
 
     def stream_begin(self, channel, seed, x):
         """Channel point x of mt19937_64(seed); also resets the encoder (a fresh channel object)."""

@@ -428,6 +428,25 @@ int ldpc_hip_decode_batch_typed(ldpc_hip_ctx *ctx, decoder_param dec, uint64_t n
     });
 }
 
+// (each engine method runs its host-only checks first: a refused call has touched no GPU, and n == 0 returns after them)
+int ldpc_hip_encode_batch(ldpc_hip_ctx *ctx, uint64_t n, const void *info, int info_format, uint8_t *codeword,
+                          uint32_t *codeword_bits, void *hip_stream)
+{
+    return guarded([&] { ctx->eng->encode_batch(n, info, info_format, codeword, codeword_bits, hip_stream); });
+}
+
+int ldpc_hip_syndrome_batch(ldpc_hip_ctx *ctx, uint64_t n, const void *word, int word_format, uint8_t *syndrome,
+                            uint32_t *syndrome_bits, uint32_t *weight, void *hip_stream)
+{
+    return guarded([&] { ctx->eng->syndrome_batch(n, word, word_format, syndrome, syndrome_bits, weight, hip_stream); });
+}
+
+int ldpc_hip_bit_errors_batch(ldpc_hip_ctx *ctx, uint64_t n, const void *a, int a_format, const void *b, int b_format,
+                              uint32_t *bit_errors, void *hip_stream)
+{
+    return guarded([&] { ctx->eng->bit_errors_batch(n, a, a_format, b, b_format, bit_errors, hip_stream); });
+}
+
 int64_t ldpc_hip_layered_fixed_direct_lds_bytes(const ldpc_hip_ctx *ctx)
 {
     int64_t bytes = -1; // (the plan builder allocates; -1 for every code the layered plan refuses)

@@ -1419,7 +1419,6 @@ void Engine::decode_typed(const DecParams &p, uint64_t n, const void *llr_in, in
     if (n == 0)
         return;
     upload_plan();
-    hipStream_t s = static_cast<hipStream_t>(stream);
     const uint64_t nc = static_cast<uint64_t>(plan_.nc), sub = max_sub_batch();
     const size_t elem = llr_type_bytes(type); // the typed source advances in units of its own element size
     const uint64_t words = (nc + 31) / 32;    // ... and the packed decisions in words per frame
@@ -1444,37 +1443,218 @@ void Engine::decode_typed(const DecParams &p, uint64_t n, const void *llr_in, in
         const size_t bytes = elem * m * nc;
         DecodeArgs a{};
         a.mode = kModeLlr;
-        const void *src = static_cast<const char *>(llr_in) + elem * done * nc;
-        if (!is_device_ptr(src))
-        {
-            // staged in its own type (binary64 where the decoder reads it; the widened image of the others goes there)
-            void *d = (type == kLlrF64 ? stage_in_ : stage_typed_).reserve(bytes);
-            const void *from = src;
-            if (bytes <= (1u << 20)) // small inputs through page-locked memory (see OutStage::flush)
-            {
-                if (!pin_in_ev_)
-                {
-                    hipEvent_t ev;
-                    check(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
-                    pin_in_ev_ = ev;
-                }
-                else
-                    check(hipEventSynchronize(static_cast<hipEvent_t>(pin_in_ev_)), "event"); // the previous copy out of the buffer is done
-                void *h = pin_in_.reserve(bytes);
-                std::memcpy(h, src, bytes);
-                from = h;
-            }
-            check(hipMemcpyAsync(d, from, bytes, hipMemcpyHostToDevice, s), "copy in");
-            if (from != src)
-                check(hipEventRecord(static_cast<hipEvent_t>(pin_in_ev_), s), "event");
-            src = d;
-        }
+        // host input is staged in its own type (binary64 where the decoder reads it; the widened image of the others goes there)
+        const void *src = stage_input(static_cast<const char *>(llr_in) + elem * done * nc, bytes, type == kLlrF64 ? stage_in_ : stage_typed_, stream);
         if (type == kLlrF64)
             a.llr_in = static_cast<const double *>(src);
         else
             io.llr = src;
         io.hard_bits = hard_bits ? hard_bits + done * words : nullptr;
         run_decode(a, p, out.at(done, nc), m, stream, type == kLlrF64 && !hard_bits ? nullptr : &io);
+    }
+}
+
+const void *Engine::stage_input(const void *src, size_t bytes, DeviceBuffer &stage, void *stream)
+{
+    if (is_device_ptr(src))
+        return src;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    void *d = stage.reserve(bytes);
+    const void *from = src;
+    if (bytes <= (1u << 20)) // small inputs through page-locked memory (see OutStage::flush)
+    {
+        if (!pin_in_ev_)
+        {
+            hipEvent_t ev;
+            check(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
+            pin_in_ev_ = ev;
+        }
+        else
+            check(hipEventSynchronize(static_cast<hipEvent_t>(pin_in_ev_)), "event"); // the previous copy out of the buffer is done
+        void *h = pin_in_.reserve(bytes);
+        std::memcpy(h, src, bytes);
+        from = h;
+    }
+    check(hipMemcpyAsync(d, from, bytes, hipMemcpyHostToDevice, s), "copy in");
+    if (from != src)
+        check(hipEventRecord(static_cast<hipEvent_t>(pin_in_ev_), s), "event");
+    return d;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Frames of bits on the device: encode, syndrome, bit errors (kernels_gf2.hip)
+static std::string bits_format_refusal(const char *entry, const char *operand, int format)
+{
+    if (bits_format_known(format))
+        return "";
+    return std::string(entry) + ": unknown format " + std::to_string(format) + " of " + operand + " (0 = LDPC_HIP_BITS_U8, 1 = LDPC_HIP_BITS_PACKED32)";
+}
+
+std::string Engine::encode_refusal(int info_format) const
+{
+    const char *who = "ldpc_hip_encode_batch";
+    if (std::string why = bits_format_refusal(who, "info", info_format); !why.empty())
+        return why;
+    if (!code_->has_G())
+        return std::string(who) + ": the context has no generator matrix";
+    const int kc = code_->kc();
+    if (kc <= 0 || code_->G.rows > kc)
+        return std::string(who) + ": generator matrix does not match the code (rows > nc - mc)";
+    if (static_cast<uint64_t>(plan_.nc) * ((static_cast<uint64_t>(kc) + 31) / 32) * 4 > (256ull << 20))
+        return std::string(who) + ": the column masks of G (nc x ceil(kc / 32) words) would exceed 256 MiB";
+    return "";
+}
+
+std::string Engine::syndrome_refusal(int word_format) const
+{
+    const char *who = "ldpc_hip_syndrome_batch";
+    if (std::string why = bits_format_refusal(who, "word", word_format); !why.empty())
+        return why;
+    const uint32_t nc = static_cast<uint32_t>(plan_.nc);
+    if ((256 / (64 * gf2_syndrome_waves_per_frame(nc))) * gf2_syndrome_frame_lds_bytes(nc) > kGf2SyndromeMaxLds)
+        return std::string(who) + ": a frame of more than 524 288 columns does not fit the kernel's LDS";
+    return "";
+}
+
+std::string Engine::bit_errors_refusal(int a_format, int b_format) const
+{
+    const char *who = "ldpc_hip_bit_errors_batch";
+    if (std::string why = bits_format_refusal(who, "a", a_format); !why.empty())
+        return why;
+    return bits_format_refusal(who, "b", b_format);
+}
+
+uint64_t Engine::gf2_sub_batch() const
+{
+    return std::clamp<uint64_t>((256ull << 20) / static_cast<uint64_t>(plan_.nc), 1, 1u << 20);
+}
+
+void Engine::encode_batch(uint64_t n, const void *info, int info_format, uint8_t *codeword, uint32_t *codeword_bits, void *stream)
+{
+    const char *who = "ldpc_hip_encode_batch";
+    if (const std::string why = encode_refusal(info_format); !why.empty())
+        throw std::runtime_error(why);
+    if (n && !info)
+        throw std::runtime_error(std::string(who) + ": null info");
+    if (n == 0 || (!codeword && !codeword_bits))
+        return;
+    bind_device();
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint64_t nc = static_cast<uint64_t>(plan_.nc), kc = static_cast<uint64_t>(code_->kc());
+    const uint64_t words = (kc + 31) / 32, out_words = (nc + 31) / 32;
+    if (!gf2_mask_) // the columns of G as masks over the information word, once per context
+    {
+        const uint64_t cols = (nc + 255) / 256 * 256;
+        std::vector<uint32_t> mask(words * cols, 0);
+        const SparseGF2 &G = code_->G;
+        for (int j = 0; j < G.cols && static_cast<uint64_t>(j) < nc; ++j)
+            for (int q = G.cptr[j]; q < G.cptr[j + 1]; ++q)
+            {
+                const uint64_t r = static_cast<uint64_t>(G.crow[q]);
+                mask[(r / 32) * cols + j] ^= 1u << (r % 32); // (a repeated entry cancels)
+            }
+        gf2_mask_cols_ = cols;
+        gf2_mask_ = static_cast<const uint32_t *>(upload_table(mask.data(), mask.size() * 4, "generator masks"));
+    }
+    const uint64_t sub = gf2_sub_batch();
+    const size_t in_row = bits_row_bytes(info_format, kc);
+    for (uint64_t done = 0; done < n; done += sub)
+    {
+        const uint64_t m = std::min(sub, n - done);
+        const void *src = stage_input(static_cast<const char *>(info) + in_row * done, in_row * m, stage_in_, stream);
+        if (info_format == kBitsU8) // bytes: packed by one small launch in front
+        {
+            uint32_t *packed = static_cast<uint32_t *>(gf2_info_.reserve(4 * m * words));
+            check(launch_pack_hard(static_cast<const uint8_t *>(src), m, static_cast<int>(kc), packed, s), "encode_batch (pack)");
+            src = packed;
+        }
+        OutStage st;
+        Gf2EncodeArgs a{};
+        a.nc = static_cast<uint32_t>(nc), a.words = static_cast<uint32_t>(words);
+        a.mask_cols = gf2_mask_cols_, a.mask = gf2_mask_;
+        a.info = static_cast<const uint32_t *>(src);
+        a.codeword = st.route(codeword ? codeword + done * nc : nullptr, stage_gf2_[0], m * nc);
+        a.codeword_bits = st.route(codeword_bits ? codeword_bits + done * out_words : nullptr, stage_gf2_[1], 4 * m * out_words);
+        a.n = m;
+        check(launch_gf2_encode(a, s), "encode_batch");
+        st.flush(s, &pin_out_);
+    }
+}
+
+void Engine::syndrome_batch(uint64_t n, const void *word, int word_format, uint8_t *syndrome, uint32_t *syndrome_bits, uint32_t *weight,
+                            void *stream)
+{
+    const char *who = "ldpc_hip_syndrome_batch";
+    if (const std::string why = syndrome_refusal(word_format); !why.empty())
+        throw std::runtime_error(why);
+    if (n && !word)
+        throw std::runtime_error(std::string(who) + ": null word");
+    if (n == 0 || (!syndrome && !syndrome_bits && !weight))
+        return;
+    bind_device();
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint64_t nc = static_cast<uint64_t>(plan_.nc), mc = static_cast<uint64_t>(plan_.mc), out_words = (mc + 31) / 32;
+    if (!gf2_row_ptr_)
+    {
+        const SparseGF2 &H = code_->H;
+        std::vector<uint32_t> rp(H.rptr.begin(), H.rptr.end()), rc(H.rcol.begin(), H.rcol.end());
+        gf2_row_col_ = static_cast<const uint32_t *>(upload_table(rc.data(), rc.size() * 4, "rows of H"));
+        gf2_row_ptr_ = static_cast<const uint32_t *>(upload_table(rp.data(), rp.size() * 4, "rows of H")); // last: the mark
+    }
+    const uint64_t sub = gf2_sub_batch();
+    const size_t in_row = bits_row_bytes(word_format, nc);
+    for (uint64_t done = 0; done < n; done += sub)
+    {
+        const uint64_t m = std::min(sub, n - done);
+        OutStage st;
+        Gf2SyndromeArgs a{};
+        a.nc = static_cast<uint32_t>(nc), a.mc = static_cast<uint32_t>(mc);
+        a.row_ptr = gf2_row_ptr_, a.row_col = gf2_row_col_;
+        a.word = stage_input(static_cast<const char *>(word) + in_row * done, in_row * m, stage_in_, stream);
+        a.syndrome = st.route(syndrome ? syndrome + done * mc : nullptr, stage_gf2_[0], m * mc);
+        a.syndrome_bits = st.route(syndrome_bits ? syndrome_bits + done * out_words : nullptr, stage_gf2_[1], 4 * m * out_words);
+        a.weight = st.route(weight ? weight + done : nullptr, stage_gf2_[2], 4 * m);
+        a.n = m;
+        check(launch_gf2_syndrome(a, word_format, s), "syndrome_batch");
+        st.flush(s, &pin_out_);
+    }
+}
+
+void Engine::bit_errors_batch(uint64_t n, const void *a_rows, int a_format, const void *b_rows, int b_format, uint32_t *bit_errors,
+                              void *stream)
+{
+    const char *who = "ldpc_hip_bit_errors_batch";
+    if (const std::string why = bit_errors_refusal(a_format, b_format); !why.empty())
+        throw std::runtime_error(why);
+    if (n && (!a_rows || !b_rows))
+        throw std::runtime_error(std::string(who) + ": null operand");
+    if (n == 0 || !bit_errors)
+        return;
+    bind_device();
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint64_t nc = static_cast<uint64_t>(plan_.nc);
+    if (!gf2_tx_mask_)
+    {
+        std::vector<uint64_t> tx((nc + 63) / 64, 0);
+        for (int c : code_->bit_pos)
+            tx[static_cast<size_t>(c) / 64] |= 1ull << (c % 64);
+        gf2_tx_mask_ = static_cast<const uint64_t *>(upload_table(tx.data(), tx.size() * 8, "transmitted positions"));
+    }
+    const uint64_t sub = gf2_sub_batch();
+    const size_t a_row = bits_row_bytes(a_format, nc), b_row = bits_row_bytes(b_format, nc);
+    for (uint64_t done = 0; done < n; done += sub)
+    {
+        const uint64_t m = std::min(sub, n - done);
+        OutStage st;
+        Gf2BitErrorArgs g{};
+        g.nc = static_cast<uint32_t>(nc);
+        g.tx_mask = gf2_tx_mask_;
+        g.a = stage_input(static_cast<const char *>(a_rows) + a_row * done, a_row * m, stage_in_, stream);
+        g.b = stage_input(static_cast<const char *>(b_rows) + b_row * done, b_row * m, stage_in_b_, stream);
+        g.bit_errors = st.route(bit_errors + done, stage_gf2_[0], 4 * m);
+        g.n = m;
+        check(launch_gf2_bit_errors(g, a_format, b_format, s), "bit_errors_batch");
+        st.flush(s, &pin_out_);
     }
 }
 

@@ -338,6 +338,21 @@ class Engine
     std::string typed_refusal(const DecParams &p, int type) const;
     void decode_typed(const DecParams &p, uint64_t n, const void *llr_in, int type, const BatchOut &out, uint32_t *hard_bits, void *stream);
 
+    // ---- frames of bits that stay on the device (include/ldpc_amd.h, ldpc_hip_encode_batch / _syndrome_batch /
+    // _bit_errors_batch; kernels_gf2.hip).  Rows are bytes or packed words (kernels.hpp, BitsFormat); every buffer is device or
+    // host memory, an output nullptr = not wanted.  None of them reads or changes a setting or the stream interface's state.
+    // Host only: what each call refuses before anything touches the GPU, empty when it is taken ----
+    std::string encode_refusal(int info_format) const;
+    std::string syndrome_refusal(int word_format) const;
+    std::string bit_errors_refusal(int a_format, int b_format) const;
+    // codeword[f][j] = XOR of info[f][i] over the entries (i, j) of G; column order, no running sum over the frames
+    void encode_batch(uint64_t n, const void *info, int info_format, uint8_t *codeword, uint32_t *codeword_bits, void *stream);
+    // syndrome[f][r] = XOR of word[f][c] over the entries (r, c) of H; weight[f] = the frame's unsatisfied check nodes
+    void syndrome_batch(uint64_t n, const void *word, int word_format, uint8_t *syndrome, uint32_t *syndrome_bits, uint32_t *weight,
+                        void *stream);
+    // bit_errors[f] = transmitted positions at which rows f of a and b differ
+    void bit_errors_batch(uint64_t n, const void *a, int a_format, const void *b, int b_format, uint32_t *bit_errors, void *stream);
+
     // ---- fused channel + decode on the reference's noise stream ----
     // set_channel_param semantics (channel.cpp:37-42): the stream restarts at frame 0.
     // `fresh` also resets the encoder (info-word stream position and the accumulated codeword), i.e. a
@@ -516,6 +531,16 @@ class Engine
     DeviceBuffer enc_base_; // sharded encoding: the other ranks' info-word sums (two rows of `words`)
     DeviceBuffer stage_in_, stage_iters_, stage_be_, stage_hard_, stage_llr_out_, stage_llr_in_, stage_cw_;
     DeviceBuffer stage_typed_, stage_bits_; // typed batch call: host input in its own type, packed decisions for a host buffer
+    // the batch calls on frames of bits: the tables (each uploaded by the first call that needs it: a context that never
+    // encodes builds no mask table), the packed image of byte information, staging of a second host input and of host outputs
+    const uint32_t *gf2_mask_ = nullptr;    // [ceil(kc / 32)][gf2_mask_cols_]: the columns of G as masks, word-major (Gf2EncodeArgs)
+    uint64_t gf2_mask_cols_ = 0;
+    const uint32_t *gf2_row_ptr_ = nullptr, *gf2_row_col_ = nullptr; // row CSR of H
+    const uint64_t *gf2_tx_mask_ = nullptr; // the transmitted positions (bit_pos) as a mask over the columns
+    DeviceBuffer gf2_info_, stage_in_b_, stage_gf2_[3];
+    uint64_t gf2_sub_batch() const; // frames per launch: staging buffers stay modest, no grid dimension overflows
+    // a host input of a batch call on the device (small ones through page-locked memory); a device pointer comes back as it is
+    const void *stage_input(const void *src, size_t bytes, DeviceBuffer &stage, void *stream);
     DeviceBuffer ws_msg_, ws_llr_, ws_hb_, ws_scr_;
     PinnedBuffer pin_in_, pin_out_;
     void *pin_in_ev_ = nullptr; // hipEvent_t: the last host-to-device copy out of pin_in_

@@ -322,6 +322,60 @@ int launch_decode_layered_fixed_direct(const DecodeArgs &a, const DevLayerPlan &
 int launch_widen_llr(const void *src, int type, double step, uint64_t count, double *dst, void *stream);
 int launch_pack_hard(const uint8_t *hard, uint64_t n, int nc, uint32_t *bits, void *stream);
 
+// ---- GF(2) work on frames of bits (kernels_gf2.hip; include/ldpc_amd.h, ldpc_hip_encode_batch / _syndrome_batch /
+// _bit_errors_batch).  A row of L bits is bytes (non-zero = 1) or packed as hard_bits is, ceil(L / 32) words ----
+enum BitsFormat : int
+{
+    kBitsU8 = 0,
+    kBitsPacked32 = 1,
+};
+constexpr bool bits_format_known(int f) { return f == kBitsU8 || f == kBitsPacked32; }
+constexpr size_t bits_row_bytes(int format, uint64_t bits) { return format == kBitsU8 ? bits : 4 * ((bits + 31) / 32); }
+// the encoder: a lane keeps at most kGf2MaxChunkWords words of its column's mask in registers and walks a longer information
+// word in chunks of that many; kGf2FrameTile frames share them, kGf2FramesPerBlock frames a workgroup's 256 columns
+constexpr int kGf2MaxChunkWords = 32, kGf2FrameTile = 16, kGf2FramesPerBlock = 64;
+// the chunk T of a code with `words` information words: the largest power of two <= min(words, kGf2MaxChunkWords), so that
+// every window of T words lies inside the row
+int gf2_encode_chunk_words(uint32_t words);
+struct Gf2EncodeArgs
+{
+    uint32_t nc, words;       // words = ceil(kc / 32)
+    uint64_t mask_cols;       // nc rounded up to a multiple of 256
+    const uint32_t *mask;     // [words][mask_cols]: word w of column j's mask over the information word (zero columns beyond G.cols)
+    const uint32_t *info;     // [n][words] packed information bits (the bits from kc on are not read: no mask has them)
+    uint8_t *codeword;        // [n][nc] or nullptr
+    uint32_t *codeword_bits;  // [n][ceil(nc / 32)] or nullptr
+    uint64_t n;               // at most 65535 * kGf2FramesPerBlock
+};
+int launch_gf2_encode(const Gf2EncodeArgs &a, void *stream);
+// the syndrome: one wave per frame (four frames per workgroup) up to kGf2SyndromeWaveCols columns, four waves per frame beyond;
+// the frame's packed word in LDS, 8 bytes per 64 columns
+constexpr uint32_t kGf2SyndromeWaveCols = 4096;
+constexpr size_t kGf2SyndromeMaxLds = 64 * 1024;
+constexpr int gf2_syndrome_waves_per_frame(uint32_t nc) { return nc <= kGf2SyndromeWaveCols ? 1 : 4; }
+constexpr size_t gf2_syndrome_frame_lds_bytes(uint32_t nc) { return 8 * ((static_cast<size_t>(nc) + 63) / 64); }
+struct Gf2SyndromeArgs
+{
+    uint32_t nc, mc;
+    const uint32_t *row_ptr;  // [mc + 1] row CSR of H, entries in file order (a repeated entry counts twice)
+    const uint32_t *row_col;  // [nnz]
+    const void *word;         // [n][nc] bytes or [n][ceil(nc / 32)] words
+    uint8_t *syndrome;        // [n][mc] or nullptr
+    uint32_t *syndrome_bits;  // [n][ceil(mc / 32)] or nullptr
+    uint32_t *weight;         // [n] or nullptr
+    uint64_t n;
+};
+int launch_gf2_syndrome(const Gf2SyndromeArgs &a, int format, void *stream);
+struct Gf2BitErrorArgs
+{
+    uint32_t nc;
+    const uint64_t *tx_mask;  // [ceil(nc / 64)]: bit c & 63 of word c >> 6 set where column c is transmitted
+    const void *a, *b;        // [n][nc] bytes or [n][ceil(nc / 32)] words, each in its own format
+    uint32_t *bit_errors;     // [n]
+    uint64_t n;               // at most 2^31
+};
+int launch_gf2_bit_errors(const Gf2BitErrorArgs &a, int a_format, int b_format, void *stream);
+
 // opt-in non-parity ternary min-sum, bit-sliced over 32 frames per workgroup (kernels_ternary.hip; include/ldpc_amd.h,
 // ldpc_hip_set_min_sum_ternary) on the general plan.  a.ms_* are not read.  With a.llr_out null the planes of A are left out
 // of the group's LDS (plan.hpp, ternary_lds_bytes)
