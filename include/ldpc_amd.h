@@ -393,9 +393,10 @@ int ldpc_hip_decode_batch_typed(ldpc_hip_ctx *ctx, decoder_param dec, uint64_t n
 int64_t ldpc_hip_layered_fixed_direct_lds_bytes(const ldpc_hip_ctx *ctx);
 
 /* Frames of bits that stay on the device: the transmit side of ldpc_hip_decode_batch_typed and its check,
-     ldpc_hip_encode_batch -> (the caller's modulation and channel) -> ldpc_hip_decode_batch_typed -> ldpc_hip_syndrome_batch,
+     ldpc_hip_encode_batch -> ldpc_hip_channel_batch -> ldpc_hip_decode_batch_typed -> ldpc_hip_syndrome_batch,
      ldpc_hip_bit_errors_batch
-   with packed words passing from one call to the next.  Pure GF(2): every output bit is determined.
+   with packed words passing from one call to the next.  The GF(2) calls are pure: every output bit is determined
+   (ldpc_hip_channel_batch states its own contract below).
    Common rules.  Every buffer is device or host memory (host buffers are staged; inputs and results of up to 1 MB through
    page-locked memory; device buffers are used in place).  An output pointer may be NULL = not wanted.  A row of L bits is
      LDPC_HIP_BITS_U8        L bytes, a non-zero byte is 1 (as encode() reads its input); outputs are 0 / 1;
@@ -436,6 +437,62 @@ int ldpc_hip_syndrome_batch(ldpc_hip_ctx *ctx, uint64_t n, const void *word, int
    and out->codeword of a stream decode it returns that call's out->bit_errors. */
 int ldpc_hip_bit_errors_batch(ldpc_hip_ctx *ctx, uint64_t n, const void *a, int a_format, const void *b, int b_format,
                               uint32_t *bit_errors, void *hip_stream);
+
+/* The channel between the encoder and the decoder: modulation, noise, demapper and the quantizer in one launch
+   (libldpc_amd/csrc/kernels_channel.hip).  codeword[n][nc] in, LLRs in the element type the decoder reads out; the common
+   rules above hold (device or host buffers, checks before the GPU, n == 0 returns 0 after them, ordered on hip_stream, no
+   setting read or changed, the stream interface's state untouched — the channel point and the noise mode of
+   ldpc_hip_stream_begin / ldpc_hip_set_noise included: everything the call uses is in *ch).
+   Buffers.  codeword[n][nc], column order, LDPC_HIP_BITS_U8 or LDPC_HIP_BITS_PACKED32 (what ldpc_hip_encode_batch writes);
+   NULL = the all-zero codeword.  llr[n][nc], column order, elements of ch->llr_type; may be NULL.  received[n][S], binary64,
+   S = ceil(nct / m) symbols per frame; may be NULL.  Every element of a wanted output is written exactly once: the caller
+   need not clear it.
+   Refused (host only, -1, ldpc_hip_last_error names ldpc_hip_channel_batch): a null ch; an unknown channel, format or type;
+   m outside 1..4, or m != 1 with the BSC; a non-finite x for AWGN; x outside (0, 1) for the BSC; with LDPC_HIP_LLR_I8 q_bits
+   outside 2..8 or step outside [2^-20, 2^20]; both outputs NULL with n > 0.  (The BEC is not offered: its decoder takes symbols.)
+   Arithmetic.  NON-PARITY, the noise of LDPC_HIP_NOISE_COUNTER: every bit of llr is determined given received, and received
+   is determined up to the hardware's binary32 log / sqrt / sin / cos, as for that mode.  Binary64 throughout, every operation
+   rounded once, no fused multiply-add.
+     Setup.  i = 0..nct-1 are the transmitted positions, bit_pos[i] their columns; only those columns of the codeword are read,
+       a non-zero byte counts as 1.  Symbol s carries the bits i = m s + k, k = 0..m-1; a bit beyond nct - 1 counts as 0.
+       AWGN: sigma2 = pow(10, -x / 10), sigma = sqrt(sigma2); BSC: delta = log((1 - x) / x) — the host expressions of
+       ldpc_hip_stream_begin.
+     AWGN noise.  Symbol s takes normal s % 4 of Philox block s / 4 of frame first_frame + f under tag 0 (ldpc_hip_set_noise:
+       the Box-Muller pairs specified there); noise = (double) normal * sigma + 0.0.
+     AWGN, m = 1.  a = 1 - 2 bit, y = noise + a, received = y, llr = (2 * y) / sigma2: the operations of the stream's channel.
+     AWGN, m = 2..4 (M = 2^m).  Levels level[j] = (double) (M - 1 - 2 j) * c for j = 0..M-1, c = 1.0 / sqrt((double) (M * M - 1)
+       / 3.0), built once on the host: unit mean energy; the kernel sees the table only.  g = the symbol's m bits, the first
+       the most significant; the level index j is the inverse Gray code of g: j ^ (j >> 1) == g.  y = noise + level[j],
+       received = y.  Max-log demapping: d_j = (y - level[j]) * (y - level[j]) for every j; for bit k D0 = the smallest d_j over
+       the levels whose label j ^ (j >> 1) has bit k = 0, D1 the same for bit k = 1; llr = (D1 - D0) / (2 * sigma2).  The LLRs
+       of padding bits are written nowhere.  Two such dimensions form a square 2^(2m)-QAM symbol: the error rates at the
+       per-dimension x are those of QPSK, 16-, 64- and 256-QAM.  There is no complex interface.
+     BSC.  ybit = bit ^ hit, hit = ((word i % 4 of block i / 4 under tag 1) + 0.5) / 2^32 < x; received = (double) (1 - 2 ybit);
+       llr = delta * received.
+     Other columns.  Punctured and unconnected columns get +0.0; shortened columns 99999.9 (AWGN) or delta (BSC): the stream's
+       values.
+     For m = 1 the rows of llr (LDPC_HIP_LLR_F64) equal, bit for bit, out->llr_in of ldpc_hip_stream_decode under
+       LDPC_HIP_NOISE_COUNTER, the same channel, x and seed, for the stream's frames first_frame + f and their codewords.
+     Element type, L the binary64 value above.  LDPC_HIP_LLR_F64: L.  LDPC_HIP_LLR_F32: L rounded to nearest-even.
+       LDPC_HIP_LLR_F16: that binary32 value rounded to nearest-even (two roundings); 99999.9 becomes +infinity, which the
+       decoders widen back to +infinity.  LDPC_HIP_LLR_I8: clamp(rint(fl(L * inv)), -Qmax, +Qmax), inv = fl(1 / step), Qmax =
+       2^(q_bits - 1) - 1: item 1 of ldpc_hip_set_min_sum_quantization, the clamp applied in binary64, a NaN gives 0 — feed it to
+       ldpc_hip_decode_batch_typed under a fixed-point mode of the same step.
+   How it runs: one launch per 2^31 / (lanes per frame) frames at most; a lane owns one Philox block of a frame — four symbols,
+   4 m bits — and further lanes fill the columns the channel does not write; no LDS. */
+typedef struct
+{
+    int channel;          /* LDPC_HIP_AWGN or LDPC_HIP_BSC */
+    double x;             /* AWGN: Es / sigma^2 in dB; BSC: crossover probability (ldpc_hip_stream_begin's meaning) */
+    uint64_t seed;        /* Philox key, as LDPC_HIP_NOISE_COUNTER takes it */
+    uint64_t first_frame; /* row f of the call is frame first_frame + f of that noise */
+    int bits_per_symbol;  /* m: AWGN 1..4 (2^m-ASK per real dimension), BSC 1 */
+    int llr_type;         /* LDPC_HIP_LLR_F64 / F32 / F16 / I8: element type of llr */
+    int q_bits;           /* LDPC_HIP_LLR_I8 only: 2..8 */
+    double step;          /* LDPC_HIP_LLR_I8 only: 2^-20..2^20 */
+} ldpc_hip_channel;
+int ldpc_hip_channel_batch(ldpc_hip_ctx *ctx, const ldpc_hip_channel *ch, uint64_t n, const void *codeword,
+                           int codeword_format, void *llr, double *received, void *hip_stream);
 
 /* channel point x of stream mt19937_64(seed): set_channel_param semantics, frame position := 0 */
 int ldpc_hip_stream_begin(ldpc_hip_ctx *ctx, int channel, uint64_t seed, double x);

@@ -36,6 +36,11 @@ class ldpc_hip_out(ct.Structure):
                 ("llr_out", ct.c_void_p), ("llr_in", ct.c_void_p), ("codeword", ct.c_void_p)]
 
 
+class ldpc_hip_channel(ct.Structure):
+    _fields_ = [("channel", ct.c_int), ("x", ct.c_double), ("seed", ct.c_uint64), ("first_frame", ct.c_uint64),
+                ("bits_per_symbol", ct.c_int), ("llr_type", ct.c_int), ("q_bits", ct.c_int), ("step", ct.c_double)]
+
+
 _lib = None
 
 
@@ -99,6 +104,8 @@ def load_library(path=LIB_PATH):
     L.ldpc_hip_syndrome_batch.argtypes = [vp, u64, vp, i32, vp, vp, vp, vp]
     L.ldpc_hip_bit_errors_batch.restype = i32
     L.ldpc_hip_bit_errors_batch.argtypes = [vp, u64, vp, i32, vp, i32, vp, vp]
+    L.ldpc_hip_channel_batch.restype = i32
+    L.ldpc_hip_channel_batch.argtypes = [vp, ct.POINTER(ldpc_hip_channel), u64, vp, i32, vp, vp, vp]
     L.ldpc_hip_stream_begin.restype = i32
     L.ldpc_hip_stream_begin.argtypes = [vp, i32, u64, ct.c_double]
     L.ldpc_hip_stream_skip.restype = i32
@@ -516,6 +523,40 @@ class HipDecoder:
         self._check(self.lib.ldpc_hip_bit_errors_batch(self.ctx, n, _ptr(a), fa, _ptr(b), fb, _ptr(res), stream),
                     "ldpc_hip_bit_errors_batch")
         return res
+
+    def channel_batch(self, codeword, channel, x, seed=0, first_frame=0, bits_per_symbol=1, llr="float64", q_bits=0, step=1.0,
+                      frames=None, want=("llr",), out=None, stream=None):
+        """codeword[n][nc] (uint8 or packed uint32, column order; None = `frames` all-zero codewords) through the channel
+        ("AWGN": x = Es / sigma^2 in dB, 2^bits_per_symbol-ASK; "BSC": x = the crossover probability) under the counter noise of
+        (seed, first_frame + row) -> "llr" ([n][nc] of dtype `llr`: float64, float32, float16, or int8 with q_bits and step)
+        and / or "received" (float64 [n][ceil(nct / bits_per_symbol)]); include/ldpc_amd.h, ldpc_hip_channel_batch.  codeword
+        and the buffers in `out` are numpy arrays or torch tensors, host or device; a wrong dtype raises TypeError, a wrong shape
+        ValueError."""
+        if llr not in self.LLR_TYPES:
+            raise TypeError(f"channel_batch writes float64, float32, float16 or int8 LLRs, not {llr!r}")
+        if codeword is None:
+            if frames is None:
+                raise ValueError("channel_batch: codeword=None (all-zero codewords) needs frames=")
+            n, fmt = int(frames), 0
+        else:
+            n, fmt = self._bits(codeword, self.nc, "channel_batch")
+            if frames is not None and int(frames) != n:
+                raise ValueError(f"channel_batch: frames={frames} against {n} rows")
+        m = int(bits_per_symbol)
+        symbols = -(-self.nct // m) if 1 <= m <= 4 else 0  # (the library refuses other m)
+        spec = {"llr": ((n, self.nc), np.dtype(llr)), "received": ((n, symbols), np.float64)}
+        bufs = self._wanted(want, out, spec)
+        for name, buf in bufs.items():
+            shape, dt = spec[name]
+            if str(buf.dtype).replace("torch.", "") != np.dtype(dt).name:
+                raise TypeError(f"channel_batch: {name} is {np.dtype(dt).name}, not {buf.dtype}")
+            if tuple(buf.shape) != shape:
+                raise ValueError(f"channel_batch: {name} is {shape}, not {tuple(buf.shape)}")
+        ch = ldpc_hip_channel(CHANNELS[channel] if isinstance(channel, str) else int(channel), float(x), int(seed), int(first_frame),
+                              m, self.LLR_TYPES[llr], int(q_bits), float(step))
+        self._check(self.lib.ldpc_hip_channel_batch(self.ctx, ct.byref(ch), n, _ptr(codeword), fmt, _ptr(bufs.get("llr")),
+                                                    _ptr(bufs.get("received")), stream), "ldpc_hip_channel_batch")
+        return bufs
 
     def stream_begin(self, channel, seed, x):
         """Channel point x of mt19937_64(seed); also resets the encoder (a fresh channel object)."""

@@ -447,6 +447,20 @@ int ldpc_hip_bit_errors_batch(ldpc_hip_ctx *ctx, uint64_t n, const void *a, int 
     return guarded([&] { ctx->eng->bit_errors_batch(n, a, a_format, b, b_format, bit_errors, hip_stream); });
 }
 
+int ldpc_hip_channel_batch(ldpc_hip_ctx *ctx, const ldpc_hip_channel *ch, uint64_t n, const void *codeword, int codeword_format,
+                           void *llr, double *received, void *hip_stream)
+{
+    return guarded([&] {
+        Engine::ChannelSpec spec;
+        if (ch)
+        {
+            spec.channel = ch->channel, spec.x = ch->x, spec.seed = ch->seed, spec.first_frame = ch->first_frame;
+            spec.bits_per_symbol = ch->bits_per_symbol, spec.llr_type = ch->llr_type, spec.q_bits = ch->q_bits, spec.step = ch->step;
+        }
+        ctx->eng->channel_batch(ch ? &spec : nullptr, n, codeword, codeword_format, llr, received, hip_stream);
+    });
+}
+
 int64_t ldpc_hip_layered_fixed_direct_lds_bytes(const ldpc_hip_ctx *ctx)
 {
     int64_t bytes = -1; // (the plan builder allocates; -1 for every code the layered plan refuses)

@@ -1658,6 +1658,115 @@ void Engine::bit_errors_batch(uint64_t n, const void *a_rows, int a_format, cons
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The channel between the encoder and the decoder (kernels_channel.hip)
+std::string Engine::channel_refusal(const ChannelSpec *spec, uint64_t n, int codeword_format, const void *llr, const double *received) const
+{
+    const std::string who = "ldpc_hip_channel_batch: ";
+    if (!spec)
+        return who + "null channel description";
+    const ChannelSpec &c = *spec;
+    if (c.channel != kAwgn && c.channel != kBsc)
+        return who + "unknown channel " + std::to_string(c.channel) + " (1 = LDPC_HIP_AWGN, 2 = LDPC_HIP_BSC)";
+    if (std::string why = bits_format_refusal("ldpc_hip_channel_batch", "codeword", codeword_format); !why.empty())
+        return why;
+    if (llr_type_bytes(c.llr_type) == 0)
+        return who + "unknown LLR type " + std::to_string(c.llr_type) + " (0 = binary64, 1 = binary32, 2 = binary16, 3 = int8)";
+    if (c.bits_per_symbol < 1 || c.bits_per_symbol > kChannelMaxBitsPerSymbol)
+        return who + "bits_per_symbol " + std::to_string(c.bits_per_symbol) + " outside 1..4";
+    if (c.channel == kBsc && c.bits_per_symbol != 1)
+        return who + "the BSC carries one bit per symbol, not " + std::to_string(c.bits_per_symbol);
+    if (c.channel == kAwgn && !std::isfinite(c.x))
+        return who + "the AWGN point x (Es / sigma^2 in dB) is not finite";
+    if (c.channel == kBsc && !(c.x > 0.0 && c.x < 1.0))
+        return who + "the BSC crossover probability x is outside (0, 1)";
+    if (c.llr_type == kLlrI8)
+    {
+        if (c.q_bits < 2 || c.q_bits > 8)
+            return who + "q_bits " + std::to_string(c.q_bits) + " outside 2..8 for int8 LLRs";
+        if (!(c.step >= 0x1p-20 && c.step <= 0x1p20))
+            return who + "step outside [2^-20, 2^20] for int8 LLRs";
+    }
+    if (n && !llr && !received)
+        return who + "neither llr nor received is wanted";
+    return "";
+}
+
+void Engine::channel_batch(const ChannelSpec *spec, uint64_t n, const void *codeword, int codeword_format, void *llr, double *received,
+                           void *stream)
+{
+    if (const std::string why = channel_refusal(spec, n, codeword_format, llr, received); !why.empty())
+        throw std::runtime_error(why);
+    if (n == 0)
+        return;
+    const ChannelSpec &c = *spec;
+    upload_plan();
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint64_t nc = static_cast<uint64_t>(plan_.nc), nct = static_cast<uint64_t>(plan_.nct);
+    const int m = c.bits_per_symbol;
+    if (!chan_levels_)
+    {
+        // the columns the channel does not write, in column order: punctured and unconnected ones get +0.0, shortened ones
+        // the channel's value (plan.cpp, rank_kind: the stream's rule)
+        std::vector<uint32_t> other;
+        for (uint32_t col = 0; col < nc; ++col)
+            if (const uint8_t kind = plan_.rank_kind[plan_.col_rank[col]]; kind != 0)
+                other.push_back(col | (kind == 2 ? kChannelShortened : 0u));
+        chan_n_other_ = static_cast<uint32_t>(other.size());
+        chan_other_ = static_cast<const uint32_t *>(upload_table(other.data(), other.size() * 4, "columns outside the channel"));
+        // 2^m-ASK of unit mean energy, m = 2..4, 16 entries each: level[j] = (M - 1 - 2 j) c, c = 1 / sqrt((M^2 - 1) / 3)
+        std::vector<double> level(16 * (kChannelMaxBitsPerSymbol + 1), 0.0);
+        for (int mm = 2; mm <= kChannelMaxBitsPerSymbol; ++mm)
+        {
+            const int M = 1 << mm;
+            const double cc = 1.0 / std::sqrt(static_cast<double>(M * M - 1) / 3.0);
+            for (int j = 0; j < M; ++j)
+                level[16 * mm + j] = static_cast<double>(M - 1 - 2 * j) * cc;
+        }
+        chan_levels_ = static_cast<const double *>(upload_table(level.data(), level.size() * 8, "constellations")); // last: the mark
+    }
+    ChannelArgs a{};
+    a.nc = static_cast<uint32_t>(nc), a.nct = static_cast<uint32_t>(nct);
+    a.symbols = static_cast<uint32_t>((nct + m - 1) / m);
+    a.blocks = (a.symbols + 3) / 4;
+    a.n_other = chan_n_other_, a.work = a.blocks + a.n_other;
+    a.bit_pos = dev_.bit_pos, a.other = chan_other_, a.level = m > 1 ? chan_levels_ + 16 * m : nullptr;
+    a.codeword_format = codeword_format, a.channel = c.channel;
+    a.key[0] = static_cast<uint32_t>(c.seed), a.key[1] = static_cast<uint32_t>(c.seed >> 32);
+    if (c.channel == kAwgn) // the host expressions of stream_begin
+    {
+        a.sigma2 = std::pow(10, -c.x / 10);
+        a.sigma = std::sqrt(a.sigma2);
+        a.shorten = 99999.9;
+    }
+    else
+    {
+        a.eps = c.x;
+        a.delta = std::log((1 - c.x) / c.x);
+        a.shorten = a.delta;
+    }
+    a.inv = 1.0, a.qmax = 1;
+    if (c.llr_type == kLlrI8)
+        a.inv = 1.0 / c.step, a.qmax = (1 << (c.q_bits - 1)) - 1;
+    if (a.work == 0) // (a code without columns)
+        return;
+    const size_t elem = llr_type_bytes(c.llr_type), in_row = bits_row_bytes(codeword_format, nc);
+    // frames per launch: the staging buffers stay modest and a launch's lanes below 2^31
+    const uint64_t sub = std::clamp<uint64_t>(std::min<uint64_t>((128ull << 20) / nc, ((1ull << 31) - 1) / a.work), 1, 1u << 20);
+    for (uint64_t done = 0; done < n; done += sub)
+    {
+        const uint64_t k = std::min(sub, n - done);
+        OutStage st;
+        a.codeword = codeword ? stage_input(static_cast<const char *>(codeword) + in_row * done, in_row * k, stage_in_, stream) : nullptr;
+        a.llr = st.route(llr ? static_cast<char *>(llr) + elem * done * nc : nullptr, stage_chan_[0], elem * k * nc);
+        a.received = st.route(received ? received + done * a.symbols : nullptr, stage_chan_[1], 8 * k * a.symbols);
+        a.frame0 = c.first_frame + done;
+        a.n = k;
+        check(launch_channel(a, m, c.llr_type, s), "channel_batch");
+        st.flush(s, &pin_out_);
+    }
+}
+
 void Engine::stream_rewind_encoder(uint64_t frames_back, void *stream)
 {
     if (!code_->has_G() || frames_back == 0 || counter_) // (counter-based noise: a codeword depends on its frame index alone)

@@ -352,6 +352,22 @@ class Engine
                         void *stream);
     // bit_errors[f] = transmitted positions at which rows f of a and b differ
     void bit_errors_batch(uint64_t n, const void *a, int a_format, const void *b, int b_format, uint32_t *bit_errors, void *stream);
+    // the channel between them (include/ldpc_amd.h, ldpc_hip_channel_batch; kernels_channel.hip): codeword[n][nc] (nullptr =
+    // all zero) -> llr[n][nc] of spec.llr_type and / or received[n][ceil(nct / m)], the noise that of the counter mode under
+    // (spec.seed, spec.first_frame + row).  Reads neither the stream interface's channel point nor its noise setting
+    struct ChannelSpec
+    {
+        int channel = 0; // kAwgn or kBsc
+        double x = 0.0;  // stream_begin's meaning
+        uint64_t seed = 0, first_frame = 0;
+        int bits_per_symbol = 1;
+        int llr_type = kLlrF64;
+        int q_bits = 0;    // kLlrI8 only
+        double step = 1.0; // kLlrI8 only
+    };
+    std::string channel_refusal(const ChannelSpec *spec, uint64_t n, int codeword_format, const void *llr, const double *received) const;
+    void channel_batch(const ChannelSpec *spec, uint64_t n, const void *codeword, int codeword_format, void *llr, double *received,
+                       void *stream);
 
     // ---- fused channel + decode on the reference's noise stream ----
     // set_channel_param semantics (channel.cpp:37-42): the stream restarts at frame 0.
@@ -538,6 +554,12 @@ class Engine
     const uint32_t *gf2_row_ptr_ = nullptr, *gf2_row_col_ = nullptr; // row CSR of H
     const uint64_t *gf2_tx_mask_ = nullptr; // the transmitted positions (bit_pos) as a mask over the columns
     DeviceBuffer gf2_info_, stage_in_b_, stage_gf2_[3];
+    // the channel call: the columns the channel does not write (column | kChannelShortened) and the ASK constellations of
+    // m = 2..4 (16 levels each, binary64), both uploaded by the first call; staging of host outputs
+    const uint32_t *chan_other_ = nullptr;
+    uint32_t chan_n_other_ = 0;
+    const double *chan_levels_ = nullptr;
+    DeviceBuffer stage_chan_[2];
     uint64_t gf2_sub_batch() const; // frames per launch: staging buffers stay modest, no grid dimension overflows
     // a host input of a batch call on the device (small ones through page-locked memory); a device pointer comes back as it is
     const void *stage_input(const void *src, size_t bytes, DeviceBuffer &stage, void *stream);

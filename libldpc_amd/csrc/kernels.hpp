@@ -376,6 +376,39 @@ struct Gf2BitErrorArgs
 };
 int launch_gf2_bit_errors(const Gf2BitErrorArgs &a, int a_format, int b_format, void *stream);
 
+// ---- channel and demapper for frames of bits (kernels_channel.hip; include/ldpc_amd.h, ldpc_hip_channel_batch): codeword bits
+// in, LLRs of element type `llr_type` out, the noise that of the counter mode (device_philox.hpp).  One lane owns one Philox
+// block of a frame: four symbols of m bits; the columns the channel does not write (punctured, shortened, unconnected) are
+// filled by further lanes of the same launch ----
+constexpr int kChannelMaxBitsPerSymbol = 4;
+constexpr uint32_t kChannelShortened = 0x80000000u; // ChannelArgs::other: the column is shortened (else it gets +0.0)
+struct ChannelArgs
+{
+    uint32_t nc, nct;
+    uint32_t symbols;         // S = ceil(nct / m)
+    uint32_t blocks;          // ceil(S / 4): the lanes of a frame that own a Philox block
+    uint32_t n_other;         // columns the channel does not write
+    uint32_t work;            // blocks + n_other: lanes per frame
+    const int *bit_pos;       // [nct] transmitted index -> column
+    const uint32_t *other;    // [n_other] column | kChannelShortened
+    const double *level;      // [2^m] the constellation, m >= 2 only (built on the host)
+    const void *codeword;     // [n][nc] bytes or [n][ceil(nc / 32)] words, nullptr = all zero
+    int32_t codeword_format;  // BitsFormat
+    int32_t channel;          // 1 AWGN, 2 BSC
+    void *llr;                // [n][nc] of llr_type, or nullptr
+    double *received;         // [n][S], or nullptr
+    uint32_t key[2];          // Philox key (seed low, seed high)
+    uint64_t frame0;          // row f is frame frame0 + f of the noise
+    double sigma, sigma2;     // AWGN
+    double eps, delta;        // BSC
+    double shorten;           // the LLR of a shortened column: 99999.9 / delta
+    double inv;               // kLlrI8: fl(1 / step)
+    int32_t qmax;             // kLlrI8: 2^(q_bits - 1) - 1
+    int32_t pad;
+    uint64_t n;               // n * work < 2^31
+};
+int launch_channel(const ChannelArgs &a, int bits_per_symbol, int llr_type, void *stream);
+
 // opt-in non-parity ternary min-sum, bit-sliced over 32 frames per workgroup (kernels_ternary.hip; include/ldpc_amd.h,
 // ldpc_hip_set_min_sum_ternary) on the general plan.  a.ms_* are not read.  With a.llr_out null the planes of A are left out
 // of the group's LDS (plan.hpp, ternary_lds_bytes)
