@@ -494,6 +494,87 @@ typedef struct
 int ldpc_hip_channel_batch(ldpc_hip_ctx *ctx, const ldpc_hip_channel *ch, uint64_t n, const void *codeword,
                            int codeword_format, void *llr, double *received, void *hip_stream);
 
+/* The third channel and its decoder, for a caller who holds received words with holes in them:
+     ldpc_hip_encode_batch -> ldpc_hip_erasure_channel_batch -> ldpc_hip_erasure_decode_batch -> ldpc_hip_syndrome_batch,
+     ldpc_hip_bit_errors_batch
+   (libldpc_amd/csrc/kernels_erasure.hip).  The common rules of this block hold for both calls: device or host buffers,
+   checks before the GPU naming the entry in ldpc_hip_last_error, n == 0 returns 0 after them, ordered on hip_stream, no
+   setting and no state of the stream interface read or changed.  Every output bit is determined.  W = ceil(nc / 32); a
+   packed row is the layout of hard_bits / LDPC_HIP_BITS_PACKED32.
+
+   The erasure channel.  codeword[n][nc], column order, LDPC_HIP_BITS_U8 or LDPC_HIP_BITS_PACKED32; NULL = the all-zero
+   codeword.  word_bits[n][W] and erased_bits[n][W]: either may be NULL, not both when n > 0.  Refused (host only, -1): an
+   unknown format, eps outside (0, 1) — the endpoints and a NaN included —, both outputs NULL with n > 0.
+   Per column c of frame first_frame + f:
+     - c = bit_pos[i] for an i < nct, a transmitted position: erased iff (w + 0.5) / 2^32 < eps (binary64, exact), w = word
+       i % 4 of Philox block i / 4 of the frame under tag 1 and `seed`: exactly the draw of LDPC_HIP_NOISE_COUNTER for the BEC
+       (ldpc_hip_set_noise);
+     - a punctured column (one listed as both punctured and shortened counts as shortened): erased;
+     - every other column — shortened ones, the surplus positions a column in both lists leaves in bit_pos, unconnected
+       ones —: known, carrying the codeword's bit of THAT column.  Deliberately not the stream channel's value for a
+       shortened column, which the reference reads from the transmitted-symbol vector at the column's index
+       (channel.cpp:222);
+     - word = the codeword's bit & ~erased everywhere; the bits of a row's last word from nc on are 0 in both outputs.
+   For a code without shortened columns erased_bits and word_bits are, bit for bit, (llr_in == 69) and (llr_in == 1) of
+   ldpc_hip_stream_decode on the BEC under LDPC_HIP_NOISE_COUNTER, the same eps and seed, for the stream's frames
+   first_frame + f and their codewords.
+   How it runs: one launch per 2^31 / W frames at most, no LDS; a lane owns one output word of a frame — 32 columns — and
+   writes it once, with the Philox block of the last transmitted index in registers: where bit_pos is consecutive every
+   block is computed once. */
+int ldpc_hip_erasure_channel_batch(ldpc_hip_ctx *ctx, double eps, uint64_t seed, uint64_t first_frame, uint64_t n,
+                                   const void *codeword, int codeword_format, uint32_t *word_bits, uint32_t *erased_bits,
+                                   void *hip_stream);
+/* The erasure decoder (flooding, peeling): word[n][nc] and erased[n][nc] in, both in `format` (LDPC_HIP_BITS_U8: a non-zero
+   byte is 1 / erased; LDPC_HIP_BITS_PACKED32: the bits of a row's last word from nc on are ignored); word_out[n][W],
+   erased_out[n][W], iters[n] and unresolved[n] out, each may be NULL.  It needs no generator matrix, no codeword and no
+   knowledge of what was sent (the stream's BEC decoder compares every message with the transmitted bit).  Refused (host
+   only, -1): an unknown format, a bit of `flags` other than the two below, a missing input with n > 0, and a code whose
+   group does not fit (ldpc_hip_erasure_lds_bytes returns -1; there is no other kernel).
+   Per frame, E the set of erased columns and V the set of columns of value 1; a value under an erased bit is ignored:
+   V := word & ~E on entry.
+     1. Pass I = 0 .. iterations - 1, while the frame is active.  For every check node r, over the entries of H as the
+        library loaded it (an entry listed twice is two edges):
+          c0[r] = some edge's column is in E;  c1[r] = two or more edges' columns are in E;
+          xa[r] = XOR over the edges of (column in V).
+     2. For every column v in E: res = OR over its edges (r, v) of (c0[r] & ~c1[r]), val = OR over them of (c0[r] & ~c1[r] &
+        xa[r]).  If res, v leaves E, and enters V iff val.  All of step 2 reads the c0 / c1 / xa of step 1: a flooding pass.
+        (For a codeword with erasures every resolving check node agrees; the OR is the rule for inconsistent input.)
+     3. The frame still holds an erasure iff E is non-empty over all nc columns, punctured, unconnected and degree-0 ones
+        included.  With LDPC_HIP_ERASURE_EARLY_TERM a frame whose pass left E empty stops; with
+        LDPC_HIP_ERASURE_STOP_STALLED a frame also stops after a pass that removed nothing from E (no later pass would).  A
+        stopped frame's outputs are frozen while other frames go on.
+     4. iters[f]: with LDPC_HIP_ERASURE_EARLY_TERM the number of passes the frame ran after which it still held an erasure —
+        the stream decoder's convention (decoder.cpp:169-186): resolved in pass I gives I; without it the number of passes
+        the frame ran: `iterations` with neither flag.  A frame stopped as stalled after pass I gives I + 1 either way.
+     5. unresolved[f] = |E| at the end, erased_out = E, word_out = V; the bits of a row's last word from nc on are 0.
+     6. iterations == 0: word_out = word & ~erased, erased_out = erased, iters = 0, unresolved = |E|.  (Not the stream
+        decoder's all-zero rows: here the inputs are the caller's data.)
+     7. A frame's results do not depend on which frames share its call.
+   Identity: after every pass E and V are those of the message-passing decoder of decoder.cpp:91-192 run without its genie
+   (an erased variable node of degree 1 sends an erasure); fed the outputs of ldpc_hip_erasure_channel_batch for the
+   stream's codewords, iters, erased_out and word_out equal the stream's iters, (llr_out == 69) and (llr_out == 1) under
+   ldpc_hip_set_bec_compat(0) for iterations > 0.
+   How it runs: byte input is packed by one small launch per operand in front; one workgroup of 512 threads decodes 32
+   consecutive frames bit-sliced, all state in LDS, one launch per 2^20 frames at most. */
+enum
+{
+    LDPC_HIP_ERASURE_EARLY_TERM = 1,
+    LDPC_HIP_ERASURE_STOP_STALLED = 2
+};
+int ldpc_hip_erasure_decode_batch(ldpc_hip_ctx *ctx, uint32_t iterations, int flags, uint64_t n, const void *word,
+                                  const void *erased, int format, uint32_t *word_out, uint32_t *erased_out, uint32_t *iters,
+                                  uint32_t *unresolved, void *hip_stream);
+/* LDS bytes one 32-frame group of ldpc_hip_erasure_decode_batch takes on this context's code (host only; worked out once
+   per context), -1 for a code the decoder refuses: a group beyond 160 KB or more than 524 288 columns.
+     bytes = 4 (2 (nc + 1) + 2 (mc + 1)) + 8 C + 144, rounded up to 16
+   — per column its erased word and its value word, per check node TWO words, not three: the kernel stores c0 & ~c1 and
+   c0 & ~c1 & xa, all that step 2 reads; one zero word behind each of the four arrays (what a padded list entry points
+   at); 8 bytes for each of the C chunks the graph is cut into, C = ceil(mc / 64) + ceil(n8 / 16) + ceil((nc - n8) / 64)
+   with n8 the columns of degree >= 8; 144 bytes of votes and counts.  tests/golden/h.txt: 17 888 bytes; four groups of
+   512 threads, the 32 waves a CU holds, take 70 KB of its 160.  (Within 160 KB nc and mc stay below 20 480: every index
+   of the graph's lists is 16 bits.) */
+int64_t ldpc_hip_erasure_lds_bytes(const ldpc_hip_ctx *ctx);
+
 /* channel point x of stream mt19937_64(seed): set_channel_param semantics, frame position := 0 */
 int ldpc_hip_stream_begin(ldpc_hip_ctx *ctx, int channel, uint64_t seed, double x);
 /* advance the stream by n frames without decoding them */

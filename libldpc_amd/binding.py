@@ -106,6 +106,12 @@ def load_library(path=LIB_PATH):
     L.ldpc_hip_bit_errors_batch.argtypes = [vp, u64, vp, i32, vp, i32, vp, vp]
     L.ldpc_hip_channel_batch.restype = i32
     L.ldpc_hip_channel_batch.argtypes = [vp, ct.POINTER(ldpc_hip_channel), u64, vp, i32, vp, vp, vp]
+    L.ldpc_hip_erasure_channel_batch.restype = i32
+    L.ldpc_hip_erasure_channel_batch.argtypes = [vp, ct.c_double, u64, u64, u64, vp, i32, vp, vp, vp]
+    L.ldpc_hip_erasure_decode_batch.restype = i32
+    L.ldpc_hip_erasure_decode_batch.argtypes = [vp, ct.c_uint32, i32, u64, vp, vp, i32, vp, vp, vp, vp, vp]
+    L.ldpc_hip_erasure_lds_bytes.restype = ct.c_int64
+    L.ldpc_hip_erasure_lds_bytes.argtypes = [vp]
     L.ldpc_hip_stream_begin.restype = i32
     L.ldpc_hip_stream_begin.argtypes = [vp, i32, u64, ct.c_double]
     L.ldpc_hip_stream_skip.restype = i32
@@ -557,6 +563,64 @@ class HipDecoder:
         self._check(self.lib.ldpc_hip_channel_batch(self.ctx, ct.byref(ch), n, _ptr(codeword), fmt, _ptr(bufs.get("llr")),
                                                     _ptr(bufs.get("received")), stream), "ldpc_hip_channel_batch")
         return bufs
+
+    def _check_bufs(self, what, bufs, spec):
+        for name, buf in bufs.items():
+            shape, dt = spec[name]
+            if str(buf.dtype).replace("torch.", "") != np.dtype(dt).name:
+                raise TypeError(f"{what}: {name} is {np.dtype(dt).name}, not {buf.dtype}")
+            if tuple(buf.shape) != shape:
+                raise ValueError(f"{what}: {name} is {shape}, not {tuple(buf.shape)}")
+
+    def erasure_channel_batch(self, codeword, eps, seed=0, first_frame=0, frames=None, want=("word", "erased"), out=None, stream=None):
+        """codeword[n][nc] (uint8 or packed uint32, column order; None = `frames` all-zero codewords) through the erasure channel
+        of probability eps under the counter noise of (seed, first_frame + row) -> "word" and / or "erased", both packed uint32
+        [n][ceil(nc / 32)]: erased marks the holes (punctured columns always), word is the codeword where it is not erased
+        (include/ldpc_amd.h, ldpc_hip_erasure_channel_batch).  codeword and the buffers in `out` are numpy arrays or torch
+        tensors, host or device; a wrong dtype raises TypeError, a wrong shape ValueError."""
+        if codeword is None:
+            if frames is None:
+                raise ValueError("erasure_channel_batch: codeword=None (all-zero codewords) needs frames=")
+            n, fmt = int(frames), 0
+        else:
+            n, fmt = self._bits(codeword, self.nc, "erasure_channel_batch")
+            if frames is not None and int(frames) != n:
+                raise ValueError(f"erasure_channel_batch: frames={frames} against {n} rows")
+        packed = ((n, (self.nc + 31) // 32), np.uint32)
+        spec = {"word": packed, "erased": packed}
+        bufs = self._wanted(want, out, spec)
+        self._check_bufs("erasure_channel_batch", bufs, spec)
+        self._check(self.lib.ldpc_hip_erasure_channel_batch(self.ctx, float(eps), int(seed), int(first_frame), n, _ptr(codeword), fmt,
+                                                            _ptr(bufs.get("word")), _ptr(bufs.get("erased")), stream),
+                    "ldpc_hip_erasure_channel_batch")
+        return bufs
+
+    ERASURE_EARLY_TERM, ERASURE_STOP_STALLED = 1, 2
+
+    def erasure_decode_batch(self, word, erased, iterations=50, early_term=True, stop_stalled=False,
+                             want=("word", "erased", "iters", "unresolved"), out=None, stream=None):
+        """word[n][nc] and erased[n][nc] (both uint8 or both packed uint32) -> what peeling recovers: "word" and "erased" (packed
+        uint32 [n][ceil(nc / 32)]: the values and the holes that are left), "iters" and "unresolved" (uint32 [n]: passes, holes
+        left).  No generator and no codeword is needed.  early_term: a frame without holes stops; stop_stalled: so does one whose
+        pass filled none (include/ldpc_amd.h, ldpc_hip_erasure_decode_batch).  Inputs and the buffers in `out` are numpy arrays
+        or torch tensors, host or device."""
+        n, fmt = self._bits(word, self.nc, "erasure_decode_batch")
+        ne, fe = self._bits(erased, self.nc, "erasure_decode_batch")
+        if (n, fmt) != (ne, fe):
+            raise ValueError(f"erasure_decode_batch: word is {tuple(word.shape)} {word.dtype}, erased is {tuple(erased.shape)} {erased.dtype}")
+        packed = ((n, (self.nc + 31) // 32), np.uint32)
+        spec = {"word": packed, "erased": packed, "iters": ((n,), np.uint32), "unresolved": ((n,), np.uint32)}
+        bufs = self._wanted(want, out, spec)
+        self._check_bufs("erasure_decode_batch", bufs, spec)
+        flags = (self.ERASURE_EARLY_TERM if early_term else 0) | (self.ERASURE_STOP_STALLED if stop_stalled else 0)
+        self._check(self.lib.ldpc_hip_erasure_decode_batch(self.ctx, int(iterations), flags, n, _ptr(word), _ptr(erased), fmt,
+                                                           _ptr(bufs.get("word")), _ptr(bufs.get("erased")), _ptr(bufs.get("iters")),
+                                                           _ptr(bufs.get("unresolved")), stream), "ldpc_hip_erasure_decode_batch")
+        return bufs
+
+    def erasure_lds_bytes(self):
+        """LDS bytes one 32-frame group of erasure_decode_batch takes (-1: the decoder does not take the code)."""
+        return int(self.lib.ldpc_hip_erasure_lds_bytes(self.ctx))
 
     def stream_begin(self, channel, seed, x):
         """Channel point x of mt19937_64(seed); also resets the encoder (a fresh channel object)."""

@@ -461,6 +461,30 @@ int ldpc_hip_channel_batch(ldpc_hip_ctx *ctx, const ldpc_hip_channel *ch, uint64
     });
 }
 
+int ldpc_hip_erasure_channel_batch(ldpc_hip_ctx *ctx, double eps, uint64_t seed, uint64_t first_frame, uint64_t n, const void *codeword,
+                                   int codeword_format, uint32_t *word_bits, uint32_t *erased_bits, void *hip_stream)
+{
+    return guarded([&] {
+        ctx->eng->erasure_channel_batch(eps, seed, first_frame, n, codeword, codeword_format, word_bits, erased_bits, hip_stream);
+    });
+}
+
+int ldpc_hip_erasure_decode_batch(ldpc_hip_ctx *ctx, uint32_t iterations, int flags, uint64_t n, const void *word, const void *erased,
+                                  int format, uint32_t *word_out, uint32_t *erased_out, uint32_t *iters, uint32_t *unresolved,
+                                  void *hip_stream)
+{
+    return guarded([&] {
+        ctx->eng->erasure_decode_batch(iterations, flags, n, word, erased, format, word_out, erased_out, iters, unresolved, hip_stream);
+    });
+}
+
+int64_t ldpc_hip_erasure_lds_bytes(const ldpc_hip_ctx *ctx)
+{
+    int64_t bytes = -1; // (the tables are built on the host at the first call; -1 for a code the decoder refuses)
+    guarded([&] { bytes = ctx->eng->erasure_lds_bytes(); });
+    return bytes;
+}
+
 int64_t ldpc_hip_layered_fixed_direct_lds_bytes(const ldpc_hip_ctx *ctx)
 {
     int64_t bytes = -1; // (the plan builder allocates; -1 for every code the layered plan refuses)

@@ -1767,6 +1767,207 @@ void Engine::channel_batch(const ChannelSpec *spec, uint64_t n, const void *code
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The erasure channel and the genie-free erasure decoder (kernels_erasure.hip)
+std::string Engine::erasure_channel_refusal(double eps, uint64_t n, int codeword_format, const void *word_bits, const void *erased_bits) const
+{
+    const std::string who = "ldpc_hip_erasure_channel_batch: ";
+    if (std::string why = bits_format_refusal("ldpc_hip_erasure_channel_batch", "codeword", codeword_format); !why.empty())
+        return why;
+    if (!(eps > 0.0 && eps < 1.0))
+        return who + "the erasure probability eps is outside (0, 1)";
+    if (n && !word_bits && !erased_bits)
+        return who + "neither word_bits nor erased_bits is wanted";
+    return "";
+}
+
+void Engine::erasure_channel_batch(double eps, uint64_t seed, uint64_t first_frame, uint64_t n, const void *codeword, int codeword_format,
+                                   uint32_t *word_bits, uint32_t *erased_bits, void *stream)
+{
+    if (const std::string why = erasure_channel_refusal(eps, n, codeword_format, word_bits, erased_bits); !why.empty())
+        throw std::runtime_error(why);
+    if (n == 0)
+        return;
+    bind_device();
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint64_t nc = static_cast<uint64_t>(plan_.nc), words = (nc + 31) / 32;
+    if (!era_col_tx_)
+    {
+        // what each column is, by output word: transmitted (its index i < nct), punctured (erased), anything else (known) —
+        // plan.cpp, rank_kind: a column in both lists counts as shortened, the surplus entries of bit_pos as never written
+        std::vector<uint32_t> tx(32 * words, kErasureColPad);
+        for (uint64_t c = 0; c < nc; ++c)
+            tx[(c % 32) * words + c / 32] = plan_.rank_kind[plan_.col_rank[c]] == 1 ? kErasureColErased : kErasureColKnown;
+        for (int i = 0; i < plan_.nct; ++i)
+        {
+            const uint64_t c = static_cast<uint64_t>(code_->bit_pos[i]);
+            tx[(c % 32) * words + c / 32] = static_cast<uint32_t>(i);
+        }
+        era_col_tx_ = static_cast<const uint32_t *>(upload_table(tx.data(), tx.size() * 4, "columns of the erasure channel"));
+    }
+    ErasureChannelArgs a{};
+    a.nc = static_cast<uint32_t>(nc), a.words = static_cast<uint32_t>(words);
+    a.col_tx = era_col_tx_;
+    a.codeword_format = codeword_format;
+    a.key[0] = static_cast<uint32_t>(seed), a.key[1] = static_cast<uint32_t>(seed >> 32);
+    a.eps = eps;
+    const size_t in_row = bits_row_bytes(codeword_format, nc);
+    // frames per launch: the staging buffers stay modest and a launch's lanes below 2^31
+    const uint64_t sub = std::clamp<uint64_t>(std::min<uint64_t>((128ull << 20) / nc, ((1ull << 31) - 1) / words), 1, 1u << 20);
+    for (uint64_t done = 0; done < n; done += sub)
+    {
+        const uint64_t k = std::min(sub, n - done);
+        OutStage st;
+        a.codeword = codeword ? stage_input(static_cast<const char *>(codeword) + in_row * done, in_row * k, stage_in_, stream) : nullptr;
+        a.word_bits = st.route(word_bits ? word_bits + done * words : nullptr, stage_era_[0], 4 * k * words);
+        a.erased_bits = st.route(erased_bits ? erased_bits + done * words : nullptr, stage_era_[1], 4 * k * words);
+        a.frame0 = first_frame + done;
+        a.n = k;
+        check(launch_erasure_channel(a, s), "erasure_channel_batch");
+        st.flush(s, &pin_out_);
+    }
+}
+
+// The graph cut into chunks of 64 lanes (kernels.hpp, ErasureDecodeArgs).  Host only.
+const Engine::ErasureTables &Engine::erasure_tables()
+{
+    if (erasure_tables_)
+        return *erasure_tables_;
+    ErasureTables t;
+    const SparseGF2 &H = code_->H;
+    const uint32_t nc = static_cast<uint32_t>(plan_.nc), mc = static_cast<uint32_t>(plan_.mc);
+    const auto cdeg = [&](uint32_t r) { return static_cast<uint32_t>(H.rptr[r + 1] - H.rptr[r]); };
+    const auto vdeg = [&](uint32_t c) { return static_cast<uint32_t>(H.cptr[c + 1] - H.cptr[c]); };
+    std::vector<uint32_t> thin, wide;
+    for (uint32_t c = 0; c < nc; ++c)
+        (vdeg(c) >= static_cast<uint32_t>(kErasureWideDegree) ? wide : thin).push_back(c);
+    t.cn_chunks = (mc + 63) / 64;
+    t.vn_chunks = static_cast<uint32_t>((wide.size() + 15) / 16 + (thin.size() + 63) / 64);
+    const size_t bytes = ldpc_amd::erasure_lds_bytes(nc, mc, static_cast<size_t>(t.cn_chunks) + t.vn_chunks);
+    if (nc <= 524288u && bytes <= kCuLdsBytes) // (8 (nc + 1) and 8 (mc + 1) within 160 KB: every index fits 16 bits)
+    {
+        t.lds_bytes = static_cast<int64_t>(bytes);
+        // check nodes by degree, so that a chunk's lanes make the same trips; the slot a check node gets names it to the columns
+        std::vector<uint32_t> order(mc), slot(mc);
+        for (uint32_t r = 0; r < mc; ++r)
+            order[r] = r;
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return cdeg(x) < cdeg(y); });
+        for (uint32_t q = 0; q < mc; ++q)
+            slot[order[q]] = q;
+        for (uint32_t k = 0; k < t.cn_chunks; ++k)
+        {
+            const uint32_t first = 64 * k, count = std::min(64u, mc - first);
+            uint32_t trips = 0;
+            for (uint32_t l = 0; l < count; ++l)
+                trips = std::max(trips, cdeg(order[first + l]));
+            const size_t off = t.cn_entries.size();
+            t.desc.push_back(static_cast<uint32_t>(off)), t.desc.push_back(trips);
+            t.cn_entries.resize(off + 64 * static_cast<size_t>(trips), static_cast<uint16_t>(nc));
+            for (uint32_t l = 0; l < count; ++l)
+                for (uint32_t j = 0, r = order[first + l]; j < cdeg(r); ++j)
+                    t.cn_entries[off + 64 * j + l] = static_cast<uint16_t>(H.rcol[H.rptr[r] + j]);
+        }
+        // columns: the wide ones first (four lanes each, 16 to a chunk), then the thin ones, each kind by degree
+        const auto by_degree = [&](uint32_t x, uint32_t y) { return vdeg(x) > vdeg(y); };
+        std::stable_sort(wide.begin(), wide.end(), by_degree);
+        std::stable_sort(thin.begin(), thin.end(), by_degree);
+        const auto add = [&](const std::vector<uint32_t> &cols, uint32_t per_chunk, uint32_t lanes_per_col) {
+            for (size_t first = 0; first < cols.size(); first += per_chunk)
+            {
+                const uint32_t count = static_cast<uint32_t>(std::min<size_t>(per_chunk, cols.size() - first));
+                uint32_t trips = 0;
+                for (uint32_t i = 0; i < count; ++i)
+                    trips = std::max(trips, (vdeg(cols[first + i]) + lanes_per_col - 1) / lanes_per_col);
+                const size_t off = t.vn_entries.size(), at = t.vn_col.size();
+                t.desc.push_back(static_cast<uint32_t>(off)), t.desc.push_back(trips | (lanes_per_col > 1 ? kErasureWideChunk : 0u));
+                t.vn_entries.resize(off + 64 * static_cast<size_t>(trips), static_cast<uint16_t>(mc));
+                t.vn_col.resize(at + 64, static_cast<uint16_t>(nc));
+                for (uint32_t i = 0; i < count; ++i)
+                {
+                    const uint32_t c = cols[first + i];
+                    for (uint32_t sub = 0; sub < lanes_per_col; ++sub)
+                        t.vn_col[at + lanes_per_col * i + sub] = static_cast<uint16_t>(c);
+                    for (uint32_t p = 0; p < vdeg(c); ++p)
+                        t.vn_entries[off + 64 * (p / lanes_per_col) + lanes_per_col * i + p % lanes_per_col] =
+                            static_cast<uint16_t>(slot[H.crow[H.cptr[c] + p]]);
+                }
+            }
+        };
+        add(wide, 16, 4);
+        add(thin, 64, 1);
+    }
+    erasure_tables_ = std::move(t);
+    return *erasure_tables_;
+}
+
+int64_t Engine::erasure_lds_bytes() { return erasure_tables().lds_bytes; }
+
+std::string Engine::erasure_decode_refusal(int flags, int format)
+{
+    const std::string who = "ldpc_hip_erasure_decode_batch: ";
+    if (std::string why = bits_format_refusal("ldpc_hip_erasure_decode_batch", "word and erased", format); !why.empty())
+        return why;
+    if (flags & ~(kErasureEarlyTerm | kErasureStopStalled))
+        return who + "unknown flags " + std::to_string(flags) + " (1 = LDPC_HIP_ERASURE_EARLY_TERM, 2 = LDPC_HIP_ERASURE_STOP_STALLED)";
+    if (plan_.nc > 524288)
+        return who + "more than 524 288 columns";
+    if (erasure_lds_bytes() < 0)
+        return who + "a group of 32 frames does not fit the 160 KB of LDS of a CU (ldpc_hip_erasure_lds_bytes; there is no other kernel)";
+    return "";
+}
+
+void Engine::erasure_decode_batch(uint32_t iterations, int flags, uint64_t n, const void *word, const void *erased, int format,
+                                  uint32_t *word_out, uint32_t *erased_out, uint32_t *iters, uint32_t *unresolved, void *stream)
+{
+    if (const std::string why = erasure_decode_refusal(flags, format); !why.empty())
+        throw std::runtime_error(why);
+    if (n && (!word || !erased))
+        throw std::runtime_error("ldpc_hip_erasure_decode_batch: null word or erased");
+    if (n == 0 || (!word_out && !erased_out && !iters && !unresolved))
+        return;
+    bind_device();
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const ErasureTables &t = erasure_tables();
+    if (!era_desc_)
+    {
+        era_cn_entries_ = static_cast<const uint16_t *>(upload_table(t.cn_entries.data(), t.cn_entries.size() * 2, "erasure graph"));
+        era_vn_entries_ = static_cast<const uint16_t *>(upload_table(t.vn_entries.data(), t.vn_entries.size() * 2, "erasure graph"));
+        era_vn_col_ = static_cast<const uint16_t *>(upload_table(t.vn_col.data(), t.vn_col.size() * 2, "erasure graph"));
+        era_desc_ = static_cast<const uint32_t *>(upload_table(t.desc.data(), t.desc.size() * 4, "erasure graph")); // last: the mark
+    }
+    const uint64_t nc = static_cast<uint64_t>(plan_.nc), words = (nc + 31) / 32;
+    ErasureDecodeArgs a{};
+    a.nc = static_cast<uint32_t>(nc), a.mc = static_cast<uint32_t>(plan_.mc), a.words = static_cast<uint32_t>(words);
+    a.cn_chunks = t.cn_chunks, a.vn_chunks = t.vn_chunks;
+    a.iterations = iterations, a.flags = flags;
+    a.lds_bytes = static_cast<uint32_t>(t.lds_bytes);
+    a.desc = era_desc_, a.cn_entries = era_cn_entries_, a.vn_entries = era_vn_entries_, a.vn_col = era_vn_col_;
+    const uint64_t sub = gf2_sub_batch();
+    const size_t in_row = bits_row_bytes(format, nc);
+    for (uint64_t done = 0; done < n; done += sub)
+    {
+        const uint64_t m = std::min(sub, n - done);
+        const void *src[2] = {stage_input(static_cast<const char *>(word) + in_row * done, in_row * m, stage_in_, stream),
+                              stage_input(static_cast<const char *>(erased) + in_row * done, in_row * m, stage_in_b_, stream)};
+        if (format == kBitsU8) // bytes: packed by one small launch each in front
+            for (int i = 0; i < 2; ++i)
+            {
+                uint32_t *packed = static_cast<uint32_t *>(era_packed_[i].reserve(4 * m * words));
+                check(launch_pack_hard(static_cast<const uint8_t *>(src[i]), m, static_cast<int>(nc), packed, s), "erasure_decode_batch (pack)");
+                src[i] = packed;
+            }
+        OutStage st;
+        a.word = static_cast<const uint32_t *>(src[0]), a.erased = static_cast<const uint32_t *>(src[1]);
+        a.word_out = st.route(word_out ? word_out + done * words : nullptr, stage_era_[0], 4 * m * words);
+        a.erased_out = st.route(erased_out ? erased_out + done * words : nullptr, stage_era_[1], 4 * m * words);
+        a.iters = st.route(iters ? iters + done : nullptr, stage_era_[2], 4 * m);
+        a.unresolved = st.route(unresolved ? unresolved + done : nullptr, stage_era_[3], 4 * m);
+        a.n = m;
+        check(launch_erasure_decode(a, s), "erasure_decode_batch");
+        st.flush(s, &pin_out_);
+    }
+}
+
 void Engine::stream_rewind_encoder(uint64_t frames_back, void *stream)
 {
     if (!code_->has_G() || frames_back == 0 || counter_) // (counter-based noise: a codeword depends on its frame index alone)

@@ -368,6 +368,17 @@ class Engine
     std::string channel_refusal(const ChannelSpec *spec, uint64_t n, int codeword_format, const void *llr, const double *received) const;
     void channel_batch(const ChannelSpec *spec, uint64_t n, const void *codeword, int codeword_format, void *llr, double *received,
                        void *stream);
+    // the erasure channel and the genie-free erasure decoder behind it (include/ldpc_amd.h, ldpc_hip_erasure_channel_batch /
+    // ldpc_hip_erasure_decode_batch; kernels_erasure.hip): packed words and erasure masks [n][ceil(nc / 32)] out of the
+    // channel, into the decoder and out of it.  Host only: what each call refuses, empty when it is taken; the LDS of one
+    // 32-frame group, -1 for a code the decoder refuses
+    std::string erasure_channel_refusal(double eps, uint64_t n, int codeword_format, const void *word_bits, const void *erased_bits) const;
+    void erasure_channel_batch(double eps, uint64_t seed, uint64_t first_frame, uint64_t n, const void *codeword, int codeword_format,
+                               uint32_t *word_bits, uint32_t *erased_bits, void *stream);
+    std::string erasure_decode_refusal(int flags, int format);
+    int64_t erasure_lds_bytes();
+    void erasure_decode_batch(uint32_t iterations, int flags, uint64_t n, const void *word, const void *erased, int format,
+                              uint32_t *word_out, uint32_t *erased_out, uint32_t *iters, uint32_t *unresolved, void *stream);
 
     // ---- fused channel + decode on the reference's noise stream ----
     // set_channel_param semantics (channel.cpp:37-42): the stream restarts at frame 0.
@@ -560,6 +571,21 @@ class Engine
     uint32_t chan_n_other_ = 0;
     const double *chan_levels_ = nullptr;
     DeviceBuffer stage_chan_[2];
+    // the erasure calls: the channel's column table ([32][ceil(nc / 32)], kernels.hpp ErasureChannelArgs) and the decoder's
+    // chunked graph (kernels.hpp ErasureDecodeArgs), each built on the host at the first call that needs it and uploaded by
+    // the first one that launches; the packed images of byte input; staging of host outputs
+    struct ErasureTables
+    {
+        std::vector<uint32_t> desc;
+        std::vector<uint16_t> cn_entries, vn_entries, vn_col;
+        uint32_t cn_chunks = 0, vn_chunks = 0;
+        int64_t lds_bytes = -1; // -1: the decoder does not take the code
+    };
+    std::optional<ErasureTables> erasure_tables_;
+    const ErasureTables &erasure_tables();
+    const uint32_t *era_col_tx_ = nullptr, *era_desc_ = nullptr;
+    const uint16_t *era_cn_entries_ = nullptr, *era_vn_entries_ = nullptr, *era_vn_col_ = nullptr;
+    DeviceBuffer era_packed_[2], stage_era_[4];
     uint64_t gf2_sub_batch() const; // frames per launch: staging buffers stay modest, no grid dimension overflows
     // a host input of a batch call on the device (small ones through page-locked memory); a device pointer comes back as it is
     const void *stage_input(const void *src, size_t bytes, DeviceBuffer &stage, void *stream);

@@ -409,6 +409,72 @@ struct ChannelArgs
 };
 int launch_channel(const ChannelArgs &a, int bits_per_symbol, int llr_type, void *stream);
 
+// ---- erasure channel and genie-free erasure decoder for frames of bits (kernels_erasure.hip; include/ldpc_amd.h,
+// ldpc_hip_erasure_channel_batch / ldpc_hip_erasure_decode_batch).  Rows are packed as hard_bits is ----
+// the channel: one lane owns one output word (32 columns) of one frame and writes it once; col_tx says what each column is
+constexpr uint32_t kErasureColErased = 0xFFFFFFFFu; // punctured: always erased
+constexpr uint32_t kErasureColKnown = 0xFFFFFFFEu;  // neither transmitted nor punctured: carries the codeword's bit
+constexpr uint32_t kErasureColPad = 0xFFFFFFFDu;    // beyond nc: both output bits 0
+struct ErasureChannelArgs
+{
+    uint32_t nc, words;       // words = ceil(nc / 32)
+    const uint32_t *col_tx;   // [32][words]: column 32 w + b at [b * words + w]: its index among the transmitted bits, or one of the three marks
+    const void *codeword;     // [n][nc] bytes or [n][words] words, nullptr = all zero
+    int32_t codeword_format;  // BitsFormat
+    int32_t pad;
+    uint32_t *word_bits;      // [n][words] or nullptr
+    uint32_t *erased_bits;    // [n][words] or nullptr
+    uint32_t key[2];          // Philox key (seed low, seed high)
+    uint64_t frame0;          // row f is frame frame0 + f of the noise
+    double eps;
+    uint64_t n;               // n * words < 2^31
+};
+int launch_erasure_channel(const ErasureChannelArgs &a, void *stream);
+// the decoder: one workgroup of kErasureThreads decodes kErasureFrames consecutive frames, bit f of every LDS word is frame f.
+// The graph as work for whole waves, built once per context (engine.cpp, erasure_tables): a CHUNK is 64 lanes' worth of nodes
+// and `trips` entries per lane, entry j of lane l at entries[offset + 64 j + l] (adjacent lanes read adjacent indices); a
+// lane with fewer edges is padded with the index of a word that is always zero (column nc / check node mc).
+//   check-node chunks   64 check nodes (sorted by degree; which check node a lane holds does not matter to any output), the
+//                       entries are columns;
+//   column chunks       64 columns of degree < kErasureWideDegree, or 16 columns of degree >= kErasureWideDegree on four lanes
+//                       each (lane 4 i + s takes the edges s, s + 4, ...), the entries are check-node slots; vn_col names the
+//                       lane's column (nc = none).  Every column 0..nc-1 is named by exactly one lane with s == 0.
+// desc[2 k], desc[2 k + 1] = {offset, trips | kErasureWideChunk} of chunk k, the check-node chunks first
+constexpr int kErasureFrames = 32, kErasureThreads = 512, kErasureWideDegree = 8;
+constexpr uint32_t kErasureWideChunk = 0x80000000u;
+constexpr uint32_t kErasureVoteWords = 36; // still[2], changed[2], unresolved counts[32]
+// LDS of one group (include/ldpc_amd.h, ldpc_hip_erasure_lds_bytes): E[nc + 1] V[nc + 1] (the last word of each the zero
+// word), ONE[mc + 1] VAL[mc + 1] (likewise), the chunk descriptors and the votes
+constexpr size_t erasure_lds_bytes(size_t nc, size_t mc, size_t chunks)
+{
+    return (4 * (2 * (nc + 1) + 2 * (mc + 1)) + 8 * chunks + 4 * kErasureVoteWords + 15) / 16 * 16;
+}
+enum ErasureFlags : int
+{
+    kErasureEarlyTerm = 1,
+    kErasureStopStalled = 2,
+};
+struct ErasureDecodeArgs
+{
+    uint32_t nc, mc, words;      // words = ceil(nc / 32)
+    uint32_t cn_chunks, vn_chunks;
+    uint32_t iterations;
+    int32_t flags;               // ErasureFlags
+    uint32_t lds_bytes;          // erasure_lds_bytes(nc, mc, cn_chunks + vn_chunks)
+    const uint32_t *desc;        // [2 (cn_chunks + vn_chunks)]
+    const uint16_t *cn_entries;  // columns, <= nc
+    const uint16_t *vn_entries;  // check-node slots, <= mc
+    const uint16_t *vn_col;      // [64 vn_chunks]
+    const uint32_t *word;        // [n][words]
+    const uint32_t *erased;      // [n][words]
+    uint32_t *word_out;          // [n][words] or nullptr
+    uint32_t *erased_out;        // [n][words] or nullptr
+    uint32_t *iters;             // [n] or nullptr
+    uint32_t *unresolved;        // [n] or nullptr
+    uint64_t n;                  // at most 2^31 - 1 groups
+};
+int launch_erasure_decode(const ErasureDecodeArgs &a, void *stream);
+
 // opt-in non-parity ternary min-sum, bit-sliced over 32 frames per workgroup (kernels_ternary.hip; include/ldpc_amd.h,
 // ldpc_hip_set_min_sum_ternary) on the general plan.  a.ms_* are not read.  With a.llr_out null the planes of A are left out
 // of the group's LDS (plan.hpp, ternary_lds_bytes)
