@@ -575,6 +575,66 @@ int ldpc_hip_erasure_decode_batch(ldpc_hip_ctx *ctx, uint32_t iterations, int fl
    of the graph's lists is 16 bits.) */
 int64_t ldpc_hip_erasure_lds_bytes(const ldpc_hip_ctx *ctx);
 
+/* Maximum-likelihood erasure decoding: every erased bit that the parity checks determine
+   (libldpc_amd/csrc/kernels_erasure_solve.hip).  Peeling stops at the first stopping set; the erased bits still satisfy a
+   linear system over GF(2), and this call solves it.  The common rules of this block hold: device or host buffers, checks
+   before the GPU naming the entry in ldpc_hip_last_error, n == 0 returns 0 after them, every output may be NULL, ordered on
+   hip_stream, no setting and no state of the stream interface read or changed, a frame's results do not depend on which
+   frames share its call, every output bit is determined.
+   word[n][nc] and erased[n][nc] in, both in `format`, exactly as ldpc_hip_erasure_decode_batch reads them (LDPC_HIP_BITS_U8:
+   a non-zero byte is 1 / erased; LDPC_HIP_BITS_PACKED32: the bits of a row's last word from nc on are ignored; a value
+   under an erased bit is ignored); word_out[n][W], erased_out[n][W], unresolved[n], rank[n] and status[n] out.  Refused
+   (host only, -1): an unknown format, a missing input with n > 0, max_unknowns == 0, and a code and cap whose frame does not
+   fit (ldpc_hip_erasure_solve_lds_bytes returns -1; there is no other kernel).  max_unknowns above nc counts as nc.
+   Per frame, with E the erased columns on entry and V = word & ~E:
+     1. The matrix.  M[r][c] = (the number of times (r, c) is listed in H as the library loaded it) mod 2: an entry listed
+        twice cancels.  This is GF(2) — deliberately NOT the rule of ldpc_hip_erasure_decode_batch, where an entry listed twice
+        is two edges.
+     2. The solutions.  S = the set of x in GF(2)^nc with M x = 0 and x[c] = V[c] for every column c not in E.  All mc check
+        nodes count, those without an erased column included.
+     3. status[f] = LDPC_HIP_ERASURE_TOO_LARGE if |E| > max_unknowns; otherwise LDPC_HIP_ERASURE_INCONSISTENT if S is empty;
+        otherwise LDPC_HIP_ERASURE_SOLVED if every column of E has the same value in all of S; otherwise
+        LDPC_HIP_ERASURE_PARTIAL.
+     4. SOLVED and PARTIAL: a column of E on which all of S agrees leaves E and takes that value; the others stay erased.
+        INCONSISTENT and TOO_LARGE: the frame is returned as it came, word_out = V, erased_out = E.
+     5. rank[f] = the rank over GF(2) of the columns E of M for SOLVED, PARTIAL and INCONSISTENT, 0 for TOO_LARGE.  For
+        SOLVED and PARTIAL |S| = 2^(|E| - rank).
+     6. unresolved[f] = |E| at the end.  The bits of a row's last word from nc on are 0 in both packed outputs.
+     7. A frame without erasures is SOLVED iff its syndrome is zero (rank 0), else INCONSISTENT.
+   None of this depends on the order of the pivots: a column of E is determined iff its unit vector lies in the row space of
+   M restricted to E, which is a property of that row space alone — the reason why the kernel and the numpy mirror of the
+   tests, which choose their pivots differently, agree bit for bit.
+   Consequence: a bit that peeling recovers is a determined bit.  Solving what the channel delivered and solving what
+   ldpc_hip_erasure_decode_batch left of it give the same word_out, erased_out, unresolved and status wherever both stay
+   within max_unknowns; rank differs (fewer columns are left).  The advised use is ldpc_hip_erasure_decode_batch with
+   LDPC_HIP_ERASURE_EARLY_TERM | LDPC_HIP_ERASURE_STOP_STALLED first and this call on what is left.
+   How it runs: byte input is packed by one small launch per operand in front; one workgroup of up to 1024 threads solves
+   one frame, its whole system in LDS, by Gauss-Jordan elimination with one barrier per unknown; a frame without erasures or
+   over the cap leaves before the matrix is built; one launch per 2^20 frames at most.  ldpcsim, simulate() and the stream's
+   BEC decoder are not touched: they stay peeling decoders, as the reference's is. */
+enum
+{
+    LDPC_HIP_ERASURE_SOLVED = 0,
+    LDPC_HIP_ERASURE_PARTIAL = 1,
+    LDPC_HIP_ERASURE_INCONSISTENT = 2,
+    LDPC_HIP_ERASURE_TOO_LARGE = 3
+};
+int ldpc_hip_erasure_solve_batch(ldpc_hip_ctx *ctx, uint32_t max_unknowns, uint64_t n, const void *word, const void *erased,
+                                 int format, uint32_t *word_out, uint32_t *erased_out, uint32_t *unresolved, uint32_t *rank,
+                                 uint32_t *status, void *hip_stream);
+/* LDS bytes one frame of ldpc_hip_erasure_solve_batch takes at that cap on this context's code (host only), -1 for
+   max_unknowns == 0 and for a frame beyond 160 KB.  With U = min(max_unknowns, nc), W = ceil(nc / 32), d the largest number
+   of entries H lists for one column:
+     R = min(mc, U d)          the rows: the check nodes that list an erased column — each of at most U erased columns is
+                               listed by at most d of them, so a sparse code of many check nodes stays in range at a small cap;
+     S = ceil((U + 1) / 64) | 1   64-bit words of a row: a bit per unknown and the right-hand side, made odd so that the rows
+                               of adjacent threads start on different banks;
+     bytes = 8 R S + 12 ceil(mc / 64) + 4 (3 W + 1) + 4 U + 64, rounded up to 16
+   — the matrix; per 64 check nodes the mask of those with a row and the rows in front of them; E, V and the unknowns in
+   front of each word of E; the column of every unknown; 64 bytes of votes and counts.  Monotone in max_unknowns.
+   tests/golden/h.txt (mc = 1024, d = 15) at max_unknowns = 1024: R = 1024, S = 17, 144 064 bytes: one frame per CU. */
+int64_t ldpc_hip_erasure_solve_lds_bytes(const ldpc_hip_ctx *ctx, uint32_t max_unknowns);
+
 /* channel point x of stream mt19937_64(seed): set_channel_param semantics, frame position := 0 */
 int ldpc_hip_stream_begin(ldpc_hip_ctx *ctx, int channel, uint64_t seed, double x);
 /* advance the stream by n frames without decoding them */

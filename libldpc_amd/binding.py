@@ -112,6 +112,10 @@ def load_library(path=LIB_PATH):
     L.ldpc_hip_erasure_decode_batch.argtypes = [vp, ct.c_uint32, i32, u64, vp, vp, i32, vp, vp, vp, vp, vp]
     L.ldpc_hip_erasure_lds_bytes.restype = ct.c_int64
     L.ldpc_hip_erasure_lds_bytes.argtypes = [vp]
+    L.ldpc_hip_erasure_solve_batch.restype = i32
+    L.ldpc_hip_erasure_solve_batch.argtypes = [vp, ct.c_uint32, u64, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.ldpc_hip_erasure_solve_lds_bytes.restype = ct.c_int64
+    L.ldpc_hip_erasure_solve_lds_bytes.argtypes = [vp, ct.c_uint32]
     L.ldpc_hip_stream_begin.restype = i32
     L.ldpc_hip_stream_begin.argtypes = [vp, i32, u64, ct.c_double]
     L.ldpc_hip_stream_skip.restype = i32
@@ -621,6 +625,47 @@ class HipDecoder:
     def erasure_lds_bytes(self):
         """LDS bytes one 32-frame group of erasure_decode_batch takes (-1: the decoder does not take the code)."""
         return int(self.lib.ldpc_hip_erasure_lds_bytes(self.ctx))
+
+    ERASURE_SOLVED, ERASURE_PARTIAL, ERASURE_INCONSISTENT, ERASURE_TOO_LARGE = 0, 1, 2, 3
+
+    def erasure_solve_batch(self, word, erased, max_unknowns=None, want=("word", "erased", "unresolved", "rank", "status"), out=None,
+                            stream=None):
+        """word[n][nc] and erased[n][nc] (both uint8 or both packed uint32) -> every erased bit that the parity checks determine,
+        by elimination over GF(2): "word" and "erased" (packed uint32 [n][ceil(nc / 32)]: the values and the holes that are left),
+        "unresolved", "rank" and "status" (uint32 [n]: holes left, rank of the erased columns, ERASURE_SOLVED / _PARTIAL /
+        _INCONSISTENT / _TOO_LARGE); include/ldpc_amd.h, ldpc_hip_erasure_solve_batch.  A frame with more than max_unknowns holes
+        comes back as it is; None = the largest cap that fits the LDS of a CU.  Advised: erasure_decode_batch(stop_stalled=True)
+        first, this call on what it leaves.  Inputs and the buffers in `out` are numpy arrays or torch tensors, host or device; a
+        wrong dtype raises TypeError, a wrong shape ValueError."""
+        n, fmt = self._bits(word, self.nc, "erasure_solve_batch")
+        ne, fe = self._bits(erased, self.nc, "erasure_solve_batch")
+        if (n, fmt) != (ne, fe):
+            raise ValueError(f"erasure_solve_batch: word is {tuple(word.shape)} {word.dtype}, erased is {tuple(erased.shape)} {erased.dtype}")
+        packed = ((n, (self.nc + 31) // 32), np.uint32)
+        spec = {"word": packed, "erased": packed, "unresolved": ((n,), np.uint32), "rank": ((n,), np.uint32), "status": ((n,), np.uint32)}
+        bufs = self._wanted(want, out, spec)
+        self._check_bufs("erasure_solve_batch", bufs, spec)
+        cap = (self.erasure_solve_max_unknowns() or 1) if max_unknowns is None else int(max_unknowns)  # (1: refused for its LDS)
+        if not 0 <= cap < 2**32:
+            raise ValueError(f"erasure_solve_batch: max_unknowns={max_unknowns}")
+        self._check(self.lib.ldpc_hip_erasure_solve_batch(self.ctx, cap, n, _ptr(word), _ptr(erased), fmt, _ptr(bufs.get("word")),
+                                                          _ptr(bufs.get("erased")), _ptr(bufs.get("unresolved")), _ptr(bufs.get("rank")),
+                                                          _ptr(bufs.get("status")), stream), "ldpc_hip_erasure_solve_batch")
+        return bufs
+
+    def erasure_solve_lds_bytes(self, max_unknowns):
+        """LDS bytes one frame of erasure_solve_batch takes at that cap (-1: it does not fit a CU, or the cap is 0)."""
+        return int(self.lib.ldpc_hip_erasure_solve_lds_bytes(self.ctx, int(max_unknowns)))
+
+    def erasure_solve_max_unknowns(self):
+        """The largest max_unknowns erasure_solve_batch takes on this code (the LDS is monotone in it); 0 if none fits."""
+        if self.erasure_solve_lds_bytes(self.nc) >= 0:
+            return self.nc
+        lo, hi = 0, self.nc  # lo fits (or is 0), hi does not
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            lo, hi = (mid, hi) if self.erasure_solve_lds_bytes(mid) >= 0 else (lo, mid)
+        return lo
 
     def stream_begin(self, channel, seed, x):
         """Channel point x of mt19937_64(seed); also resets the encoder (a fresh channel object)."""

@@ -485,6 +485,22 @@ int64_t ldpc_hip_erasure_lds_bytes(const ldpc_hip_ctx *ctx)
     return bytes;
 }
 
+int ldpc_hip_erasure_solve_batch(ldpc_hip_ctx *ctx, uint32_t max_unknowns, uint64_t n, const void *word, const void *erased, int format,
+                                 uint32_t *word_out, uint32_t *erased_out, uint32_t *unresolved, uint32_t *rank, uint32_t *status,
+                                 void *hip_stream)
+{
+    return guarded([&] {
+        ctx->eng->erasure_solve_batch(max_unknowns, n, word, erased, format, word_out, erased_out, unresolved, rank, status, hip_stream);
+    });
+}
+
+int64_t ldpc_hip_erasure_solve_lds_bytes(const ldpc_hip_ctx *ctx, uint32_t max_unknowns)
+{
+    int64_t bytes = -1;
+    guarded([&] { bytes = ctx->eng->erasure_solve_lds_bytes(max_unknowns); });
+    return bytes;
+}
+
 int64_t ldpc_hip_layered_fixed_direct_lds_bytes(const ldpc_hip_ctx *ctx)
 {
     int64_t bytes = -1; // (the plan builder allocates; -1 for every code the layered plan refuses)

@@ -1581,6 +1581,16 @@ void Engine::encode_batch(uint64_t n, const void *info, int info_format, uint8_t
     }
 }
 
+void Engine::upload_rows_of_h()
+{
+    if (gf2_row_ptr_)
+        return;
+    const SparseGF2 &H = code_->H;
+    std::vector<uint32_t> rp(H.rptr.begin(), H.rptr.end()), rc(H.rcol.begin(), H.rcol.end());
+    gf2_row_col_ = static_cast<const uint32_t *>(upload_table(rc.data(), rc.size() * 4, "rows of H"));
+    gf2_row_ptr_ = static_cast<const uint32_t *>(upload_table(rp.data(), rp.size() * 4, "rows of H")); // last: the mark
+}
+
 void Engine::syndrome_batch(uint64_t n, const void *word, int word_format, uint8_t *syndrome, uint32_t *syndrome_bits, uint32_t *weight,
                             void *stream)
 {
@@ -1594,13 +1604,7 @@ void Engine::syndrome_batch(uint64_t n, const void *word, int word_format, uint8
     bind_device();
     hipStream_t s = static_cast<hipStream_t>(stream);
     const uint64_t nc = static_cast<uint64_t>(plan_.nc), mc = static_cast<uint64_t>(plan_.mc), out_words = (mc + 31) / 32;
-    if (!gf2_row_ptr_)
-    {
-        const SparseGF2 &H = code_->H;
-        std::vector<uint32_t> rp(H.rptr.begin(), H.rptr.end()), rc(H.rcol.begin(), H.rcol.end());
-        gf2_row_col_ = static_cast<const uint32_t *>(upload_table(rc.data(), rc.size() * 4, "rows of H"));
-        gf2_row_ptr_ = static_cast<const uint32_t *>(upload_table(rp.data(), rp.size() * 4, "rows of H")); // last: the mark
-    }
+    upload_rows_of_h();
     const uint64_t sub = gf2_sub_batch();
     const size_t in_row = bits_row_bytes(word_format, nc);
     for (uint64_t done = 0; done < n; done += sub)
@@ -1964,6 +1968,77 @@ void Engine::erasure_decode_batch(uint32_t iterations, int flags, uint64_t n, co
         a.unresolved = st.route(unresolved ? unresolved + done : nullptr, stage_era_[3], 4 * m);
         a.n = m;
         check(launch_erasure_decode(a, s), "erasure_decode_batch");
+        st.flush(s, &pin_out_);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Maximum-likelihood erasure decoding (kernels_erasure_solve.hip)
+int64_t Engine::erasure_solve_lds_bytes(uint32_t max_unknowns) const
+{
+    if (max_unknowns == 0)
+        return -1;
+    const size_t nc = static_cast<size_t>(plan_.nc), mc = static_cast<size_t>(plan_.mc), cap = std::min<size_t>(max_unknowns, nc);
+    const size_t bytes = ldpc_amd::erasure_solve_lds_bytes(nc, mc, cap, erasure_solve_rows(mc, cap, static_cast<size_t>(plan_.max_vn_degree)));
+    return bytes <= kCuLdsBytes ? static_cast<int64_t>(bytes) : -1;
+}
+
+std::string Engine::erasure_solve_refusal(uint32_t max_unknowns, int format) const
+{
+    const std::string who = "ldpc_hip_erasure_solve_batch: ";
+    if (std::string why = bits_format_refusal("ldpc_hip_erasure_solve_batch", "word and erased", format); !why.empty())
+        return why;
+    if (max_unknowns == 0)
+        return who + "max_unknowns is 0";
+    if (erasure_solve_lds_bytes(max_unknowns) < 0)
+        return who + "a frame of " + std::to_string(std::min<uint64_t>(max_unknowns, static_cast<uint64_t>(plan_.nc))) +
+               " unknowns does not fit the 160 KB of LDS of a CU (ldpc_hip_erasure_solve_lds_bytes; there is no other kernel)";
+    return "";
+}
+
+void Engine::erasure_solve_batch(uint32_t max_unknowns, uint64_t n, const void *word, const void *erased, int format, uint32_t *word_out,
+                                 uint32_t *erased_out, uint32_t *unresolved, uint32_t *rank, uint32_t *status, void *stream)
+{
+    if (const std::string why = erasure_solve_refusal(max_unknowns, format); !why.empty())
+        throw std::runtime_error(why);
+    if (n && (!word || !erased))
+        throw std::runtime_error("ldpc_hip_erasure_solve_batch: null word or erased");
+    if (n == 0 || (!word_out && !erased_out && !unresolved && !rank && !status))
+        return;
+    bind_device();
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    upload_rows_of_h();
+    const uint64_t nc = static_cast<uint64_t>(plan_.nc), mc = static_cast<uint64_t>(plan_.mc), words = (nc + 31) / 32;
+    ErasureSolveArgs a{};
+    a.nc = static_cast<uint32_t>(nc), a.mc = static_cast<uint32_t>(mc), a.words = static_cast<uint32_t>(words);
+    a.cap = static_cast<uint32_t>(std::min<uint64_t>(max_unknowns, nc));
+    a.rows = static_cast<uint32_t>(erasure_solve_rows(mc, a.cap, static_cast<size_t>(plan_.max_vn_degree)));
+    a.threads = std::clamp<uint32_t>((a.rows + 63u) / 64u * 64u, 64u, kErasureSolveMaxThreads); // a thread per row where they reach
+    a.lds_bytes = static_cast<uint32_t>(erasure_solve_lds_bytes(max_unknowns));
+    a.row_ptr = gf2_row_ptr_, a.row_col = gf2_row_col_;
+    const uint64_t sub = gf2_sub_batch();
+    const size_t in_row = bits_row_bytes(format, nc);
+    for (uint64_t done = 0; done < n; done += sub)
+    {
+        const uint64_t m = std::min(sub, n - done);
+        const void *src[2] = {stage_input(static_cast<const char *>(word) + in_row * done, in_row * m, stage_in_, stream),
+                              stage_input(static_cast<const char *>(erased) + in_row * done, in_row * m, stage_in_b_, stream)};
+        if (format == kBitsU8) // bytes: packed by one small launch each in front
+            for (int i = 0; i < 2; ++i)
+            {
+                uint32_t *packed = static_cast<uint32_t *>(era_packed_[i].reserve(4 * m * words));
+                check(launch_pack_hard(static_cast<const uint8_t *>(src[i]), m, static_cast<int>(nc), packed, s), "erasure_solve_batch (pack)");
+                src[i] = packed;
+            }
+        OutStage st;
+        a.word = static_cast<const uint32_t *>(src[0]), a.erased = static_cast<const uint32_t *>(src[1]);
+        a.word_out = st.route(word_out ? word_out + done * words : nullptr, stage_era_[0], 4 * m * words);
+        a.erased_out = st.route(erased_out ? erased_out + done * words : nullptr, stage_era_[1], 4 * m * words);
+        a.unresolved = st.route(unresolved ? unresolved + done : nullptr, stage_era_[2], 4 * m);
+        a.rank = st.route(rank ? rank + done : nullptr, stage_era_[3], 4 * m);
+        a.status = st.route(status ? status + done : nullptr, stage_era_[4], 4 * m);
+        a.n = m;
+        check(launch_erasure_solve(a, s), "erasure_solve_batch");
         st.flush(s, &pin_out_);
     }
 }

@@ -379,6 +379,13 @@ class Engine
     int64_t erasure_lds_bytes();
     void erasure_decode_batch(uint32_t iterations, int flags, uint64_t n, const void *word, const void *erased, int format,
                               uint32_t *word_out, uint32_t *erased_out, uint32_t *iters, uint32_t *unresolved, void *stream);
+    // maximum-likelihood erasure decoding: what elimination over GF(2) determines (include/ldpc_amd.h,
+    // ldpc_hip_erasure_solve_batch; kernels_erasure_solve.hip).  Host only: the refusal, and the LDS of one frame at a cap,
+    // -1 for a cap of 0 or a frame beyond a CU
+    std::string erasure_solve_refusal(uint32_t max_unknowns, int format) const;
+    int64_t erasure_solve_lds_bytes(uint32_t max_unknowns) const;
+    void erasure_solve_batch(uint32_t max_unknowns, uint64_t n, const void *word, const void *erased, int format, uint32_t *word_out,
+                             uint32_t *erased_out, uint32_t *unresolved, uint32_t *rank, uint32_t *status, void *stream);
 
     // ---- fused channel + decode on the reference's noise stream ----
     // set_channel_param semantics (channel.cpp:37-42): the stream restarts at frame 0.
@@ -563,6 +570,7 @@ class Engine
     const uint32_t *gf2_mask_ = nullptr;    // [ceil(kc / 32)][gf2_mask_cols_]: the columns of G as masks, word-major (Gf2EncodeArgs)
     uint64_t gf2_mask_cols_ = 0;
     const uint32_t *gf2_row_ptr_ = nullptr, *gf2_row_col_ = nullptr; // row CSR of H
+    void upload_rows_of_h();                                         // (the first call that reads them)
     const uint64_t *gf2_tx_mask_ = nullptr; // the transmitted positions (bit_pos) as a mask over the columns
     DeviceBuffer gf2_info_, stage_in_b_, stage_gf2_[3];
     // the channel call: the columns the channel does not write (column | kChannelShortened) and the ASK constellations of
@@ -585,7 +593,7 @@ class Engine
     const ErasureTables &erasure_tables();
     const uint32_t *era_col_tx_ = nullptr, *era_desc_ = nullptr;
     const uint16_t *era_cn_entries_ = nullptr, *era_vn_entries_ = nullptr, *era_vn_col_ = nullptr;
-    DeviceBuffer era_packed_[2], stage_era_[4];
+    DeviceBuffer era_packed_[2], stage_era_[5]; // (five outputs: the solver's)
     uint64_t gf2_sub_batch() const; // frames per launch: staging buffers stay modest, no grid dimension overflows
     // a host input of a batch call on the device (small ones through page-locked memory); a device pointer comes back as it is
     const void *stage_input(const void *src, size_t bytes, DeviceBuffer &stage, void *stream);

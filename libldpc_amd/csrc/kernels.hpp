@@ -475,6 +475,43 @@ struct ErasureDecodeArgs
 };
 int launch_erasure_decode(const ErasureDecodeArgs &a, void *stream);
 
+// ---- maximum-likelihood erasure decoding of frames of bits (kernels_erasure_solve.hip; include/ldpc_amd.h,
+// ldpc_hip_erasure_solve_batch): one workgroup eliminates one frame's system over GF(2), all of it in LDS ----
+// A row of the augmented matrix is `stride` 64-bit words: bit j < |E| = unknown j (the erased columns in column order), bit
+// |E| = the right-hand side.  stride = ceil((cap + 1) / 64) made odd: a thread walks one row, and the rows of 32 adjacent
+// threads then start on 32 different pairs of banks for the 8-byte reads and on 16 for each 16-lane group of the 8-byte
+// writes.  A frame uses the stride of its own |E|, never more.  `rows` bounds the check nodes that list an erased column.
+constexpr uint32_t kErasureSolveMaxThreads = 1024, kErasureSolveScalars = 16, kErasureSolveRowsPerThread = 32;
+constexpr uint32_t kErasureSolved = 0, kErasurePartial = 1, kErasureInconsistent = 2, kErasureTooLarge = 3;
+constexpr size_t erasure_solve_stride(size_t cap) { return ((cap + 1 + 63) / 64) | 1; }
+constexpr size_t erasure_solve_rows(size_t mc, size_t cap, size_t max_column_degree) { return mc < cap * max_column_degree ? mc : cap * max_column_degree; }
+// LDS of one frame (include/ldpc_amd.h, ldpc_hip_erasure_solve_lds_bytes): the matrix; per 64 check nodes the mask of those
+// with an erased column and their count so far; E, V and the unknowns in front of each word of E; the column of every
+// unknown; the votes
+constexpr size_t erasure_solve_lds_bytes(size_t nc, size_t mc, size_t cap, size_t rows)
+{
+    return (8 * rows * erasure_solve_stride(cap) + 12 * ((mc + 63) / 64) + 4 * (3 * ((nc + 31) / 32) + 1) + 4 * cap + 4 * kErasureSolveScalars + 15) / 16 * 16;
+}
+struct ErasureSolveArgs
+{
+    uint32_t nc, mc, words;   // words = ceil(nc / 32)
+    uint32_t cap;             // 1 <= cap <= nc: a frame with more erased columns is returned as it came
+    uint32_t rows;            // erasure_solve_rows(mc, cap, largest column degree)
+    uint32_t threads;         // a multiple of 64, <= kErasureSolveMaxThreads, rows <= kErasureSolveRowsPerThread * threads
+    uint32_t lds_bytes;       // erasure_solve_lds_bytes(nc, mc, cap, rows)
+    const uint32_t *row_ptr;  // [mc + 1]: the rows of H as the library loaded it, repeated entries included
+    const uint32_t *row_col;  // columns, < nc
+    const uint32_t *word;     // [n][words]
+    const uint32_t *erased;   // [n][words]
+    uint32_t *word_out;       // [n][words] or nullptr
+    uint32_t *erased_out;     // [n][words] or nullptr
+    uint32_t *unresolved;     // [n] or nullptr
+    uint32_t *rank;           // [n] or nullptr
+    uint32_t *status;         // [n] or nullptr
+    uint64_t n;               // < 2^31
+};
+int launch_erasure_solve(const ErasureSolveArgs &a, void *stream);
+
 // opt-in non-parity ternary min-sum, bit-sliced over 32 frames per workgroup (kernels_ternary.hip; include/ldpc_amd.h,
 // ldpc_hip_set_min_sum_ternary) on the general plan.  a.ms_* are not read.  With a.llr_out null the planes of A are left out
 // of the group's LDS (plan.hpp, ternary_lds_bytes)
