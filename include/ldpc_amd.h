@@ -635,6 +635,68 @@ int ldpc_hip_erasure_solve_batch(ldpc_hip_ctx *ctx, uint32_t max_unknowns, uint6
    tests/golden/h.txt (mc = 1024, d = 15) at max_unknowns = 1024: R = 1024, S = 17, 144 064 bytes: one frame per CU. */
 int64_t ldpc_hip_erasure_solve_lds_bytes(const ldpc_hip_ctx *ctx, uint32_t max_unknowns);
 
+/* Ordered-statistics decoding (OSD) of frames of LLRs, order 0 and order-1 reprocessing
+   (libldpc_amd/csrc/kernels_osd.hip): the codeword that agrees with the hard decisions on the most reliable independent
+   positions, and the best of the first `candidates` single flips among them.  Meant as BP + OSD behind a decoder of the
+   noisy channels: fed with the llr_out of a frame that message passing left with a non-zero syndrome, it returns a codeword,
+   often the transmitted one on short codes; fed with a codeword's LLRs it returns that codeword.  The common rules of this
+   block hold: device or host buffers, checks before the GPU naming the entry in ldpc_hip_last_error, n == 0 returns 0 after
+   them, every output may be NULL, ordered on hip_stream, no setting and no state of the stream interface read or changed, a
+   frame's results do not depend on which frames share its call, every output bit is determined.
+   llr[n][nc] in, column order, elements of llr_type (LDPC_HIP_LLR_F64 / F32 / F16 / I8); word_out[n][W] (packed as
+   hard_bits is, W = ceil(nc / 32), the bits of a row's last word from nc on 0), flips[n], metric[n], flipped_column[n] and
+   status[n] out.  Refused (host only, -1): an unknown llr_type, a NULL llr with n > 0, and a code whose frame does not fit
+   (ldpc_hip_osd_lds_bytes returns -1; there is no other kernel).
+   Per frame — everything after step 1 is integer or GF(2) arithmetic, nothing depends on a summation order:
+     1. The widened value.  W[c] = the element widened exactly to binary64, as in ldpc_hip_decode_batch_typed; for
+        LDPC_HIP_LLR_I8 the integer k itself (no step is read: a positive scale changes nothing that matters).
+        The decision z[c] = (W[c] <= 0), the decoders' rule; a NaN gives 0.  The reliability
+        q[c] = min(floor(|W[c]| * 4096), 2^31 - 1) as uint32; a NaN gives 0, an infinity 2^31 - 1; for I8 it is |k| * 4096.
+     2. The matrix.  M[r][c] = (the number of times (r, c) is listed in H as the library loaded it) mod 2, the rule of
+        ldpc_hip_erasure_solve_batch.
+     3. The order pi lists the columns by (q ascending, column index ascending): the least reliable first.
+     4. The solved set.  Scan pi; a column joins the solved set P iff its column of M is linearly independent of the columns
+        already in P.  P does not depend on which row is taken as a pivot; |P| = rank(M).  K = every other column, kept in
+        the order of pi: the n - rank(M) columns that are trusted, the most reliable ones among them last.
+     5. Order 0.  x0 = the unique x with M x = 0 and x[c] = z[c] on K (it exists: the columns of P span the column space of
+        M; it is unique: they are independent).
+     6. The metric of a word x = the sum of q[c] over the columns where x[c] != z[c], as uint64.
+     7. Order-1 reprocessing.  T = min(candidates, |K|).  For the t-th column j of K in the order of pi, t < T, x_j = the
+        unique solution that agrees with z on K except at j.  The winner is x0 unless some x_j has a strictly smaller metric;
+        among those the smallest metric wins, among equal metrics the smallest t.
+     8. word_out = the winner; flips = the number of columns where it differs from z; metric = its metric;
+        flipped_column = j if an x_j won, 0xFFFFFFFF otherwise; status = LDPC_HIP_OSD_CODEWORD if M z = 0 (then the winner
+        is z itself with metric 0 and 0 flips: the label is the only thing this case changes), otherwise
+        LDPC_HIP_OSD_REPROCESSED if an x_j won, otherwise LDPC_HIP_OSD_ORDER0.
+   Identities: M word_out = 0 always, so ldpc_hip_syndrome_batch of word_out has weight 0 on every frame; the metric is
+   non-increasing in `candidates` (a larger T only adds words to choose from, and the first T stay the first T).
+   None of this depends on the order of the pivots — the reason why the kernel and the numpy mirror of the tests, which
+   choose their pivots differently, agree bit for bit.
+   How it runs: the elements are read in place in their own type (no widening launch in front); one workgroup of up to 1024
+   threads takes one frame, its whole check matrix as mc rows of bits in LDS; the order by counting ranks over the nc keys;
+   Gauss-Jordan elimination over the columns in that order with one barrier per column (a dependent column costs a vote
+   only); x0 from the reduced rows; the candidates scored a wave each from the reduced rows; a frame whose z is a codeword
+   leaves before the matrix is built; one launch per 2^20 frames at most.  ldpcsim, simulate() and the stream interface are
+   not touched. */
+enum
+{
+    LDPC_HIP_OSD_CODEWORD = 0,
+    LDPC_HIP_OSD_ORDER0 = 1,
+    LDPC_HIP_OSD_REPROCESSED = 2
+};
+int ldpc_hip_osd_batch(ldpc_hip_ctx *ctx, uint32_t candidates, uint64_t n, const void *llr, int llr_type, uint32_t *word_out,
+                       uint32_t *flips, uint64_t *metric, uint32_t *flipped_column, uint32_t *status, void *hip_stream);
+/* LDS bytes one frame of ldpc_hip_osd_batch takes on this context's code (host only), -1 for a code with 65 536 columns or
+   more, with more than 32 768 check nodes, or with a frame beyond 160 KB.  With V = ceil(nc / 64):
+     S = (V + 1) | 1           64-bit words of a row: a bit per column and at least one word beside them (what the candidate
+                               search reads of the row's pivot column), made odd so that the rows of adjacent threads
+                               start on different banks;
+     bytes = max(8 mc S, 4 nc rounded up to 8) + 24 V + (2 nc rounded up to 8) + 384, rounded up to 16
+   — the matrix, whose region holds the nc sort keys before it is built; z, P and the word as masks; the order, 16 bits a
+   column; 384 bytes of votes, sums and one best candidate per wave.
+   tests/golden/h.txt (mc = 1024, nc = 1152): V = 18, S = 19, 155 648 + 432 + 2 304 + 384 = 158 768 bytes: one frame per CU. */
+int64_t ldpc_hip_osd_lds_bytes(const ldpc_hip_ctx *ctx);
+
 /* channel point x of stream mt19937_64(seed): set_channel_param semantics, frame position := 0 */
 int ldpc_hip_stream_begin(ldpc_hip_ctx *ctx, int channel, uint64_t seed, double x);
 /* advance the stream by n frames without decoding them */

@@ -116,6 +116,10 @@ def load_library(path=LIB_PATH):
     L.ldpc_hip_erasure_solve_batch.argtypes = [vp, ct.c_uint32, u64, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     L.ldpc_hip_erasure_solve_lds_bytes.restype = ct.c_int64
     L.ldpc_hip_erasure_solve_lds_bytes.argtypes = [vp, ct.c_uint32]
+    L.ldpc_hip_osd_batch.restype = i32
+    L.ldpc_hip_osd_batch.argtypes = [vp, ct.c_uint32, u64, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.ldpc_hip_osd_lds_bytes.restype = ct.c_int64
+    L.ldpc_hip_osd_lds_bytes.argtypes = [vp]
     L.ldpc_hip_stream_begin.restype = i32
     L.ldpc_hip_stream_begin.argtypes = [vp, i32, u64, ct.c_double]
     L.ldpc_hip_stream_skip.restype = i32
@@ -666,6 +670,37 @@ class HipDecoder:
             mid = (lo + hi) // 2
             lo, hi = (mid, hi) if self.erasure_solve_lds_bytes(mid) >= 0 else (lo, mid)
         return lo
+
+    OSD_CODEWORD, OSD_ORDER0, OSD_REPROCESSED, OSD_NO_COLUMN = 0, 1, 2, 0xFFFFFFFF
+
+    def osd_batch(self, llr, candidates=0, want=("word", "flips", "metric", "flipped_column", "status"), out=None, stream=None):
+        """llr[n][nc] (float64, float32, float16 or int8, column order; a decoder's llr_out for BP + OSD) -> the codeword of
+        ordered-statistics decoding: order 0 on the most reliable independent columns, then the best of the first `candidates`
+        single flips among them.  "word" (packed uint32 [n][ceil(nc / 32)], always a codeword), "flips" (uint32 [n]: the columns
+        where it leaves the hard decisions), "metric" (uint64 [n]: their reliabilities summed), "flipped_column" (uint32 [n]:
+        the column of the winning flip, OSD_NO_COLUMN if none) and "status" (uint32 [n]: OSD_CODEWORD / _ORDER0 / _REPROCESSED);
+        include/ldpc_amd.h, ldpc_hip_osd_batch.  llr and the buffers in `out` are numpy arrays or torch tensors, host or device;
+        a wrong dtype raises TypeError, a wrong shape ValueError."""
+        name = str(llr.dtype).replace("torch.", "")
+        if name not in self.LLR_TYPES:
+            raise TypeError(f"osd_batch takes float64, float32, float16 or int8 LLRs, not {llr.dtype}")
+        if len(llr.shape) != 2 or int(llr.shape[1]) != self.nc:
+            raise ValueError(f"osd_batch: llr is [n][{self.nc}], not {tuple(llr.shape)}")
+        if not 0 <= int(candidates) < 2**32:
+            raise ValueError(f"osd_batch: candidates={candidates}")
+        n = int(llr.shape[0])
+        spec = {"word": ((n, (self.nc + 31) // 32), np.uint32), "flips": ((n,), np.uint32), "metric": ((n,), np.uint64),
+                "flipped_column": ((n,), np.uint32), "status": ((n,), np.uint32)}
+        bufs = self._wanted(want, out, spec)
+        self._check_bufs("osd_batch", bufs, spec)
+        self._check(self.lib.ldpc_hip_osd_batch(self.ctx, int(candidates), n, _ptr(llr), self.LLR_TYPES[name], _ptr(bufs.get("word")),
+                                                _ptr(bufs.get("flips")), _ptr(bufs.get("metric")), _ptr(bufs.get("flipped_column")),
+                                                _ptr(bufs.get("status")), stream), "ldpc_hip_osd_batch")
+        return bufs
+
+    def osd_lds_bytes(self):
+        """LDS bytes one frame of osd_batch takes (-1: the check matrix does not fit a CU, and osd_batch refuses the code)."""
+        return int(self.lib.ldpc_hip_osd_lds_bytes(self.ctx))
 
     def stream_begin(self, channel, seed, x):
         """Channel point x of mt19937_64(seed); also resets the encoder (a fresh channel object)."""

@@ -501,6 +501,19 @@ int64_t ldpc_hip_erasure_solve_lds_bytes(const ldpc_hip_ctx *ctx, uint32_t max_u
     return bytes;
 }
 
+int ldpc_hip_osd_batch(ldpc_hip_ctx *ctx, uint32_t candidates, uint64_t n, const void *llr, int llr_type, uint32_t *word_out, uint32_t *flips,
+                       uint64_t *metric, uint32_t *flipped_column, uint32_t *status, void *hip_stream)
+{
+    return guarded([&] { ctx->eng->osd_batch(candidates, n, llr, llr_type, word_out, flips, metric, flipped_column, status, hip_stream); });
+}
+
+int64_t ldpc_hip_osd_lds_bytes(const ldpc_hip_ctx *ctx)
+{
+    int64_t bytes = -1;
+    guarded([&] { bytes = ctx->eng->osd_lds_bytes(); });
+    return bytes;
+}
+
 int64_t ldpc_hip_layered_fixed_direct_lds_bytes(const ldpc_hip_ctx *ctx)
 {
     int64_t bytes = -1; // (the plan builder allocates; -1 for every code the layered plan refuses)

@@ -2043,6 +2043,65 @@ void Engine::erasure_solve_batch(uint32_t max_unknowns, uint64_t n, const void *
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Ordered-statistics decoding (kernels_osd.hip)
+int64_t Engine::osd_lds_bytes() const
+{
+    const size_t nc = static_cast<size_t>(plan_.nc), mc = static_cast<size_t>(plan_.mc);
+    if (nc > 0xFFFFu || mc > static_cast<size_t>(kOsdRowsPerThread) * kOsdMaxThreads) // (the order is 16 bits a column)
+        return -1;
+    const size_t bytes = ldpc_amd::osd_lds_bytes(nc, mc);
+    return bytes <= kCuLdsBytes ? static_cast<int64_t>(bytes) : -1;
+}
+
+std::string Engine::osd_refusal(int llr_type) const
+{
+    const std::string who = "ldpc_hip_osd_batch: ";
+    if (llr_type_bytes(llr_type) == 0)
+        return who + "unknown LLR type " + std::to_string(llr_type) + " (0 = binary64, 1 = binary32, 2 = binary16, 3 = int8)";
+    if (osd_lds_bytes() < 0)
+        return who + "the check matrix of " + std::to_string(plan_.mc) + " x " + std::to_string(plan_.nc) +
+               " bits does not fit the 160 KB of LDS of a CU (ldpc_hip_osd_lds_bytes; there is no other kernel)";
+    return "";
+}
+
+void Engine::osd_batch(uint32_t candidates, uint64_t n, const void *llr, int llr_type, uint32_t *word_out, uint32_t *flips, uint64_t *metric,
+                       uint32_t *flipped_column, uint32_t *status, void *stream)
+{
+    if (const std::string why = osd_refusal(llr_type); !why.empty())
+        throw std::runtime_error(why);
+    if (n && !llr)
+        throw std::runtime_error("ldpc_hip_osd_batch: null llr");
+    if (n == 0 || (!word_out && !flips && !metric && !flipped_column && !status))
+        return;
+    bind_device();
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    upload_rows_of_h();
+    const uint64_t nc = static_cast<uint64_t>(plan_.nc), mc = static_cast<uint64_t>(plan_.mc), words = (nc + 31) / 32;
+    OsdArgs a{};
+    a.nc = static_cast<uint32_t>(nc), a.mc = static_cast<uint32_t>(mc), a.words = static_cast<uint32_t>(words);
+    a.candidates = candidates, a.llr_type = llr_type;
+    a.threads = std::clamp<uint32_t>((a.mc + 63u) / 64u * 64u, 64u, kOsdMaxThreads); // a thread per row where they reach
+    a.lds_bytes = static_cast<uint32_t>(osd_lds_bytes());
+    a.row_ptr = gf2_row_ptr_, a.row_col = gf2_row_col_;
+    const uint64_t sub = std::max<uint64_t>(gf2_sub_batch() / llr_type_bytes(llr_type), 1); // (elements of up to 8 bytes, not bits)
+    const size_t in_row = llr_type_bytes(llr_type) * nc;
+    for (uint64_t done = 0; done < n; done += sub)
+    {
+        const uint64_t m = std::min(sub, n - done);
+        a.llr = stage_input(static_cast<const char *>(llr) + in_row * done, in_row * m, llr_type == kLlrF64 ? stage_in_ : stage_typed_, stream);
+        OutStage st;
+        a.word_out = st.route(word_out ? word_out + done * words : nullptr, stage_osd_[0], 4 * m * words);
+        a.flips = st.route(flips ? flips + done : nullptr, stage_osd_[1], 4 * m);
+        a.metric = st.route(metric ? metric + done : nullptr, stage_osd_[2], 8 * m);
+        a.flipped_column = st.route(flipped_column ? flipped_column + done : nullptr, stage_osd_[3], 4 * m);
+        a.status = st.route(status ? status + done : nullptr, stage_osd_[4], 4 * m);
+        a.n = m;
+        check(launch_osd(a, s), "osd_batch");
+        st.flush(s, &pin_out_);
+    }
+}
+
 void Engine::stream_rewind_encoder(uint64_t frames_back, void *stream)
 {
     if (!code_->has_G() || frames_back == 0 || counter_) // (counter-based noise: a codeword depends on its frame index alone)

@@ -386,6 +386,12 @@ class Engine
     int64_t erasure_solve_lds_bytes(uint32_t max_unknowns) const;
     void erasure_solve_batch(uint32_t max_unknowns, uint64_t n, const void *word, const void *erased, int format, uint32_t *word_out,
                              uint32_t *erased_out, uint32_t *unresolved, uint32_t *rank, uint32_t *status, void *stream);
+    // ordered-statistics decoding of LLR frames: order 0 and the first `candidates` single flips (include/ldpc_amd.h,
+    // ldpc_hip_osd_batch; kernels_osd.hip).  Host only: the refusal, and the LDS of one frame, -1 for a code beyond a CU
+    std::string osd_refusal(int llr_type) const;
+    int64_t osd_lds_bytes() const;
+    void osd_batch(uint32_t candidates, uint64_t n, const void *llr, int llr_type, uint32_t *word_out, uint32_t *flips, uint64_t *metric,
+                   uint32_t *flipped_column, uint32_t *status, void *stream);
 
     // ---- fused channel + decode on the reference's noise stream ----
     // set_channel_param semantics (channel.cpp:37-42): the stream restarts at frame 0.
@@ -594,6 +600,7 @@ class Engine
     const uint32_t *era_col_tx_ = nullptr, *era_desc_ = nullptr;
     const uint16_t *era_cn_entries_ = nullptr, *era_vn_entries_ = nullptr, *era_vn_col_ = nullptr;
     DeviceBuffer era_packed_[2], stage_era_[5]; // (five outputs: the solver's)
+    DeviceBuffer stage_osd_[5];                 // the outputs of osd_batch for host buffers
     uint64_t gf2_sub_batch() const; // frames per launch: staging buffers stay modest, no grid dimension overflows
     // a host input of a batch call on the device (small ones through page-locked memory); a device pointer comes back as it is
     const void *stage_input(const void *src, size_t bytes, DeviceBuffer &stage, void *stream);

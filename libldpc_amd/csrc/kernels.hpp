@@ -512,6 +512,45 @@ struct ErasureSolveArgs
 };
 int launch_erasure_solve(const ErasureSolveArgs &a, void *stream);
 
+// ---- ordered-statistics decoding of frames of LLRs (kernels_osd.hip; include/ldpc_amd.h, ldpc_hip_osd_batch): one
+// workgroup reduces one frame's whole check matrix over GF(2) in LDS, in the order of the frame's reliabilities ----
+// A row is `stride` 64-bit words: bit c of the first ceil(nc / 64) = the entry of column c, then at least one word beside
+// them, which after the elimination holds what the candidate search reads of the row's pivot column (its reliability, its
+// index, whether order 0 flips it).  stride = (ceil(nc / 64) + 1) made odd, for the banks (erasure_solve_stride).
+constexpr uint32_t kOsdMaxThreads = 1024, kOsdRowsPerThread = 32, kOsdSideBytes = 384;
+constexpr uint32_t kOsdCodeword = 0, kOsdOrder0 = 1, kOsdReprocessed = 2, kOsdNoColumn = 0xFFFFFFFFu, kOsdQMax = 0x7FFFFFFFu;
+constexpr size_t osd_row_words(size_t nc) { return (nc + 63) / 64; }
+constexpr size_t osd_stride(size_t nc) { return (osd_row_words(nc) + 1) | 1; }
+// the region the matrix shares with the sort keys (4 bytes a column, gone before the matrix is built)
+constexpr size_t osd_matrix_bytes(size_t nc, size_t mc)
+{
+    return 8 * mc * osd_stride(nc) > (4 * nc + 7) / 8 * 8 ? 8 * mc * osd_stride(nc) : (4 * nc + 7) / 8 * 8;
+}
+// LDS of one frame (include/ldpc_amd.h, ldpc_hip_osd_lds_bytes): the matrix; the decisions z, the solved set P and the word
+// being built as masks over the columns; the order (16 bits a column); votes, sums and one best candidate per wave
+constexpr size_t osd_lds_bytes(size_t nc, size_t mc)
+{
+    return (osd_matrix_bytes(nc, mc) + 24 * osd_row_words(nc) + (2 * nc + 7) / 8 * 8 + kOsdSideBytes + 15) / 16 * 16;
+}
+struct OsdArgs
+{
+    uint32_t nc, mc, words;  // words = ceil(nc / 32); nc < 65536
+    uint32_t candidates;     // order-1 candidates tried (the first of K in the order; more than |K| counts as |K|)
+    uint32_t threads;        // a multiple of 64, <= kOsdMaxThreads, mc <= kOsdRowsPerThread * threads
+    uint32_t lds_bytes;      // osd_lds_bytes(nc, mc)
+    int32_t llr_type;        // LlrType: the kernel reads the elements in place
+    const uint32_t *row_ptr; // [mc + 1]: the rows of H as the library loaded it, repeated entries included
+    const uint32_t *row_col; // columns, < nc
+    const void *llr;         // [n][nc] elements of llr_type
+    uint32_t *word_out;      // [n][words] or nullptr
+    uint32_t *flips;         // [n] or nullptr
+    uint64_t *metric;        // [n] or nullptr
+    uint32_t *flipped_column; // [n] or nullptr
+    uint32_t *status;        // [n] or nullptr
+    uint64_t n;              // <= 2^20
+};
+int launch_osd(const OsdArgs &a, void *stream);
+
 // opt-in non-parity ternary min-sum, bit-sliced over 32 frames per workgroup (kernels_ternary.hip; include/ldpc_amd.h,
 // ldpc_hip_set_min_sum_ternary) on the general plan.  a.ms_* are not read.  With a.llr_out null the planes of A are left out
 // of the group's LDS (plan.hpp, ternary_lds_bytes)
