@@ -789,6 +789,9 @@ int ldpc_hip_comm_allgather(ldpc_hip_comm *comm, const void *send, void *recv, u
    take it): info = {the code qualifies, message slots, variable-node blocks per wave, leaf calls per wave, the small
    instantiation applies, check-node calls per wave + 1, the code has shortened bits, entries of the slot table} */
 void ldpc_hip_fused_plan_info(const ldpc_hip_ctx *ctx, int64_t info[8]);
+/* index of the compile-time wave program whose shape that plan has (libldpc_amd/csrc/fused_program.hpp): the first ratio
+   launch then runs the program's kernel instead of interpreting the plan; -1: no program (or no fused plan).  Host only */
+int ldpc_hip_fused_program(const ldpc_hip_ctx *ctx);
 /* the launches a batch decoded with `dec` takes on this context, in order (host only; honours ldpc_hip_set_fast_mode,
    ldpc_hip_set_min_sum_schedule, ldpc_hip_set_min_sum_quantization, ldpc_hip_set_min_sum_ternary and ldpc_hip_set_min_sum_layered_fixed): stages[i] = 0 whole, 1 ratio-first, 2 ratio-separate, 3 list-chain,
    4 llr-redo, 5 handover-first, 6 handover-resume; returns their number, 1 to 3 */

@@ -154,6 +154,8 @@ def load_library(path=LIB_PATH):
     L.ldpc_hip_comm_allgather.argtypes = [vp, vp, vp, u64]
     L.ldpc_hip_fused_plan_info.restype = None
     L.ldpc_hip_fused_plan_info.argtypes = [vp, vp]
+    L.ldpc_hip_fused_program.restype = i32
+    L.ldpc_hip_fused_program.argtypes = [vp]
     L.ldpc_hip_decode_stages.restype = i32
     L.ldpc_hip_decode_stages.argtypes = [vp, decoder_param, vp]
     L.ldpc_hip_decoder_choice.restype = i32
@@ -325,6 +327,11 @@ class HipDecoder:
         info = (ct.c_int64 * 8)()
         self.lib.ldpc_hip_fused_plan_info(self.ctx, info)
         return dict(zip(("ok", "n_slots", "vnb", "cnl", "small", "calls_stride", "has_shortened", "table_entries"), [int(v) for v in info]))
+
+    def fused_program(self):
+        """Index of the compile-time wave program the fused plan matches (include/ldpc_amd.h, ldpc_hip_fused_program), or -1:
+        the plan is interpreted.  Touches no GPU."""
+        return int(self.lib.ldpc_hip_fused_program(self.ctx))
 
     STAGES = ("whole", "ratio-first", "ratio-separate", "list-chain", "llr-redo", "handover-first", "handover-resume")
 

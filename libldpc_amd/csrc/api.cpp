@@ -825,6 +825,12 @@ void ldpc_hip_fused_plan_info(const ldpc_hip_ctx *ctx, int64_t info[8])
     info[5] = f.calls_stride, info[6] = f.has_shortened ? 1 : 0, info[7] = static_cast<int64_t>(f.vn_slot.size());
 }
 
+int ldpc_hip_fused_program(const ldpc_hip_ctx *ctx)
+{
+    const FusedPlan &f = ctx->eng->fused_plan();
+    return f.ok ? f.program : -1;
+}
+
 int ldpc_hip_decode_stages(const ldpc_hip_ctx *ctx, decoder_param dec, int32_t stages[3])
 {
     const StageSeq seq = ctx->eng->stages(to_params(dec));

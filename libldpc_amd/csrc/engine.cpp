@@ -676,6 +676,7 @@ void Engine::upload_plan()
         dev_fused_.has_shortened = f.has_shortened ? 1 : 0;
         dev_fused_.need_lambda = f.need_lambda ? 1 : 0;
         dev_fused_.wide_exclusive = f.wide_exclusive ? 1 : 0;
+        dev_fused_.program = f.program;
         std::memcpy(dev_fused_.vn_prog, f.vn_prog, sizeof f.vn_prog);
         // the message slots; the prologue stages one 16-byte entry per transmitted bit or column (+ 2) in the same space
         dev_fused_.lds_bytes = static_cast<uint32_t>(std::max<size_t>(8 * static_cast<size_t>(f.n_slots), 16 * (static_cast<size_t>(std::max(p.nc, p.nct)) + 2)) + 15) & ~15u;

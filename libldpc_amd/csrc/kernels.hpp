@@ -194,6 +194,7 @@ struct DevFusedPlan
     const uint32_t *vn_slot;
     const uint32_t *lane_tab;    // [kDecodeWaves][kFusedLaneRows][64]
     const uint32_t *ho_map;      // [n_slots] (plan.hpp, FusedPlan::ho_map)
+    int program;                 // plan.hpp, FusedPlan::program (read by the host side of the launch only: it selects the kernel)
 };
 // the fused family on the LDS-resident decoder's plan: kRatioFirst, kHandoverFirst (separately divided outputs; the messages
 // are handed over as LLRs: handover_llr for the resuming launch) and kWhole = min-sum without early termination

@@ -24,10 +24,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <utility>
 
 #include "device_cn.hpp"
 #include "device_math.hpp"
 #include "device_philox.hpp"
+#include "fused_program.hpp"
 #include "fused_rule.h"
 #include "kernels.hpp"
 #include "launch_lds.hpp"
@@ -404,9 +406,15 @@ __device__ __forceinline__ bool stage_channel(const DecodeArgs &a, const DevFuse
 }
 
 // =======================================================================================================================
-template <bool WANT_LLR, int VNB, int CNL, bool EXCL, bool HO = false, int NK = kNoiseStream>
+// PROG >= 0: the plan has the shape of kFusedPrograms[PROG] (fused_program.hpp; plan.cpp, match_fused_program) and the loop's
+// two passes run the wave's calls as straight-line code instead of interpreting the plan's descriptors; everything else —
+// prologue, vote, escape, epilogue, the routines and the order of a frame's operations — is the interpreter's
+template <bool WANT_LLR, int VNB, int CNL, bool EXCL, bool HO = false, int NK = kNoiseStream, int PROG = -1>
 __device__ __forceinline__ void fused_body(const DecodeArgs &a, const DevFusedPlan &F)
 {
+    static_assert(PROG < 0 || (PROG < kNumFusedPrograms && !WANT_LLR && VNB == 4 && CNL == 1 && EXCL && !HO),
+                  "a wave program is a shape of the small instantiation of the first ratio launch");
+    static_assert(kDecodeWaves == 4 && kFusedProgCalls == 2, "the passes of a wave program are written out for four waves of two calls");
     extern __shared__ double lds[];
     __shared__ int misc[4];
     __shared__ int votes[2][kDecodeWaves];
@@ -742,6 +750,102 @@ __device__ __forceinline__ void fused_body(const DecodeArgs &a, const DevFusedPl
         }
         vn_bits = bits;
     };
+    // ---- the two passes of a wave program: what cn_pass / vn_pass do for this plan, nothing read, nothing tested ----
+    [[maybe_unused]] auto prog_cn = [&]<int W, int C>() { // call C of wave W; C = -1: its call with leaves
+        if constexpr (PROG >= 0)
+        {
+            constexpr FusedProgCall k = C < 0 ? kFusedPrograms[PROG].wave[W].leaf : kFusedPrograms[PROG].wave[W].calls[C];
+            if constexpr (k.cnt0 != 0)
+            {
+                constexpr bool LEAF = C < 0;
+                uint32_t lb0 = 0, lb1 = 0, par = 0;
+                double tot0 = 1.0, tot1 = 1.0;
+                const uint32_t prev0 = LEAF ? leaf_bits << 31 : 0u, prev1 = LEAF ? leaf_bits << 30 : 0u;
+                const double rho0 = LEAF ? leaf_rho[0] : 0.0, rho1 = LEAF ? leaf_rho[1] : 0.0;
+                if constexpr (k.two())
+                    par = cnf_call<k.degree, LEAF, k.flip(), true, false>(msg, k.off0, k.off1, k.cnt0, lane, rho0, rho1, prev0, prev1, lb0, lb1, t, tot0, tot1);
+                else if (lane < static_cast<int>(k.cnt0))
+                    par = cnf_call<k.degree, LEAF, k.flip(), false, false>(msg, k.off0, 0, k.cnt0, lane, rho0, rho1, prev0, prev1, lb0, lb1, t, tot0, tot1);
+                bad |= par;
+                if constexpr (LEAF)
+                    new_leaf_bits |= lb0 | (lb1 << 1);
+            }
+        }
+    };
+    [[maybe_unused]] auto prog_cn_wave = [&]<int W>() { prog_cn.template operator()<W, -1>(), prog_cn.template operator()<W, 0>(), prog_cn.template operator()<W, 1>(); };
+    [[maybe_unused]] auto prog_vn2 = [&]<int W, int S>() { // slots S, S + 1 of wave W: blocks of degree 2
+        if constexpr (PROG >= 0)
+        {
+            constexpr FusedProgWave pw = kFusedPrograms[PROG].wave[W];
+            if constexpr (pw.vn_kind[S] == kFusedVnPair && pw.vn_kind[S + 1] == kFusedVnPair)
+            {
+                uint32_t sga, sgb;
+                double ta, tb;
+                vn2_pair(msg, idx_at(S), idx_at(S + 1), val_at(S), val_at(S + 1), t, sga, sgb, ta, tb);
+                bits |= ((sga >> 31) << S) | ((sgb >> 31) << (S + 1));
+            }
+            else
+            {
+#pragma unroll
+                for (int s = S; s < S + 2; ++s)
+                    if (pw.vn_kind[s] == kFusedVn2 && lane < static_cast<int>(pw.vn_cnt[s]))
+                    {
+                        uint32_t sg;
+                        double tt;
+                        vn2_one(msg, idx_at(s), val_at(s), t, sg, tt);
+                        bits |= (sg >> 31) << s;
+                    }
+            }
+        }
+    };
+    [[maybe_unused]] auto prog_vn_wave = [&]<int W>() {
+        if constexpr (PROG >= 0)
+        {
+            constexpr FusedProgWave pw = kFusedPrograms[PROG].wave[W];
+            if constexpr (pw.vn_kind[0] == kFusedVnWide)
+            {
+                if (pw.vn_cnt[0] == kWaveSize || lane < static_cast<int>(pw.vn_cnt[0]))
+                {
+                    uint32_t sg;
+                    vn_wide<static_cast<int>(pw.vn_deg[0]), true>(msg, wide_idx, my_val[0], t, sg);
+                    bits |= sg >> 31;
+                }
+            }
+            else
+                prog_vn2.template operator()<W, 0>(), prog_vn2.template operator()<W, 2>();
+        }
+    };
+#define LDPC_WAVE_SWITCH(f)                                                                                                                    \
+    switch (wave) /* wave-uniform */                                                                                                           \
+    {                                                                                                                                          \
+    case 0: f.template operator()<0>(); break;                                                                                                 \
+    case 1: f.template operator()<1>(); break;                                                                                                 \
+    case 2: f.template operator()<2>(); break;                                                                                                 \
+    default: f.template operator()<3>(); break;                                                                                                \
+    }
+    auto loop_cn_pass = [&] {
+        if constexpr (PROG >= 0)
+        {
+            bad = 0, new_leaf_bits = 0;
+            LDPC_WAVE_SWITCH(prog_cn_wave)
+        }
+        else
+        {
+            refresh_tables();
+            cn_pass();
+        }
+    };
+    auto loop_vn_pass = [&] {
+        if constexpr (PROG >= 0)
+        {
+            bits = 0;
+            LDPC_WAVE_SWITCH(prog_vn_wave)
+            vn_bits = bits;
+        }
+        else
+            vn_pass();
+    };
+#undef LDPC_WAVE_SWITCH
     if constexpr (HO)
     {
         // Without early termination (detmath.h "Hand-over", separately divided check-node outputs): the checks of a pass come
@@ -849,8 +953,7 @@ __device__ __forceinline__ void fused_body(const DecodeArgs &a, const DevFusedPl
     {
         // ---- loop pass I: check-node pass I, which also sees — in the sign bits of its inputs and the leaf bits — the
         // syndrome of the decisions of variable-node pass I-1 (decoder.cpp:25-45, decoder.h:47-64) ----
-        refresh_tables();
-        cn_pass();
+        loop_cn_pass();
         const int ph = I & 1;
         const bool esc = dm_box_escaped(t.hmax, t.hmin) || t.pmax >= DM_FUSED_P_HI;
         const int wave_vote = (__ballot((bad & 0x80000000u) != 0) != 0) | ((__ballot(esc) != 0) << 1);
@@ -879,7 +982,7 @@ __device__ __forceinline__ void fused_body(const DecodeArgs &a, const DevFusedPl
             break;
         commit_leaves();
 
-        vn_pass();
+        loop_vn_pass();
         __syncthreads();
         ++I;
     }
@@ -1299,6 +1402,14 @@ decode_fused_small(const DecodeArgs a, const DevFusedPlan f)
     fused_body<false, 4, 1, true>(a, f);
 }
 
+// the same for a plan of the shape of kFusedPrograms[P] (fused_program.hpp): the loop without the interpreter
+template <int P>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(LDPC_AMD_FUSED_WAVES, LDPC_AMD_FUSED_WAVES))) void
+decode_fused_prog(const DecodeArgs a, const DevFusedPlan f)
+{
+    fused_body<false, 4, 1, true, false, kNoiseStream, P>(a, f);
+}
+
 template <bool WANT_LLR, int VNB, int CNL>
 __global__ __launch_bounds__(kThreads) void decode_fused_ho_kernel(const DecodeArgs a, const DevFusedPlan f)
 {
@@ -1361,10 +1472,19 @@ __global__ __launch_bounds__(kThreads) void decode_fused_msc_kernel(const Decode
 
 using FusedKernel = void (*)(const DecodeArgs, const DevFusedPlan);
 
+template <int... P>
+FusedKernel fused_prog_kernel(int program, std::integer_sequence<int, P...>)
+{
+    FusedKernel k = nullptr;
+    ((program == P ? (k = decode_fused_prog<P>, 0) : 0), ...);
+    return k;
+}
+
 // The kernel of a stage (null: the fused family has none).  exclusive: the plan's wide_exclusive, which together with no LLR
-// output and the <4, 1> shape selects the small instantiations; counter: the counter-based noise mode
+// output and the <4, 1> shape selects the small instantiations; counter: the counter-based noise mode; program: the plan's
+// wave program (FusedPlan::program), whose kernel takes the small instantiation's place on the reference stream's noise
 template <bool WANT_LLR, int VNB, int CNL>
-FusedKernel fused_kernel_of(Stage stage, bool counter, bool ms_correct, [[maybe_unused]] bool exclusive)
+FusedKernel fused_kernel_of(Stage stage, bool counter, bool ms_correct, [[maybe_unused]] bool exclusive, [[maybe_unused]] int program)
 {
     constexpr bool kHasSmall = !WANT_LLR && VNB == 4 && CNL == 1;
     switch (stage)
@@ -1372,7 +1492,11 @@ FusedKernel fused_kernel_of(Stage stage, bool counter, bool ms_correct, [[maybe_
     case Stage::kRatioFirst:
         if constexpr (kHasSmall)
             if (exclusive)
+            {
+                if (program >= 0 && !counter)
+                    return fused_prog_kernel(program, std::make_integer_sequence<int, kNumFusedPrograms>{});
                 return counter ? decode_ctr_fused_small : decode_fused_small;
+            }
         return counter ? decode_ctr_fused_kernel<WANT_LLR, VNB, CNL> : decode_fused_kernel<WANT_LLR, VNB, CNL>;
     case Stage::kHandoverFirst:
         if constexpr (kHasSmall)
@@ -1402,11 +1526,11 @@ int launch_decode_fused(const DecodeArgs &a, const DevFusedPlan &f, Stage stage,
     const bool counter = a.mode == kModeAwgnCtr || a.mode == kModeBscCtr, exclusive = f.wide_exclusive != 0;
     FusedKernel k = nullptr;
     if (f.vnb <= 4 && f.cnl <= 1)
-        k = a.llr_out ? fused_kernel_of<true, 4, 1>(stage, counter, a.ms_correct, exclusive)
-                      : fused_kernel_of<false, 4, 1>(stage, counter, a.ms_correct, exclusive);
+        k = a.llr_out ? fused_kernel_of<true, 4, 1>(stage, counter, a.ms_correct, exclusive, f.program)
+                      : fused_kernel_of<false, 4, 1>(stage, counter, a.ms_correct, exclusive, f.program);
     else
-        k = a.llr_out ? fused_kernel_of<true, kFusedVnSlots, kFusedLeafCalls>(stage, counter, a.ms_correct, exclusive)
-                      : fused_kernel_of<false, kFusedVnSlots, kFusedLeafCalls>(stage, counter, a.ms_correct, exclusive);
+        k = a.llr_out ? fused_kernel_of<true, kFusedVnSlots, kFusedLeafCalls>(stage, counter, a.ms_correct, exclusive, f.program)
+                      : fused_kernel_of<false, kFusedVnSlots, kFusedLeafCalls>(stage, counter, a.ms_correct, exclusive, f.program);
     if (!k)
         return hipErrorInvalidValue;
     return launch_with_lds(k, dim3(static_cast<unsigned>(a.n_frames)), dim3(kThreads), f.lds_bytes, stream, a, f);

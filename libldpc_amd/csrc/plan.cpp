@@ -1,6 +1,7 @@
 // plan.cpp — builds the device execution plan (see plan.hpp).
 #include "plan.hpp"
 
+#include "fused_program.hpp"
 #include "fused_rule.h"
 
 #include <algorithm>
@@ -9,6 +10,12 @@
 #include <map>
 #include <numeric>
 #include <stdexcept>
+
+// 0: no plan is matched with a compile-time wave program, every fused plan is interpreted (an A/B build:
+// tools/build_variant.sh NAME plan.cpp "-DLDPC_AMD_FUSED_PROGRAM=0")
+#ifndef LDPC_AMD_FUSED_PROGRAM
+#define LDPC_AMD_FUSED_PROGRAM 1
+#endif
 
 namespace ldpc_amd
 {
@@ -762,7 +769,52 @@ FusedPlan build_fused_plan(const LdpcCode &code, const Plan &plan)
                 f.wide_exclusive = false;
     }
     f.ok = true;
+    f.program = match_fused_program(f);
     return f;
+}
+
+// The compile-time wave program (fused_program.hpp) that makes exactly this plan's calls: every field the kernel of a
+// program has compiled in — classes, counts, offsets, order, wave assignment, the variable-node slots — is compared.
+int match_fused_program(const FusedPlan &f)
+{
+#if LDPC_AMD_FUSED_PROGRAM
+    auto same = [](const FusedCall &a, const FusedCall &b) { return a.offs == b.offs && a.cnts == b.cnts && a.cls == b.cls; };
+    auto matches = [&](const FusedProgram &p) {
+        if (f.n_slots != p.n_slots || f.vnb != p.vnb || f.cnl != p.cnl || !f.wide_exclusive)
+            return false;
+        for (int w = 0; w < kDecodeWaves; ++w)
+        {
+            const FusedProgWave &pw = p.wave[w];
+            const FusedCall *leaf = &f.leaf_calls[static_cast<size_t>(w) * kFusedLeafCalls];
+            if (!same(leaf[0], pw.leaf.call()))
+                return false;
+            for (int c = 1; c < kFusedLeafCalls; ++c)
+                if (leaf[c].cnts != 0)
+                    return false;
+            // the wave's list: the program's calls in order, then the zero entry that ends it
+            const FusedCall *calls = &f.calls[static_cast<size_t>(w) * f.calls_stride];
+            int n = 0;
+            while (n < kFusedProgCalls && pw.calls[n].cnt0 != 0)
+                ++n;
+            if (n + 1 > f.calls_stride || calls[n].cnts != 0)
+                return false;
+            for (int c = 0; c < n; ++c)
+                if (!same(calls[c], pw.calls[c].call()))
+                    return false;
+            if (f.vn_prog[w] != pw.vn_prog())
+                return false;
+            for (int s = 0; s < kFusedVnSlots; ++s)
+                if (f.vn_desc[(static_cast<size_t>(w) * kFusedVnSlots + s) * 4] != (s < 4 ? pw.vn_desc(s) : 0u))
+                    return false;
+        }
+        return true;
+    };
+    if (f.ok)
+        for (int p = 0; p < kNumFusedPrograms; ++p)
+            if (matches(kFusedPrograms[p]))
+                return p;
+#endif
+    return -1;
 }
 
 // Steps of the layered schedule: check nodes in file order within each degree, each put into the first step of its degree

@@ -301,6 +301,8 @@ struct FusedPlan
     // a wave that serves a block through register-held offsets (slot 0, degree 3..15) serves no other, and no block goes
     // through the slot table: what the small instantiation of the kernel is compiled for
     bool wide_exclusive = false;
+    // index of the compile-time wave program of this plan's shape (fused_program.hpp), or -1: the kernel interprets the plan
+    int program = -1;
     std::vector<FusedCall> leaf_calls; // [kDecodeWaves][kFusedLeafCalls]
     std::vector<FusedCall> calls;      // [kDecodeWaves][calls_stride], each row ends in a zero entry
     int calls_stride = 0;

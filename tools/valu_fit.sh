@@ -10,15 +10,15 @@ mkdir -p "$out"; export TMPDIR=/tmp
 root=${GRAFT_REPO_ROOT:-$PWD}
 : > "$out/points.jsonl"
 for x in $points; do
-    (cd /tmp && timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU -d "$root/$out/x$x" -o run --output-format csv -- python3 "$root/tools/pmc_probe.py" --config 2 --x "$x" --steps 3 --warmup 2 > "$root/$out/x$x.log" 2>&1)
-    python3 - "$out" "$x" <<'PY' >> "$out/points.jsonl"
+    (cd /tmp && timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU -d "$root/$out/x$x" -o run --output-format csv -- python3 "$root/tools/pmc_probe.py" --config 2 --x "$x" --steps 3 --warmup 2 > "$root/$out/x$x.log" 2>&1) || { echo "point $x failed: see $out/x$x.log" >&2; exit 1; }
+    python3 - "$out" "$x" <<'PY' >> "$out/points.jsonl" || exit 1
 import csv, glob, json, sys
 out, x = sys.argv[1], sys.argv[2]
 line = json.loads([l for l in open(f"{out}/x{x}.log") if l.startswith("{")][-1])
 f = glob.glob(f"{out}/x{x}/**/*counter_collection.csv", recursive=True)[0]
 per = {}
 for r in csv.DictReader(open(f)):
-    if ("decode_fused_small" in r["Kernel_Name"] or "decode_kernel_w5" in r["Kernel_Name"]) and r["Counter_Name"] == "SQ_INSTS_VALU":
+    if ("decode_fused_small" in r["Kernel_Name"] or "decode_fused_prog" in r["Kernel_Name"] or "decode_kernel_w5" in r["Kernel_Name"]) and r["Counter_Name"] == "SQ_INSTS_VALU":
         per[r["Dispatch_Id"]] = per.get(r["Dispatch_Id"], 0.0) + float(r["Counter_Value"])
 launches = sorted(per.items(), key=lambda kv: int(kv[0]))[-line["steps"]:]
 valu = sum(v for _, v in launches) * 64
