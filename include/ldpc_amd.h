@@ -346,7 +346,21 @@ int ldpc_hip_min_sum_layered_fixed(const ldpc_hip_ctx *ctx, int *msg_bits, int *
    slot; behind the larger of the two the 128-byte correction table.  tests/golden/h.txt: 9 344 bytes, 17 frames per CU. */
 int64_t ldpc_hip_layered_fixed_lds_bytes(const ldpc_hip_ctx *ctx);
 
-/* decode n frames of given LLRs llr_in[n][nc] (column order, device or host). 0 on success. */
+/* decode n frames of given LLRs llr_in[n][nc] (column order, device or host). 0 on success.
+   Which values a caller may hand in, for "BP" and "BP_MS" (tests/test_gpu_edge_llrs.py, tests/edge_llrs.py):
+     - Finite values of any magnitude — signed zeros, subnormals, values on the limits the arithmetic forms switch at
+       (detmath.h: 2^-52, 40, ln 2^220, 166, ln 2^240, 600, 700 ...), 1e300 — and infinities, as long as the reference's
+       arithmetic makes no NaN of them, are decoded bit for bit as the det-mode oracle decodes them: iters, hard, bit_errors,
+       llr_out and llr_in.  A frame that holds an input 0 < |L| < 2^-52 (e^L rounds to exactly 1.0 and the sign of L would be
+       lost) or |L| > 166 never takes the likelihood-ratio forms, and a check node that receives such a tiny message is
+       evaluated with the reference's expression term by term (detmath.h, dm_ratio_llr_refused, dm_llr_tiny): a tiny positive
+       LLR decides 0 and a frame of tiny LLRs converges as in the reference.
+     - A frame in which the reference's arithmetic makes a NaN — a NaN input; infinite inputs on all or all but one of the
+       neighbours of one check node (two of the three of a degree-3 node: the third receives +-inf and answers inf - inf) —
+       has unspecified outputs within iters <= dec.iterations and hard in {0, 1}.  The same call on the same batch gives the
+       same bits again.  (Min-sum takes its minima with v_min_f64, which drops a NaN operand where the reference's std::min
+       keeps or drops it by position: profiles/README.md, "Class-N frames", lists what each decoder returns.)
+     - Such a frame never affects another frame of the batch. */
 int ldpc_hip_decode_batch(ldpc_hip_ctx *ctx, decoder_param dec, uint64_t n, const double *llr_in,
                           const ldpc_hip_out *out, void *hip_stream);
 
@@ -356,7 +370,11 @@ int ldpc_hip_decode_batch(ldpc_hip_ctx *ctx, decoder_param dec, uint64_t n, cons
    The call decodes the WIDENED array W[n][nc], binary64:
      LDPC_HIP_LLR_F64  W = the value itself;
      LDPC_HIP_LLR_F32, LDPC_HIP_LLR_F16 (IEEE binary16)  W = the value widened to binary64, which is exact: NaN stays NaN,
-                       infinities and signed zeros are kept, binary16 subnormals become exact doubles;
+                       infinities and signed zeros are kept, binary16 subnormals become exact doubles.  W is then under
+                       the contract of ldpc_hip_decode_batch for non-finite inputs: a value beyond the type's range is an
+                       infinity in W (binary16: beyond 65504, so a shortened column's 99999.9), and a code with two
+                       shortened columns on one check node of degree 3 — tests/orc.py shortened_variant — then holds two
+                       infinities there: outputs unspecified, though still equal to ldpc_hip_decode_batch on W;
      LDPC_HIP_LLR_I8   an element k stands for W = fl((double) k * D), D = the `step` of the fixed-point mode in force: what a
                        demapper with q-bit outputs delivers.  Accepted only when dec.type is "BP_MS" and
                        ldpc_hip_set_min_sum_quantization or ldpc_hip_set_min_sum_layered_fixed is on; otherwise (sum-product,
@@ -475,7 +493,8 @@ int ldpc_hip_bit_errors_batch(ldpc_hip_ctx *ctx, uint64_t n, const void *a, int 
        LDPC_HIP_NOISE_COUNTER, the same channel, x and seed, for the stream's frames first_frame + f and their codewords.
      Element type, L the binary64 value above.  LDPC_HIP_LLR_F64: L.  LDPC_HIP_LLR_F32: L rounded to nearest-even.
        LDPC_HIP_LLR_F16: that binary32 value rounded to nearest-even (two roundings); 99999.9 becomes +infinity, which the
-       decoders widen back to +infinity.  LDPC_HIP_LLR_I8: clamp(rint(fl(L * inv)), -Qmax, +Qmax), inv = fl(1 / step), Qmax =
+       decoders widen back to +infinity (two such columns on one check node: the non-finite contract at ldpc_hip_decode_batch).
+       LDPC_HIP_LLR_I8: clamp(rint(fl(L * inv)), -Qmax, +Qmax), inv = fl(1 / step), Qmax =
        2^(q_bits - 1) - 1: item 1 of ldpc_hip_set_min_sum_quantization, the clamp applied in binary64, a NaN gives 0 — feed it to
        ldpc_hip_decode_batch_typed under a fixed-point mode of the same step.
    How it runs: one launch per 2^31 / (lanes per frame) frames at most; a lane owns one Philox block of a frame — four symbols,

@@ -307,7 +307,9 @@ DM_FN double dm_boxplus(double x, double y)
  *
  * E must be a normal number: the caller uses this form only while every input of the node satisfies
  * |v| <= DM_SHARED_LIMIT (partial results never exceed their smaller operand in magnitude) and evaluates the
- * node with dm_boxplus otherwise (e.g. two shortened bits, LLR 99999.9, on one check node).
+ * node with dm_boxplus otherwise (e.g. two shortened bits, LLR 99999.9, on one check node).  It does the same when an
+ * input is tiny (dm_llr_tiny below: 0 < |v| < 2^-52): E(v) rounds to exactly 1 and the form would answer 0 where the
+ * reference's expression answers sign * min — all that decides a frame whose LLRs are that small.
  * ------------------------------------------------------------------------------------------------ */
 #define DM_SHARED_LIMIT 600.0
 
@@ -424,6 +426,19 @@ DM_FN double dm_sat_llr(uint32_t sign_word, double mu, double sum) { return dm_s
 #define DM_RATIO_HI 0x1p240
 #define DM_RATIO_LO 0x1p-240
 #define DM_RATIO_LLR_LIMIT 166.0
+/*
+ * The admission rule for a channel LLR, in one place: the frame leaves the ratio form at once when dm_ratio_llr_refused(L)
+ * for any of its inputs.  Beyond the limit (NaN included) e^L has no room; and for 0 < |L| < 2^-52 rho = e^L rounds to
+ * exactly 1.0, the sign of L is lost, and the tie rule of the ratio form (lambda >= 1 decides 1) would decide a tiny
+ * positive LLR as 1 where the reference's `L <= 0` decides 0.  +-0 are ties in the reference too and stay admitted.
+ */
+#define DM_RATIO_LLR_TINY 0x1p-52
+DM_FN int dm_llr_tiny(double a) { return (a < DM_RATIO_LLR_TINY) & (a != 0.0); } /* a = |L| */
+DM_FN int dm_ratio_llr_refused(double L)
+{
+    const double a = __builtin_fabs(L);
+    return (!(a <= DM_RATIO_LLR_LIMIT)) | dm_llr_tiny(a);
+}
 
 DM_FN int dm_ratio_out_of_range(double r) { return !(r >= DM_RATIO_LO && r < DM_RATIO_HI); } /* NaN: out */
 /*

@@ -82,14 +82,16 @@ __device__ __forceinline__ void cn_core(double (&v)[D], MsCorr c = MsCorr{1.0, 0
     if constexpr (!MINSUM && D > 2) // a degree-2 node only swaps its two inputs: the generic code below
     {
         // sum-product: saturated form when it applies; else the recursion is carried in E = e^-|L| (detmath.h,
-        // dm_e_combine / dm_efrac / dm_e_to_llr) while every input is within DM_SHARED_LIMIT; otherwise the direct
+        // dm_e_combine / dm_efrac / dm_e_to_llr) while every input is within DM_SHARED_LIMIT and none is tiny; otherwise the direct
         // box-plus below
         double amax = 0.0, mu = __builtin_huge_val();
+        int tiny = 0; // an input whose E = e^-|v| rounds to 1 (detmath.h, dm_llr_tiny): the direct box-plus
 #pragma unroll
         for (int j = 0; j < D; ++j)
         {
             amax = __builtin_fmax(amax, __builtin_fabs(v[j]));
             mu = __builtin_fmin(mu, __builtin_fabs(v[j]));
+            tiny |= dm_llr_tiny(__builtin_fabs(v[j]));
         }
         if (mu >= DM_SAT_MIN && ((D >= 5 && D <= 16) || amax - mu <= DM_SHARED_LIMIT))
         {
@@ -127,7 +129,7 @@ __device__ __forceinline__ void cn_core(double (&v)[D], MsCorr c = MsCorr{1.0, 0
             }
             return;
         }
-        if (amax <= DM_SHARED_LIMIT)
+        if (amax <= DM_SHARED_LIMIT && !tiny)
         {
             double ev[D];
             uint32_t sv[D], sF[D], sB[D];

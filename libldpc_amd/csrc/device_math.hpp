@@ -71,7 +71,11 @@ __device__ __forceinline__ double std_min(double a, double b) { return (b < a) ?
 // signbit(x) xor signbit(y).  Three instructions — v_min_f64 with |.| source modifiers, an xor of the high words, a bit
 // field insert — where the expression as written compiles to ten (two sign extractions, an integer product, its
 // conversion, a compare, two selects, the multiplication): 6 of the 16 lane-instructions per edge-update of the
-// min-sum kernel.  std::min(a, b) = (b < a) ? b : a and v_min_f64 differ on NaNs only, which a message never is; the
+// min-sum kernel.  std::min(a, b) = (b < a) ? b : a and v_min_f64 differ on NaNs only: std::min returns its first operand
+// whenever the other is a NaN (a NaN or not by position), v_min_f64 the operand that is not one.  A min-sum message CAN be a
+// NaN — a NaN input, or two infinite inputs on one check node of degree 3, whose third neighbour answers inf - inf (a
+// shortened column's 99999.9 is +inf in binary16) — and the instruction then departs from the reference: such frames are
+// outside the parity contract (include/ldpc_amd.h, ldpc_hip_decode_batch; tests/test_gpu_edge_llrs.py holds containment).  The
 // instruction is written out because fmin() as a builtin brings a canonicalising v_max_f64 per operand with it.
 __device__ __forceinline__ double box_minsum(double x, double y)
 {

@@ -78,7 +78,7 @@ __device__ __forceinline__ void cn_update(double *m, int stride, MsCorr c = MsCo
 // A check node wider than the register tiles (degree > 16, memory-resident decoder only): the forward partial
 // results F[j] go through a per-frame scratch array laid out like the message array, the backward ones stay in a
 // register; same recursion, same order, same arithmetic as cn_core (E-domain form while every input is within
-// DM_SHARED_LIMIT and the node has at most 64 edges — the limit of the oracle's shared form — else the reference
+// DM_SHARED_LIMIT, none is tiny and the node has at most 64 edges — the limit of the oracle's shared form — else the reference
 // expression term by term).  decoder.cpp:31-44.
 // E-domain form of a wide node (SAT: saturated form, detmath.h): partial results as (sign, fraction n/d of E = e^-|L|), the
 // sign rides in n's sign bit (n > 0); F[j] (inputs 0..j) goes to scr[j] (n) and scr2[j] (d) for 1 <= j <= d-3, the
@@ -152,17 +152,19 @@ __device__ __noinline__ void cn_wide(double *m, double *scr, double *scr2, int s
     if (!MINSUM && d <= 64)
     {
         double amax = 0.0, mu = __builtin_huge_val();
+        int tiny = 0;
         for (int j = 0; j < d; ++j)
         {
             amax = __builtin_fmax(amax, __builtin_fabs(m[j * stride]));
             mu = __builtin_fmin(mu, __builtin_fabs(m[j * stride]));
+            tiny |= dm_llr_tiny(__builtin_fabs(m[j * stride]));
         }
         if (dm_sat_applies(mu, amax))
         {
             cn_wide_eform<true>(m, scr, scr2, stride, d, mu);
             return;
         }
-        if (amax <= DM_SHARED_LIMIT)
+        if (amax <= DM_SHARED_LIMIT && !tiny)
         {
             cn_wide_eform<false>(m, scr, scr2, stride, d, 0.0);
             return;
@@ -1174,7 +1176,7 @@ __device__ __forceinline__ bool decode_body(const DecodeArgs &a, const uint32_t 
             if (P.rank_slot0[r] != kNoSlot)
             {
                 const double L = llr[r];
-                if (!(__builtin_fabs(L) <= DM_RATIO_LLR_LIMIT))
+                if (dm_ratio_llr_refused(L))
                     escaped = ~0u;
                 llr[r] = dm_exp_clamped(0.0 - L);
             }
@@ -1208,7 +1210,7 @@ __device__ __forceinline__ bool decode_body(const DecodeArgs &a, const uint32_t 
 #pragma unroll
             for (int w = 0; w < VNB; ++w)
             {
-                if (!(__builtin_fabs(my_llr[w]) <= DM_RATIO_LLR_LIMIT))
+                if (dm_ratio_llr_refused(my_llr[w]))
                     escaped = ~0u;
                 my_llr[w] = dm_exp_clamped(0.0 - my_llr[w]);
             }

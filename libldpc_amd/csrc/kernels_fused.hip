@@ -440,7 +440,7 @@ __device__ __forceinline__ void fused_body(const DecodeArgs &a, const DevFusedPl
         // code: nowhere — its wide nodes are punctured): no division in the prologue
         const bool need_lambda = F.need_lambda != 0 || given;
         auto put = [&](int s, double L) {
-            if (!(__builtin_fabs(L) <= DM_RATIO_LLR_LIMIT))
+            if (dm_ratio_llr_refused(L))
                 t.hmax = 0xFFFFFFFFu; // the frame leaves the ratio form at once
             stage[s] = double2{need_lambda ? dm_exp_clamped(0.0 - L) : 1.0, dm_exp_clamped(L)};
         };

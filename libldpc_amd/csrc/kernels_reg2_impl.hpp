@@ -171,7 +171,7 @@ __device__ __forceinline__ bool reg2_frame(const DecodeArgs &a, const DevReg2Pla
             const double L = llr[R.vn_rank[(i * W + wave) * 64 + lane]];
             if constexpr (RATIO)
             {
-                if (!(__builtin_fabs(L) <= DM_RATIO_LLR_LIMIT))
+                if (dm_ratio_llr_refused(L))
                     escaped = ~0u;
                 lam_i = dm_exp_clamped(0.0 - L);
                 lds[vb.tot_off + lane] = dm_ratio_div(1.0, lam_i);

@@ -42,7 +42,7 @@
             if (P.rank_slot0[r] != kNoSlot)
             {
                 const double L = llr[r];
-                if (!(__builtin_fabs(L) <= DM_RATIO_LLR_LIMIT))
+                if (dm_ratio_llr_refused(L))
                     escaped = ~0u;
                 llr[r] = dm_exp_clamped(0.0 - L);
             }

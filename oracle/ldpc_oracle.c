@@ -370,7 +370,7 @@ static void dec_free(dec_t *d)
  * ORC_MATH_DET only: the forward/backward recursion (decoder.cpp:31-44) carried in E = e^-|L| (detmath.h,
  * dm_e_combine / dm_e_to_llr) — the arithmetic the HIP kernel runs — or, when every input is large and they lie
  * close together, the saturated form (detmath.h, dm_sat_*).  Returns 0 (nothing done) when neither applies (an input
- * exceeds DM_SHARED_LIMIT); the caller then evaluates this node with dm_boxplus, as the kernel does.
+ * exceeds DM_SHARED_LIMIT or is tiny, dm_llr_tiny); the caller then evaluates this node with dm_boxplus, as the kernel does.
  * F[cw-1] and B[0], which the reference computes and never reads, are not evaluated.
  */
 static int cn_update_det_shared(dec_t *d, const int *cn, int cw)
@@ -428,7 +428,7 @@ static int cn_update_det_shared(dec_t *d, const int *cn, int cw)
         return 1;
     }
     for (int j = 0; j < cw; ++j)
-        if (!(fabs(v[j]) <= DM_SHARED_LIMIT))
+        if (!(fabs(v[j]) <= DM_SHARED_LIMIT) || dm_llr_tiny(fabs(v[j])))
             return 0;
     for (int j = 0; j < cw; ++j)
     {
@@ -746,7 +746,7 @@ static int dec_decode_ratio(dec_t *d, int allow_shared)
         if (H->cptr[i + 1] == H->cptr[i])
             continue; /* isolated variable node: its LLR multiplies nothing */
         double L = d->llr_in[i];
-        escaped |= !(fabs(L) <= DM_RATIO_LLR_LIMIT);
+        escaped |= dm_ratio_llr_refused(L);
         lam[i] = dm_exp_clamped(0.0 - L);
         double v0 = 1.0 / lam[i];
         for (int p = H->cptr[i]; p < H->cptr[i + 1]; ++p)
@@ -900,7 +900,7 @@ static int dec_decode_fused(dec_t *d)
     for (int i = 0; i < nc; ++i)
     {
         double L = d->llr_in[i];
-        escaped |= !(fabs(L) <= DM_RATIO_LLR_LIMIT);
+        escaped |= dm_ratio_llr_refused(L);
         lam[i] = dm_exp_clamped(0.0 - L);
         rho[i] = dm_exp_clamped(L); /* (the fused form takes both from the exponential: no division in its prologue) */
         for (int p = H->cptr[i]; p < H->cptr[i + 1]; ++p)
