@@ -716,6 +716,91 @@ int ldpc_hip_osd_batch(ldpc_hip_ctx *ctx, uint32_t candidates, uint64_t n, const
    tests/golden/h.txt (mc = 1024, nc = 1152): V = 18, S = 19, 155 648 + 432 + 2 304 + 384 = 158 768 bytes: one frame per CU. */
 int64_t ldpc_hip_osd_lds_bytes(const ldpc_hip_ctx *ctx);
 
+/* Quantized min-sum decoding of frames of LLRs TOWARD A GIVEN SYNDROME (libldpc_amd/csrc/kernels_syndrome_decode.hip): which
+   word x with H x = s fits these LLRs, for the s the caller holds — every other decoder of this library asks for H x = 0.
+   The decoder of syndrome-based source coding with side information (Slepian-Wolf) and of information reconciliation: one
+   side sends s = H x of ANY word x (ldpc_hip_syndrome_batch writes it, packed), the other decodes its noisy copy of x toward
+   s; and of every syndrome-measuring application: s the measured syndrome, the LLRs one prior row shared by every shot
+   (LDPC_HIP_SYNDROME_SHARED_LLR), the output an error estimate.  NON-PARITY (the reference has no such decoder).
+   The common rules of this block hold: device or host buffers, checks before the GPU naming the entry in
+   ldpc_hip_last_error, n == 0 returns 0 after them, every output may be NULL (all NULL: nothing is launched), ordered on
+   hip_stream, a frame's results do not depend on which frames share its call, every output bit is determined.  NO SETTING AND
+   NO STATE OF THE STREAM INTERFACE IS READ OR CHANGED: everything the call uses is in *p; the context's quantization,
+   correction, schedule and ternary settings are ignored.
+   In:  llr[n][nc], column order, elements of llr_type (LDPC_HIP_LLR_F64 / F32 / F16 / I8), read in place in their own type
+        (no widening launch, no binary64 staging in LDS).  All nc columns are the caller's values, as in
+        ldpc_hip_decode_batch: punctured and shortened columns get no substitute.  With LDPC_HIP_SYNDROME_SHARED_LLR in
+        p->flags llr is ONE row [nc], used for every frame.
+        syndrome[n][mc] in syndrome_format (LDPC_HIP_BITS_U8: a byte per check node, non-zero = 1; LDPC_HIP_BITS_PACKED32:
+        ceil(mc / 32) words per row), exactly what ldpc_hip_syndrome_batch writes: bit r is check node r in file row order.
+        NULL = the all-zero syndrome.  The bits of a row's last word from mc on are ignored.
+   Out: hard_bits[n][ceil(nc / 32)] (the layout of hard_bits in ldpc_hip_decode_batch_typed, the bits of a row's last word
+        from nc on 0), iters[n], weight[n], llr_out[n][nc] (binary64, column order).
+   Arithmetic: items 1..7 of ldpc_hip_set_min_sum_quantization with q = p->q_bits, D = p->step, Qmax = 2^(q-1) - 1,
+   inv = fl(1 / D) and lut built from (p->scale, p->offset) by the same host routine (item 3), with two changes and two
+   additions.  All integer after the quantizer:
+     1. Quantizer.  L[v] = clamp(rint(fl(W[v] * inv)), -Qmax, +Qmax), W the element widened exactly to binary64; a NaN gives
+        0, infinities saturate.  For LDPC_HIP_LLR_I8, L = clamp(k, -Qmax, +Qmax) — the equality stated for the direct
+        fixed-point layered path (ldpc_hip_decode_batch_typed): it is the quantizer applied to fl(k * D) for every step the
+        call takes.
+     2. CHANGE, check node sign: in check node c, c2v_j is negative iff (the number of other v2c_k < 0) + s[c] is odd.
+        Magnitudes, the table and the variable nodes are items 3..5 unchanged.
+     3. CHANGE, stop rule: with early_term the frame stops after the first iteration whose decisions satisfy
+        XOR of hard over the row == s[c] for every check node (instead of == 0).
+     4. iters = the index of the iteration whose decisions met the test (the reference's convention, as everywhere),
+        otherwise `iterations`.
+     5. ADDITION, weight[f] = the number of check nodes whose test fails on the frame's final decisions, also without
+        early termination: 0 iff the returned word has syndrome s.
+     6. ADDITION, iterations == 0 returns the quantized input: A = L, hard = (L <= 0), llr_out = fl(L * D), iters = 0, and the
+        weight of that.  Deliberately not the all-zero rows of the stream decoders: the inputs are the caller's data, as
+        ldpc_hip_erasure_decode_batch argues.
+     7. llr_out[v] = fl((double) A[v] * D) of the last iteration the frame ran.
+   Identities: with syndrome == NULL and iterations > 0, iters, the decisions and llr_out are those of
+   ldpc_hip_decode_batch_typed under ldpc_hip_set_min_sum_quantization(q, D) and ldpc_hip_set_min_sum_correction(scale,
+   offset); with any s, the messages are those of that decoder on the code [H | I] (mc further columns, column nc + r in
+   row r alone) fed 99999.9 (1 - 2 s[r]) there — the route this entry replaces —, so without early termination the first nc
+   decisions and totals agree after any number of iterations.  With early termination iters agrees too whenever
+   lut[Qmax] < Qmax (any scale below 1 that moves Qmax): an extra column decides on +-Qmax + c2v, and with (1, 0) a check node
+   whose other inputs all sit at Qmax returns -+Qmax, the total is 0, the tie decides 1 and the augmented route runs on
+   after this entry has met s.
+   Refused (host only, -1): a null p; q_bits outside 2..8; a step that is NaN, <= 0 or outside [2^-20, 2^20]; a scale
+   outside (0, 1], an offset outside [0, 1e6], a NaN in either; early_term other than 0 / 1; an unknown flag bit, llr_type
+   or syndrome_format; a NULL llr with n > 0; a code the call does not take.
+   Which codes it takes: every code the library loads in which every check node has at least two entries, with at most
+   65 535 columns and the frame's LDS (below) within 160 KB; otherwise ldpc_hip_syndrome_decode_lds_bytes returns -1 and
+   there is no other kernel.
+   How it runs: one workgroup of 256 threads per frame on the tables of quantized min-sum (built once per context, uploaded
+   at the first call that needs them); a thread per column quantizes the element it reads and stores the byte at the
+   column's place in the kernel's order; a thread per check node fetches its syndrome bit through the map from the kernel's
+   check-node order to file rows; a byte per message in LDS; the packed decisions by a ballot per 64 columns; one launch per
+   2^20 frames at most.  OSD toward a syndrome is not offered; llr_out is there to feed it later.  ldpcsim, simulate() and
+   the stream interface are not touched. */
+enum
+{
+    LDPC_HIP_SYNDROME_SHARED_LLR = 1
+};
+typedef struct
+{
+    uint32_t iterations;
+    int early_term; /* 0 / 1 */
+    int q_bits;     /* 2..8 */
+    double step;    /* 2^-20 .. 2^20 */
+    double scale;   /* (0, 1] */
+    double offset;  /* [0, 1e6] */
+    int flags;      /* LDPC_HIP_SYNDROME_SHARED_LLR or 0 */
+} ldpc_hip_syndrome_decode;
+int ldpc_hip_syndrome_decode_batch(ldpc_hip_ctx *ctx, const ldpc_hip_syndrome_decode *p, uint64_t n, const void *llr, int llr_type,
+                                   const void *syndrome, int syndrome_format, uint32_t *hard_bits, uint32_t *iters,
+                                   uint32_t *weight, double *llr_out, void *hip_stream);
+/* LDS bytes one frame of ldpc_hip_syndrome_decode_batch takes on this context's code (host only), -1 for a code the call
+   does not take.  With `slots` = the check-node degrees, each rounded up to a multiple of 4, summed (one byte per message, a
+   check node's messages padded to whole words), and every term rounded up to 16:
+     bytes = r16(slots) + r16(4 nc) + 160 + r16(4 ceil(mc / 32)) + r16(nc)
+   — the messages; the nc 32-bit totals; the 128-byte table with 32 bytes of votes and partial sums; the frame's syndrome, a
+   bit per check node; the nc quantized inputs.  There is no binary64 area.
+   tests/golden/h.txt (nc = 1152, mc = 1024): see DESIGN.md section 4 for the figure and the frames per CU. */
+int64_t ldpc_hip_syndrome_decode_lds_bytes(const ldpc_hip_ctx *ctx);
+
 /* channel point x of stream mt19937_64(seed): set_channel_param semantics, frame position := 0 */
 int ldpc_hip_stream_begin(ldpc_hip_ctx *ctx, int channel, uint64_t seed, double x);
 /* advance the stream by n frames without decoding them */

@@ -514,6 +514,29 @@ int64_t ldpc_hip_osd_lds_bytes(const ldpc_hip_ctx *ctx)
     return bytes;
 }
 
+int ldpc_hip_syndrome_decode_batch(ldpc_hip_ctx *ctx, const ldpc_hip_syndrome_decode *p, uint64_t n, const void *llr, int llr_type,
+                                   const void *syndrome, int syndrome_format, uint32_t *hard_bits, uint32_t *iters, uint32_t *weight,
+                                   double *llr_out, void *hip_stream)
+{
+    return guarded([&] {
+        Engine::SyndromeDecodeSpec spec;
+        if (p)
+        {
+            spec.iterations = p->iterations, spec.early_term = p->early_term, spec.q_bits = p->q_bits;
+            spec.step = p->step, spec.scale = p->scale, spec.offset = p->offset, spec.flags = p->flags;
+        }
+        ctx->eng->syndrome_decode_batch(p ? &spec : nullptr, n, llr, llr_type, syndrome, syndrome_format, hard_bits, iters, weight, llr_out,
+                                        hip_stream);
+    });
+}
+
+int64_t ldpc_hip_syndrome_decode_lds_bytes(const ldpc_hip_ctx *ctx)
+{
+    int64_t bytes = -1; // (the tables are built on the host at the first call; -1 for a code the call does not take)
+    guarded([&] { bytes = ctx->eng->syndrome_decode_lds_bytes(); });
+    return bytes;
+}
+
 int64_t ldpc_hip_layered_fixed_direct_lds_bytes(const ldpc_hip_ctx *ctx)
 {
     int64_t bytes = -1; // (the plan builder allocates; -1 for every code the layered plan refuses)

@@ -2103,6 +2103,95 @@ void Engine::osd_batch(uint32_t candidates, uint64_t n, const void *llr, int llr
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Quantized min-sum decoding toward a given syndrome (kernels_syndrome_decode.hip)
+int64_t Engine::syndrome_decode_lds_bytes()
+{
+    const QmsPlan &q = qms_plan();
+    if (!q.ok || plan_.nc > 0xFFFF || plan_.mc <= 0)
+        return -1;
+    const size_t bytes = ldpc_amd::syndrome_decode_lds_bytes(q.slots, static_cast<size_t>(plan_.nc), static_cast<size_t>(plan_.mc));
+    return bytes <= kCuLdsBytes ? static_cast<int64_t>(bytes) : -1;
+}
+
+std::string Engine::syndrome_decode_refusal(const SyndromeDecodeSpec *spec, int llr_type, int syndrome_format)
+{
+    const std::string who = "ldpc_hip_syndrome_decode_batch: ";
+    if (!spec)
+        return who + "null parameters";
+    if (spec->q_bits < 2 || spec->q_bits > 8)
+        return who + "q_bits " + std::to_string(spec->q_bits) + " is outside 2..8";
+    if (!(spec->step > 0.0) || spec->step < 0x1p-20 || spec->step > 0x1p20) // (a NaN fails the first)
+        return who + "the step must lie in [2^-20, 2^20]";
+    if (!(spec->scale > 0.0) || spec->scale > 1.0)
+        return who + "the scale must lie in (0, 1]";
+    if (!(spec->offset >= 0.0) || spec->offset > 1e6)
+        return who + "the offset must lie in [0, 1e6]";
+    if (spec->early_term != 0 && spec->early_term != 1)
+        return who + "early_term " + std::to_string(spec->early_term) + " is neither 0 nor 1";
+    if (spec->flags & ~kSyndromeSharedLlr)
+        return who + "unknown flag bits " + std::to_string(spec->flags & ~kSyndromeSharedLlr);
+    if (llr_type_bytes(llr_type) == 0)
+        return who + "unknown LLR type " + std::to_string(llr_type) + " (0 = binary64, 1 = binary32, 2 = binary16, 3 = int8)";
+    if (std::string why = bits_format_refusal("ldpc_hip_syndrome_decode_batch", "syndrome", syndrome_format); !why.empty())
+        return why;
+    if (syndrome_decode_lds_bytes() < 0)
+        return who + "the code of " + std::to_string(plan_.mc) + " x " + std::to_string(plan_.nc) +
+               " is not taken: more than 65 535 columns, a check node with fewer than two entries, or a frame beyond the 160 KB of LDS "
+               "of a CU (ldpc_hip_syndrome_decode_lds_bytes; there is no other kernel)";
+    return "";
+}
+
+void Engine::syndrome_decode_batch(const SyndromeDecodeSpec *spec, uint64_t n, const void *llr, int llr_type, const void *syndrome,
+                                   int syndrome_format, uint32_t *hard_bits, uint32_t *iters, uint32_t *weight, double *llr_out, void *stream)
+{
+    if (const std::string why = syndrome_decode_refusal(spec, llr_type, syndrome_format); !why.empty())
+        throw std::runtime_error(why);
+    if (n && !llr)
+        throw std::runtime_error("ldpc_hip_syndrome_decode_batch: null llr");
+    if (n == 0 || (!hard_bits && !iters && !weight && !llr_out))
+        return;
+    upload_plan();
+    upload_qms_plan();
+    if (!sd_cn_row_)
+        sd_cn_row_ = static_cast<const uint32_t *>(upload_table(plan_.cn_rank_row.data(), plan_.cn_rank_row.size() * 4, "check node order"));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint64_t nc = static_cast<uint64_t>(plan_.nc), mc = static_cast<uint64_t>(plan_.mc), words = (nc + 31) / 32;
+    const bool shared = (spec->flags & kSyndromeSharedLlr) != 0;
+    SyndromeDecodeArgs a{};
+    a.nc = static_cast<uint32_t>(nc), a.mc = static_cast<uint32_t>(mc), a.words = static_cast<uint32_t>(words);
+    a.syn_words = static_cast<uint32_t>((mc + 31) / 32);
+    a.iterations = spec->iterations, a.early_term = spec->early_term;
+    a.llr_type = llr_type, a.syndrome_format = syndrome_format, a.shared_llr = shared ? 1 : 0;
+    {
+        const QmsArgs q = quantizer_args<QmsArgs>(spec->step, spec->q_bits, spec->scale, spec->offset); // (the same host routine)
+        a.qmax = q.qmax, a.step = q.step, a.inv = q.inv;
+        std::memcpy(a.lut, q.lut, sizeof a.lut);
+    }
+    a.lds_bytes = static_cast<uint32_t>(syndrome_decode_lds_bytes());
+    a.col_rank = dev_.col_rank, a.cn_row = sd_cn_row_;
+    const size_t elem = llr_type_bytes(llr_type), in_row = elem * nc, syn_row = bits_row_bytes(syndrome_format, mc);
+    DeviceBuffer &llr_stage = llr_type == kLlrF64 ? stage_in_ : stage_typed_;
+    if (shared) // one row for every frame: staged once
+        a.llr = stage_input(llr, in_row, llr_stage, stream);
+    const uint64_t sub = std::max<uint64_t>(gf2_sub_batch() / elem, 1); // (elements of up to 8 bytes, not bits)
+    for (uint64_t done = 0; done < n; done += sub)
+    {
+        const uint64_t m = std::min(sub, n - done);
+        if (!shared)
+            a.llr = stage_input(static_cast<const char *>(llr) + in_row * done, in_row * m, llr_stage, stream);
+        a.syndrome = syndrome ? stage_input(static_cast<const char *>(syndrome) + syn_row * done, syn_row * m, stage_in_b_, stream) : nullptr;
+        OutStage st;
+        a.hard_bits = st.route(hard_bits ? hard_bits + done * words : nullptr, stage_sd_[0], 4 * m * words);
+        a.iters = st.route(iters ? iters + done : nullptr, stage_sd_[1], 4 * m);
+        a.weight = st.route(weight ? weight + done : nullptr, stage_sd_[2], 4 * m);
+        a.llr_out = st.route(llr_out ? llr_out + done * nc : nullptr, stage_sd_[3], 8 * m * nc);
+        a.n = m;
+        check(launch_syndrome_decode(a, dev_qms_, s), "syndrome_decode_batch");
+        st.flush(s, &pin_out_);
+    }
+}
+
 void Engine::stream_rewind_encoder(uint64_t frames_back, void *stream)
 {
     if (!code_->has_G() || frames_back == 0 || counter_) // (counter-based noise: a codeword depends on its frame index alone)

@@ -392,6 +392,21 @@ class Engine
     int64_t osd_lds_bytes() const;
     void osd_batch(uint32_t candidates, uint64_t n, const void *llr, int llr_type, uint32_t *word_out, uint32_t *flips, uint64_t *metric,
                    uint32_t *flipped_column, uint32_t *status, void *stream);
+    // quantized min-sum decoding toward a given syndrome (include/ldpc_amd.h, ldpc_hip_syndrome_decode_batch;
+    // kernels_syndrome_decode.hip) on the tables of qms_plan().  Everything the call uses is in the spec: no setting of the
+    // engine is read.  Host only: the refusal, and the LDS of one frame, -1 for a code the call does not take
+    struct SyndromeDecodeSpec
+    {
+        uint32_t iterations = 0;
+        int early_term = 0, q_bits = 0;
+        double step = 0.0, scale = 0.0, offset = 0.0;
+        int flags = 0;
+    };
+    static constexpr int kSyndromeSharedLlr = 1;
+    std::string syndrome_decode_refusal(const SyndromeDecodeSpec *spec, int llr_type, int syndrome_format);
+    int64_t syndrome_decode_lds_bytes();
+    void syndrome_decode_batch(const SyndromeDecodeSpec *spec, uint64_t n, const void *llr, int llr_type, const void *syndrome,
+                               int syndrome_format, uint32_t *hard_bits, uint32_t *iters, uint32_t *weight, double *llr_out, void *stream);
 
     // ---- fused channel + decode on the reference's noise stream ----
     // set_channel_param semantics (channel.cpp:37-42): the stream restarts at frame 0.
@@ -601,6 +616,8 @@ class Engine
     const uint16_t *era_cn_entries_ = nullptr, *era_vn_entries_ = nullptr, *era_vn_col_ = nullptr;
     DeviceBuffer era_packed_[2], stage_era_[5]; // (five outputs: the solver's)
     DeviceBuffer stage_osd_[5];                 // the outputs of osd_batch for host buffers
+    DeviceBuffer stage_sd_[4];                  // ... and of syndrome_decode_batch
+    const uint32_t *sd_cn_row_ = nullptr;       // Plan::cn_rank_row on the device, at the first syndrome_decode_batch
     uint64_t gf2_sub_batch() const; // frames per launch: staging buffers stay modest, no grid dimension overflows
     // a host input of a batch call on the device (small ones through page-locked memory); a device pointer comes back as it is
     const void *stage_input(const void *src, size_t bytes, DeviceBuffer &stage, void *stream);

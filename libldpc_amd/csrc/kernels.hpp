@@ -552,6 +552,43 @@ struct OsdArgs
 };
 int launch_osd(const OsdArgs &a, void *stream);
 
+// ---- quantized min-sum decoding toward a given syndrome (kernels_syndrome_decode.hip; include/ldpc_amd.h,
+// ldpc_hip_syndrome_decode_batch): one workgroup per frame on the tables of DevQmsPlan, the typed LLRs read in place ----
+// LDS of one frame (include/ldpc_amd.h, ldpc_hip_syndrome_decode_lds_bytes), every part rounded up to 16 bytes: the messages
+// (a byte each, `slots`), the 32-bit totals, the 128-byte table and 32 bytes of votes and partial sums, the syndrome (a bit
+// per check node, in the order the kernel walks them), the quantized inputs (a byte each)
+constexpr size_t syndrome_decode_round16(size_t x) { return (x + 15) & ~size_t(15); }
+constexpr size_t kSyndromeDecodeSideBytes = 160;
+constexpr size_t syndrome_decode_lds_bytes(size_t slots, size_t nc, size_t mc)
+{
+    return syndrome_decode_round16(slots) + syndrome_decode_round16(4 * nc) + kSyndromeDecodeSideBytes +
+           syndrome_decode_round16(4 * ((mc + 31) / 32)) + syndrome_decode_round16(nc);
+}
+struct SyndromeDecodeArgs
+{
+    uint32_t nc, mc;
+    uint32_t words, syn_words;  // ceil(nc / 32), ceil(mc / 32)
+    uint32_t iterations;
+    int32_t early_term;
+    int32_t llr_type;           // LlrType: the kernel reads the elements in place
+    int32_t syndrome_format;    // BitsFormat (not read where syndrome is null)
+    int32_t shared_llr;         // llr is one row [nc] for every frame
+    int32_t qmax;               // 2^(q_bits - 1) - 1, 1..127
+    double step, inv;           // the LLR step and fl(1 / step)
+    uint32_t lut[32];           // lut[m], m = 0..qmax, four per word (engine.cpp, correction_lut)
+    uint32_t lds_bytes;         // syndrome_decode_lds_bytes(slots, nc, mc)
+    const uint32_t *col_rank;   // [nc] column -> VN rank (DevPlan)
+    const uint32_t *cn_row;     // [mc] check node in the tables' order -> row of H in file order (Plan::cn_rank_row)
+    const void *llr;            // [n][nc] (or [nc]) elements of llr_type, column order
+    const void *syndrome;       // [n][mc] bytes or [n][syn_words] words, row order; nullptr = all zero
+    uint32_t *hard_bits;        // [n][words] or nullptr
+    uint32_t *iters;            // [n] or nullptr
+    uint32_t *weight;           // [n] or nullptr
+    double *llr_out;            // [n][nc] or nullptr
+    uint64_t n;                 // <= 2^20
+};
+int launch_syndrome_decode(const SyndromeDecodeArgs &a, const DevQmsPlan &Q, void *stream);
+
 // opt-in non-parity ternary min-sum, bit-sliced over 32 frames per workgroup (kernels_ternary.hip; include/ldpc_amd.h,
 // ldpc_hip_set_min_sum_ternary) on the general plan.  a.ms_* are not read.  With a.llr_out null the planes of A are left out
 // of the group's LDS (plan.hpp, ternary_lds_bytes)
