@@ -716,6 +716,71 @@ int ldpc_hip_osd_batch(ldpc_hip_ctx *ctx, uint32_t candidates, uint64_t n, const
    tests/golden/h.txt (mc = 1024, nc = 1152): V = 18, S = 19, 155 648 + 432 + 2 304 + 384 = 158 768 bytes: one frame per CU. */
 int64_t ldpc_hip_osd_lds_bytes(const ldpc_hip_ctx *ctx);
 
+/* Ordered-statistics decoding TOWARD A GIVEN SYNDROME, with a bounded order-2 sweep
+   (libldpc_amd/csrc/kernels_osd_syndrome.hip): ldpc_hip_osd_batch asks for M x = 0, this entry for M x = s with the s the
+   caller holds, and it adds a second stage of candidates — every pair among the first `pair_depth` trusted columns, the
+   "combination sweep" of BP + OSD.  Meant behind ldpc_hip_syndrome_decode_batch: fed with the llr_out and the syndromes of the
+   frames that message passing left at a weight > 0, it returns a word with syndrome s wherever one exists.
+   ldpc_hip_osd_batch is unchanged.  The common rules of this block hold: device or host buffers, checks before the GPU
+   naming the entry in ldpc_hip_last_error, n == 0 returns 0 after them, every output may be NULL, ordered on hip_stream, no
+   setting and no state of the stream interface read or changed, a frame's results do not depend on which frames share its
+   call, every output bit is determined.
+   In:  llr[n][nc] exactly as in ldpc_hip_osd_batch; syndrome[n][mc] and syndrome_format exactly as in
+        ldpc_hip_syndrome_decode_batch (LDPC_HIP_BITS_U8 or LDPC_HIP_BITS_PACKED32, what ldpc_hip_syndrome_batch writes, bit r
+        = check node r in file row order; NULL = all zero; the bits of a row's last word from mc on are ignored).
+   Out: word_out[n][W], flips[n], metric[n], status[n] as in ldpc_hip_osd_batch, and flipped_columns[n][2].  "none" below
+        is 0xFFFFFFFF.
+   Per frame, with W, z, q, M, pi, P, K and the metric of steps 1..4 and 6 of ldpc_hip_osd_batch:
+     a. Met.  If M z = s: status = LDPC_HIP_OSD_CODEWORD (value 0, read here as "z already meets s"), word_out = z, metric
+        0, 0 flips, both columns none.
+     b. Infeasible.  If s is not in the column space of M (a property of M and s alone, not of the pivots): status =
+        LDPC_HIP_OSD_INFEASIBLE, word_out = z, metric 0, 0 flips, both columns none.  Not an error return: on
+        tests/golden/h.txt (rank 1021 of 1024 check nodes) 7 of 8 random syndromes are infeasible; s = H x of any word x is
+        always feasible.
+     c. Order 0.  x0 = the unique x with M x = s and x = z on K.
+     d. Singles.  T = min(candidates, |K|); x_t agrees with z on K except at K[t], t < T; its candidate index is e = t.
+     e. Pairs.  L = min(pair_depth, |K|); for 0 <= t1 < t2 < L, x_{t1,t2} agrees with z on K except at K[t1] and K[t2]; its
+        candidate index is e = T + the lexicographic rank of (t1, t2) among those pairs.
+     f. Winner.  x0 unless some candidate has a strictly smaller metric; among the candidates the smallest metric wins,
+        among equal metrics the smallest e (every single before every pair).
+     g. status = LDPC_HIP_OSD_ORDER0 if x0 wins, LDPC_HIP_OSD_REPROCESSED if a single does, LDPC_HIP_OSD_REPROCESSED_PAIR if a
+        pair does; flipped_columns = (K[t], none), (K[t1], K[t2]) or (none, none); word_out, flips and metric are the
+        winner's.
+   Identities: for every frame that is not infeasible, ldpc_hip_syndrome_batch(word_out) XOR s has weight 0.  The metric is
+   non-increasing in `candidates` and in `pair_depth` (either only adds words to choose from).  With syndrome == NULL and
+   pair_depth == 0, word, flips, metric, status and flipped_columns[:][0] are those of ldpc_hip_osd_batch.  With s = M u for
+   a known word u and LLRs that hold no zero and no NaN, word_out = (the word of ldpc_hip_osd_batch on the LLRs with the sign
+   flipped wherever u is 1) XOR u, and flips, metric, column and status are the same: the sign flip changes z by u and leaves
+   q, pi, P and K alone.  None of this depends on the order of the pivots.
+   Refused (host only, -1): an unknown llr_type or syndrome_format, a NULL llr with n > 0, pair_depth > 256, and a code whose
+   frame does not fit (ldpc_hip_osd_syndrome_lds_bytes returns -1; there is no other kernel).  The limit on pair_depth bounds
+   a frame's time on a shared device: at most 32 640 pairs, each one pass of a wave over the mc reduced rows.  Measured at the
+   cap on an MI355X (profiles/osd_syndrome.jsonl): the pair stage takes 1.59 ms per frame of tests/golden/h.txt (16 waves) and
+   2.28 ms per frame of a (3,6)-regular code of 240 columns (2 waves, 7 140 pairs); reasoned from those, a code of at most 64
+   check nodes with 256 trusted columns (one wave) takes about 25 ms.
+   How it runs: the kernel of ldpc_hip_osd_batch with a right-hand side — every row carries the bit (s + M z) of its check
+   node in bit 63 of its side word through the elimination, order 0 reads it off the pivot rows, a row left without a pivot
+   whose bit is set is the infeasible case; singles as there; pairs a wave each, scored directly from the reduced rows
+   (metric(x0) + q[j1] + q[j2] + the signed reliabilities of the pivots of the rows that hold exactly one of the two
+   columns), so no second elimination; one launch per 2^20 frames at most.  ldpcsim, simulate() and the stream interface are
+   not touched. */
+enum
+{
+    LDPC_HIP_OSD_REPROCESSED_PAIR = 3,
+    LDPC_HIP_OSD_INFEASIBLE = 4
+};
+int ldpc_hip_osd_syndrome_batch(ldpc_hip_ctx *ctx, uint32_t candidates, uint32_t pair_depth, uint64_t n, const void *llr, int llr_type,
+                                const void *syndrome, int syndrome_format, uint32_t *word_out, uint32_t *flips, uint64_t *metric,
+                                uint32_t *flipped_columns /* [n][2] */, uint32_t *status, void *hip_stream);
+/* LDS bytes one frame of ldpc_hip_osd_syndrome_batch takes on this context's code (host only), -1 under the conditions of
+   ldpc_hip_osd_lds_bytes.  With V and S as there:
+     bytes = max(8 mc S, 4 nc rounded up to 8) + 24 V + (2 nc rounded up to 8) + 1536, rounded up to 16
+   — the parts of ldpc_hip_osd_lds_bytes with 1 536 bytes in place of 384: 512 of votes, sums and per wave its best
+   candidate (metric, index, two places in K), and 1 024 of the reliabilities of the first 256 columns of K, which the
+   pair stage reads instead of the input.  The right-hand side takes no room: it is a bit of the side word.
+   tests/golden/h.txt: 155 648 + 432 + 2 304 + 1 536 = 159 920 bytes: one frame per CU. */
+int64_t ldpc_hip_osd_syndrome_lds_bytes(const ldpc_hip_ctx *ctx);
+
 /* Quantized min-sum decoding of frames of LLRs TOWARD A GIVEN SYNDROME (libldpc_amd/csrc/kernels_syndrome_decode.hip): which
    word x with H x = s fits these LLRs, for the s the caller holds — every other decoder of this library asks for H x = 0.
    The decoder of syndrome-based source coding with side information (Slepian-Wolf) and of information reconciliation: one
@@ -773,7 +838,7 @@ int64_t ldpc_hip_osd_lds_bytes(const ldpc_hip_ctx *ctx);
    at the first call that needs them); a thread per column quantizes the element it reads and stores the byte at the
    column's place in the kernel's order; a thread per check node fetches its syndrome bit through the map from the kernel's
    check-node order to file rows; a byte per message in LDS; the packed decisions by a ballot per 64 columns; one launch per
-   2^20 frames at most.  OSD toward a syndrome is not offered; llr_out is there to feed it later.  ldpcsim, simulate() and
+   2^20 frames at most.  OSD toward a syndrome is ldpc_hip_osd_syndrome_batch: llr_out and s feed it.  ldpcsim, simulate() and
    the stream interface are not touched. */
 enum
 {

@@ -125,6 +125,10 @@ def load_library(path=LIB_PATH):
     L.ldpc_hip_osd_batch.argtypes = [vp, ct.c_uint32, u64, vp, i32, vp, vp, vp, vp, vp, vp]
     L.ldpc_hip_osd_lds_bytes.restype = ct.c_int64
     L.ldpc_hip_osd_lds_bytes.argtypes = [vp]
+    L.ldpc_hip_osd_syndrome_batch.restype = i32
+    L.ldpc_hip_osd_syndrome_batch.argtypes = [vp, ct.c_uint32, ct.c_uint32, u64, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.ldpc_hip_osd_syndrome_lds_bytes.restype = ct.c_int64
+    L.ldpc_hip_osd_syndrome_lds_bytes.argtypes = [vp]
     L.ldpc_hip_syndrome_decode_batch.restype = i32
     L.ldpc_hip_syndrome_decode_batch.argtypes = [vp, ct.POINTER(ldpc_hip_syndrome_decode), u64, vp, i32, vp, i32, vp, vp, vp, vp, vp]
     L.ldpc_hip_syndrome_decode_lds_bytes.restype = ct.c_int64
@@ -717,6 +721,45 @@ class HipDecoder:
     def osd_lds_bytes(self):
         """LDS bytes one frame of osd_batch takes (-1: the check matrix does not fit a CU, and osd_batch refuses the code)."""
         return int(self.lib.ldpc_hip_osd_lds_bytes(self.ctx))
+
+    OSD_REPROCESSED_PAIR, OSD_INFEASIBLE = 3, 4
+
+    def osd_syndrome_batch(self, llr, syndrome=None, candidates=0, pair_depth=0,
+                           want=("word", "flips", "metric", "flipped_columns", "status"), out=None, stream=None):
+        """Ordered-statistics decoding toward a given syndrome: llr[n][nc] as in osd_batch, syndrome[n][mc] as in
+        syndrome_decode_batch (uint8, or packed uint32 as syndrome_batch writes it; None = all zero) -> the word x with
+        H x = syndrome that keeps the hard decisions on the most reliable independent columns, the best of the first
+        `candidates` single flips among them and of every pair among the first `pair_depth` (at most 256) of them.  "word",
+        "flips", "metric" as in osd_batch; "flipped_columns" (uint32 [n][2]: the winning flip's columns, OSD_NO_COLUMN where
+        there is none) and "status" (uint32 [n]: OSD_CODEWORD = the decisions already meet the syndrome, OSD_ORDER0,
+        OSD_REPROCESSED, OSD_REPROCESSED_PAIR, or OSD_INFEASIBLE = no word has this syndrome, and "word" is the decisions);
+        include/ldpc_amd.h, ldpc_hip_osd_syndrome_batch.  Inputs and the buffers in `out` are numpy arrays or torch tensors,
+        host or device; a wrong dtype raises TypeError, a wrong shape ValueError."""
+        name = str(llr.dtype).replace("torch.", "")
+        if name not in self.LLR_TYPES:
+            raise TypeError(f"osd_syndrome_batch takes float64, float32, float16 or int8 LLRs, not {llr.dtype}")
+        if len(llr.shape) != 2 or int(llr.shape[1]) != self.nc:
+            raise ValueError(f"osd_syndrome_batch: llr is [n][{self.nc}], not {tuple(llr.shape)}")
+        n, fmt = int(llr.shape[0]), 0
+        if syndrome is not None:
+            ns, fmt = self._bits(syndrome, self.mc, "osd_syndrome_batch")
+            if ns != n:
+                raise ValueError(f"osd_syndrome_batch: {n} rows of llr against {ns} of syndrome")
+        if not 0 <= int(candidates) < 2**32 or not 0 <= int(pair_depth) < 2**32:
+            raise ValueError(f"osd_syndrome_batch: candidates={candidates}, pair_depth={pair_depth}")
+        spec = {"word": ((n, (self.nc + 31) // 32), np.uint32), "flips": ((n,), np.uint32), "metric": ((n,), np.uint64),
+                "flipped_columns": ((n, 2), np.uint32), "status": ((n,), np.uint32)}
+        bufs = self._wanted(want, out, spec)
+        self._check_bufs("osd_syndrome_batch", bufs, spec)
+        self._check(self.lib.ldpc_hip_osd_syndrome_batch(self.ctx, int(candidates), int(pair_depth), n, _ptr(llr), self.LLR_TYPES[name],
+                                                         _ptr(syndrome), fmt, _ptr(bufs.get("word")), _ptr(bufs.get("flips")),
+                                                         _ptr(bufs.get("metric")), _ptr(bufs.get("flipped_columns")),
+                                                         _ptr(bufs.get("status")), stream), "ldpc_hip_osd_syndrome_batch")
+        return bufs
+
+    def osd_syndrome_lds_bytes(self):
+        """LDS bytes one frame of osd_syndrome_batch takes (-1: the check matrix does not fit a CU, and the call refuses the code)."""
+        return int(self.lib.ldpc_hip_osd_syndrome_lds_bytes(self.ctx))
 
     SYNDROME_SHARED_LLR = 1
 

@@ -514,6 +514,23 @@ int64_t ldpc_hip_osd_lds_bytes(const ldpc_hip_ctx *ctx)
     return bytes;
 }
 
+int ldpc_hip_osd_syndrome_batch(ldpc_hip_ctx *ctx, uint32_t candidates, uint32_t pair_depth, uint64_t n, const void *llr, int llr_type,
+                                const void *syndrome, int syndrome_format, uint32_t *word_out, uint32_t *flips, uint64_t *metric,
+                                uint32_t *flipped_columns, uint32_t *status, void *hip_stream)
+{
+    return guarded([&] {
+        ctx->eng->osd_syndrome_batch(candidates, pair_depth, n, llr, llr_type, syndrome, syndrome_format, word_out, flips, metric,
+                                     flipped_columns, status, hip_stream);
+    });
+}
+
+int64_t ldpc_hip_osd_syndrome_lds_bytes(const ldpc_hip_ctx *ctx)
+{
+    int64_t bytes = -1;
+    guarded([&] { bytes = ctx->eng->osd_syndrome_lds_bytes(); });
+    return bytes;
+}
+
 int ldpc_hip_syndrome_decode_batch(ldpc_hip_ctx *ctx, const ldpc_hip_syndrome_decode *p, uint64_t n, const void *llr, int llr_type,
                                    const void *syndrome, int syndrome_format, uint32_t *hard_bits, uint32_t *iters, uint32_t *weight,
                                    double *llr_out, void *hip_stream)

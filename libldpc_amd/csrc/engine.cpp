@@ -2104,6 +2104,73 @@ void Engine::osd_batch(uint32_t candidates, uint64_t n, const void *llr, int llr
 }
 
 // ---------------------------------------------------------------------------------------------
+// Ordered-statistics decoding toward a given syndrome, singles and a bounded pair sweep (kernels_osd_syndrome.hip)
+int64_t Engine::osd_syndrome_lds_bytes() const
+{
+    const size_t nc = static_cast<size_t>(plan_.nc), mc = static_cast<size_t>(plan_.mc);
+    if (nc > 0xFFFFu || mc > static_cast<size_t>(kOsdRowsPerThread) * kOsdMaxThreads) // (the order is 16 bits a column)
+        return -1;
+    const size_t bytes = ldpc_amd::osd_syndrome_lds_bytes(nc, mc);
+    return bytes <= kCuLdsBytes ? static_cast<int64_t>(bytes) : -1;
+}
+
+std::string Engine::osd_syndrome_refusal(uint32_t pair_depth, int llr_type, int syndrome_format) const
+{
+    const std::string who = "ldpc_hip_osd_syndrome_batch: ";
+    if (llr_type_bytes(llr_type) == 0)
+        return who + "unknown LLR type " + std::to_string(llr_type) + " (0 = binary64, 1 = binary32, 2 = binary16, 3 = int8)";
+    if (std::string why = bits_format_refusal("ldpc_hip_osd_syndrome_batch", "syndrome", syndrome_format); !why.empty())
+        return why;
+    if (pair_depth > kOsdMaxPairDepth)
+        return who + "pair_depth " + std::to_string(pair_depth) + " is beyond " + std::to_string(kOsdMaxPairDepth) +
+               " (32 640 pairs a frame)";
+    if (osd_syndrome_lds_bytes() < 0)
+        return who + "the check matrix of " + std::to_string(plan_.mc) + " x " + std::to_string(plan_.nc) +
+               " bits does not fit the 160 KB of LDS of a CU (ldpc_hip_osd_syndrome_lds_bytes; there is no other kernel)";
+    return "";
+}
+
+void Engine::osd_syndrome_batch(uint32_t candidates, uint32_t pair_depth, uint64_t n, const void *llr, int llr_type, const void *syndrome,
+                                int syndrome_format, uint32_t *word_out, uint32_t *flips, uint64_t *metric, uint32_t *flipped_columns,
+                                uint32_t *status, void *stream)
+{
+    if (const std::string why = osd_syndrome_refusal(pair_depth, llr_type, syndrome_format); !why.empty())
+        throw std::runtime_error(why);
+    if (n && !llr)
+        throw std::runtime_error("ldpc_hip_osd_syndrome_batch: null llr");
+    if (n == 0 || (!word_out && !flips && !metric && !flipped_columns && !status))
+        return;
+    bind_device();
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    upload_rows_of_h();
+    const uint64_t nc = static_cast<uint64_t>(plan_.nc), mc = static_cast<uint64_t>(plan_.mc), words = (nc + 31) / 32;
+    OsdSyndromeArgs a{};
+    a.nc = static_cast<uint32_t>(nc), a.mc = static_cast<uint32_t>(mc), a.words = static_cast<uint32_t>(words);
+    a.syn_words = static_cast<uint32_t>((mc + 31) / 32);
+    a.candidates = candidates, a.pair_depth = pair_depth, a.llr_type = llr_type, a.syndrome_format = syndrome_format;
+    a.threads = std::clamp<uint32_t>((a.mc + 63u) / 64u * 64u, 64u, kOsdMaxThreads); // a thread per row where they reach
+    a.lds_bytes = static_cast<uint32_t>(osd_syndrome_lds_bytes());
+    a.row_ptr = gf2_row_ptr_, a.row_col = gf2_row_col_;
+    const uint64_t sub = std::max<uint64_t>(gf2_sub_batch() / llr_type_bytes(llr_type), 1); // (elements of up to 8 bytes, not bits)
+    const size_t in_row = llr_type_bytes(llr_type) * nc, syn_row = bits_row_bytes(syndrome_format, mc);
+    for (uint64_t done = 0; done < n; done += sub)
+    {
+        const uint64_t m = std::min(sub, n - done);
+        a.llr = stage_input(static_cast<const char *>(llr) + in_row * done, in_row * m, llr_type == kLlrF64 ? stage_in_ : stage_typed_, stream);
+        a.syndrome = syndrome ? stage_input(static_cast<const char *>(syndrome) + syn_row * done, syn_row * m, stage_in_b_, stream) : nullptr;
+        OutStage st;
+        a.word_out = st.route(word_out ? word_out + done * words : nullptr, stage_osd_[0], 4 * m * words);
+        a.flips = st.route(flips ? flips + done : nullptr, stage_osd_[1], 4 * m);
+        a.metric = st.route(metric ? metric + done : nullptr, stage_osd_[2], 8 * m);
+        a.flipped_columns = st.route(flipped_columns ? flipped_columns + 2 * done : nullptr, stage_osd_[3], 8 * m);
+        a.status = st.route(status ? status + done : nullptr, stage_osd_[4], 4 * m);
+        a.n = m;
+        check(launch_osd_syndrome(a, s), "osd_syndrome_batch");
+        st.flush(s, &pin_out_);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Quantized min-sum decoding toward a given syndrome (kernels_syndrome_decode.hip)
 int64_t Engine::syndrome_decode_lds_bytes()
 {

@@ -392,6 +392,13 @@ class Engine
     int64_t osd_lds_bytes() const;
     void osd_batch(uint32_t candidates, uint64_t n, const void *llr, int llr_type, uint32_t *word_out, uint32_t *flips, uint64_t *metric,
                    uint32_t *flipped_column, uint32_t *status, void *stream);
+    // ... toward a given syndrome, with every pair among the first `pair_depth` trusted columns as a second stage
+    // (include/ldpc_amd.h, ldpc_hip_osd_syndrome_batch; kernels_osd_syndrome.hip).  Host only: the refusal and the LDS
+    std::string osd_syndrome_refusal(uint32_t pair_depth, int llr_type, int syndrome_format) const;
+    int64_t osd_syndrome_lds_bytes() const;
+    void osd_syndrome_batch(uint32_t candidates, uint32_t pair_depth, uint64_t n, const void *llr, int llr_type, const void *syndrome,
+                            int syndrome_format, uint32_t *word_out, uint32_t *flips, uint64_t *metric, uint32_t *flipped_columns,
+                            uint32_t *status, void *stream);
     // quantized min-sum decoding toward a given syndrome (include/ldpc_amd.h, ldpc_hip_syndrome_decode_batch;
     // kernels_syndrome_decode.hip) on the tables of qms_plan().  Everything the call uses is in the spec: no setting of the
     // engine is read.  Host only: the refusal, and the LDS of one frame, -1 for a code the call does not take

@@ -552,6 +552,41 @@ struct OsdArgs
 };
 int launch_osd(const OsdArgs &a, void *stream);
 
+// ---- ordered-statistics decoding toward a given syndrome, with a bounded order-2 sweep (kernels_osd_syndrome.hip;
+// include/ldpc_amd.h, ldpc_hip_osd_syndrome_batch): the layout of osd_kernel, and bit 63 of a row's side word is the row's
+// right-hand side (s + M z, eliminated along with the row) ----
+constexpr uint32_t kOsdReprocessedPair = 3, kOsdInfeasible = 4, kOsdMaxPairDepth = 256;
+// beside the order: 8 bytes of metric(x0), per wave (16 of them) its best metric (8 bytes) and that candidate's index and its
+// two places in K (4 bytes each), 16 32-bit scalars = 392 bytes, rounded to 512; then the reliabilities of the first
+// kOsdMaxPairDepth columns of K (4 bytes each)
+constexpr uint32_t kOsdSyndromeSideBytes = 512 + 4 * kOsdMaxPairDepth;
+constexpr size_t osd_syndrome_lds_bytes(size_t nc, size_t mc)
+{
+    return (osd_matrix_bytes(nc, mc) + 24 * osd_row_words(nc) + (2 * nc + 7) / 8 * 8 + kOsdSyndromeSideBytes + 15) / 16 * 16;
+}
+struct OsdSyndromeArgs
+{
+    uint32_t nc, mc, words;   // words = ceil(nc / 32); nc < 65536
+    uint32_t syn_words;       // ceil(mc / 32)
+    uint32_t candidates;      // single flips tried (the first of K in the order; more than |K| counts as |K|)
+    uint32_t pair_depth;      // <= kOsdMaxPairDepth: every pair among the first min(pair_depth, |K|) of K is tried
+    uint32_t threads;         // a multiple of 64, <= kOsdMaxThreads, mc <= kOsdRowsPerThread * threads
+    uint32_t lds_bytes;       // osd_syndrome_lds_bytes(nc, mc)
+    int32_t llr_type;         // LlrType: the kernel reads the elements in place
+    int32_t syndrome_format;  // BitsFormat of `syndrome`
+    const uint32_t *row_ptr;  // [mc + 1]: the rows of H as the library loaded it, repeated entries included
+    const uint32_t *row_col;  // columns, < nc
+    const void *llr;          // [n][nc] elements of llr_type
+    const void *syndrome;     // [n][mc] bytes or [n][syn_words] words, bit r = row r; nullptr = all zero
+    uint32_t *word_out;       // [n][words] or nullptr
+    uint32_t *flips;          // [n] or nullptr
+    uint64_t *metric;         // [n] or nullptr
+    uint32_t *flipped_columns; // [n][2] or nullptr
+    uint32_t *status;         // [n] or nullptr
+    uint64_t n;               // <= 2^20
+};
+int launch_osd_syndrome(const OsdSyndromeArgs &a, void *stream);
+
 // ---- quantized min-sum decoding toward a given syndrome (kernels_syndrome_decode.hip; include/ldpc_amd.h,
 // ldpc_hip_syndrome_decode_batch): one workgroup per frame on the tables of DevQmsPlan, the typed LLRs read in place ----
 // LDS of one frame (include/ldpc_amd.h, ldpc_hip_syndrome_decode_lds_bytes), every part rounded up to 16 bytes: the messages

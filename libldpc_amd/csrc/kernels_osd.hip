@@ -25,6 +25,7 @@
 
 #include "kernels.hpp"
 #include "launch_lds.hpp"
+#include "osd_device.hpp"
 #include "plan.hpp"
 
 namespace ldpc_amd
@@ -36,37 +37,6 @@ constexpr uint32_t kNoRow = 0xFFFFFFFFu;
 // the 32-bit scalars: [0..2] the pivot votes, then
 constexpr int kOsdOdd = 3, kOsdFlips0 = 4;
 constexpr uint64_t kOsdDiffers = 1ull << 48; // side word: q in bits 0..31, the pivot column in 32..47, x0 != z there in 48
-
-// element i of the typed input, widened exactly
-__device__ __forceinline__ double osd_widen(const OsdArgs &a, uint64_t i)
-{
-    switch (a.llr_type) // (uniform)
-    {
-    case kLlrF64: return static_cast<const double *>(a.llr)[i];
-    case kLlrF32: return static_cast<double>(static_cast<const float *>(a.llr)[i]);
-    case kLlrF16: return static_cast<double>(static_cast<const _Float16 *>(a.llr)[i]);
-    default: return static_cast<double>(static_cast<const int8_t *>(a.llr)[i]);
-    }
-}
-
-// min(floor(|w| * 4096), 2^31 - 1); a NaN gives 0.  The product is exact or infinite: a power of two
-__device__ __forceinline__ uint32_t osd_reliability(double w)
-{
-    const double s = fabs(w) * 4096.0;
-    return !(s == s) ? 0u : s >= 2147483647.0 ? kOsdQMax : static_cast<uint32_t>(s);
-}
-
-__device__ __forceinline__ int64_t osd_wave_sum(int64_t v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-    {
-        const uint32_t lo = static_cast<uint32_t>(__shfl_xor(static_cast<int>(static_cast<uint64_t>(v)), o, 64));
-        const uint32_t hi = static_cast<uint32_t>(__shfl_xor(static_cast<int>(static_cast<uint64_t>(v) >> 32), o, 64));
-        v += static_cast<int64_t>((static_cast<uint64_t>(hi) << 32) | lo);
-    }
-    return v;
-}
 
 __global__ __launch_bounds__(kOsdMaxThreads) void osd_kernel(const OsdArgs a)
 {
