@@ -866,6 +866,80 @@ int ldpc_hip_syndrome_decode_batch(ldpc_hip_ctx *ctx, const ldpc_hip_syndrome_de
    tests/golden/h.txt (nc = 1152, mc = 1024): see DESIGN.md section 4 for the figure and the frames per CU. */
 int64_t ldpc_hip_syndrome_decode_lds_bytes(const ldpc_hip_ctx *ctx);
 
+/* Fixed-point LAYERED min-sum decoding of frames of LLRs toward a given syndrome
+   (libldpc_amd/csrc/kernels_syndrome_decode_layered.hip): ldpc_hip_syndrome_decode_batch on the row-serial schedule, with
+   messages of p->msg_bits bits and saturating totals of p->app_bits bits — the schedule and datapath reconciliation and
+   hardware decoders use, about half the sweeps of flooding.  NON-PARITY.  ldpc_hip_syndrome_decode_batch and its struct are
+   unchanged; this entry stands beside it.
+   The common rules are those of ldpc_hip_syndrome_decode_batch, word for word: device or host buffers, checks before the GPU
+   naming the entry in ldpc_hip_last_error, n == 0 returns 0 after them, every output may be NULL (all NULL: nothing is
+   launched), ordered on hip_stream, a frame's results do not depend on which frames share its call, every output bit is
+   determined.  NO SETTING AND NO STATE OF THE STREAM INTERFACE IS READ OR CHANGED: everything the call uses is in *p.
+   In and Out: as there.  llr[n][nc] of llr_type (F64 / F32 / F16 / I8) read in place, one row [nc] with
+   LDPC_HIP_SYNDROME_SHARED_LLR; syndrome[n][mc] U8 or PACKED32, bit r = check node r in file row order, NULL = all zero, the
+   bits of a row's last word from mc on ignored; hard_bits[n][ceil(nc / 32)] with the bits of a row's last word from nc on 0,
+   iters[n], weight[n], llr_out[n][nc] binary64 in column order.
+   Arithmetic: items 1..7 of ldpc_hip_set_min_sum_layered_fixed with q = p->msg_bits, p = p->app_bits, D = p->step,
+   Qmax = 2^(q-1) - 1, Pmax = 2^(p-1) - 1, inv = fl(1 / D), on the layered plan of the context (build_layer_plan) and with lut
+   built from (p->scale, p->offset) by the same host routine (item 3), with the two changes and two additions of
+   ldpc_hip_syndrome_decode_batch.  All integer after the quantizer:
+     1. Quantizer.  Unchanged: L[v] = clamp(rint(fl(W[v] * inv)), -Qmax, +Qmax), W the element widened exactly to binary64; a
+        NaN gives 0, infinities saturate.  For LDPC_HIP_LLR_I8, L = clamp(k, -Qmax, +Qmax).  T[v] := L[v], every message 0.
+     2. CHANGE, check node sign: in check node c, m[c][j] is negative iff (the number of other u_k < 0) + s[c] is odd.
+        t, u, the magnitudes, the table and the saturating update of T are item 4 unchanged.
+     3. CHANGE, stop rule: with early_term the frame stops after the first sweep whose decisions satisfy
+        XOR of hard over the row == s[c] for every check node (instead of == 0).
+     4. iters = the number of sweeps completed before the sweep whose decisions met the test, otherwise `iterations`.
+     5. ADDITION, weight[f] = the number of check nodes whose test fails on the frame's final decisions, also without
+        early termination: 0 iff the returned word has syndrome s.
+     6. ADDITION, iterations == 0 returns the quantized input: T = L, hard = (L <= 0), llr_out = fl(L * D), iters = 0, and the
+        weight of that.
+     7. llr_out[v] = fl((double) T[v] * D) of the last sweep the frame ran.
+   Identities (tests/test_syndrome_decode_layered_host.py on the mirror, tests/test_gpu_syndrome_decode_layered.py on the GPU):
+     (a) with syndrome == NULL and iterations > 0, iters, the decisions and llr_out are those of ldpc_hip_decode_batch_typed
+         under ldpc_hip_set_min_sum_layered_fixed(q, p, D) and ldpc_hip_set_min_sum_correction(scale, offset);
+     (b) with any s, on a code whose check nodes all have degree <= 7 and with app_bits > msg_bits, the first nc totals and
+         decisions are those of that decoder on the code [H | I] (mc further columns, column nc + r in row r alone) fed
+         99999.9 (1 - 2 s[r]) there, without early termination, after any number of sweeps.  The augmented code's plan has
+         the same steps (every degree grows by one — hence degree <= 7 —, and an extra column conflicts with nobody); the
+         extra column's total is +-Qmax + m with |m| <= Qmax, never clamped as Pmax >= 2 Qmax + 1 — hence app_bits >
+         msg_bits —, so its t is exactly +-Qmax in every sweep: the largest magnitude, which moves no minimum, and a sign that
+         is s[r].
+   Refused (host only, -1): a null p; msg_bits outside 2..8; app_bits outside msg_bits..16; a step that is NaN, <= 0 or
+   outside [2^-20, 2^20]; a scale outside (0, 1], an offset outside [0, 1e6], a NaN in either; early_term other than 0 / 1;
+   an unknown flag bit, llr_type or syndrome_format; a NULL llr with n > 0; a code the call does not take.
+   Which codes it takes: those of the layered plan — every check node of degree 2..8, at most 65 535 columns, no isolated
+   column — whose frame (below) fits 160 KB of LDS; otherwise ldpc_hip_syndrome_decode_layered_lds_bytes returns -1 and there
+   is no other kernel.
+   How it runs: one wave and one frame per workgroup on the tables of the layered plan, with one further table, (step, lane)
+   -> file row of that check node, built from the host plan and uploaded at the first call; the prologue quantizes the elements
+   it reads in place to the totals, no binary64 value is staged; the syndrome bit of a check node is bit 31 of its 32-bit
+   record (bits 0..24 hold its two magnitudes, argmin and signs), set when the records are initialised and kept by every
+   rewrite; the packed decisions by a ballot per 64 columns, the weight by one parity pass, a popcount of ballots; one launch
+   per 2^20 frames at most.  OSD toward a syndrome is ldpc_hip_osd_syndrome_batch: llr_out and s feed it. */
+typedef struct
+{
+    uint32_t iterations;
+    int early_term; /* 0 / 1 */
+    int msg_bits;   /* 2..8 */
+    int app_bits;   /* msg_bits..16 */
+    double step;    /* 2^-20 .. 2^20 */
+    double scale;   /* (0, 1] */
+    double offset;  /* [0, 1e6] */
+    int flags;      /* LDPC_HIP_SYNDROME_SHARED_LLR or 0 */
+} ldpc_hip_syndrome_decode_layered;
+int ldpc_hip_syndrome_decode_layered_batch(ldpc_hip_ctx *ctx, const ldpc_hip_syndrome_decode_layered *p, uint64_t n, const void *llr,
+                                           int llr_type, const void *syndrome, int syndrome_format, uint32_t *hard_bits,
+                                           uint32_t *iters, uint32_t *weight, double *llr_out, void *hip_stream);
+/* LDS bytes one frame of ldpc_hip_syndrome_decode_layered_batch takes on this context's code (host only), -1 for a code the
+   call does not take.  With R as for ldpc_hip_layered_fixed_lds_bytes (each step's check nodes rounded up to an even number,
+   summed):
+     bytes = round4(2 nc) + 4 R + 128, rounded up to 16
+   — the int16 totals, from the next multiple of 4 one 32-bit record per slot, behind them the 128-byte correction table:
+   exactly ldpc_hip_layered_fixed_direct_lds_bytes, the syndrome costs no byte.  tests/golden/h.txt: 6 528 bytes, 25 frames
+   per CU. */
+int64_t ldpc_hip_syndrome_decode_layered_lds_bytes(const ldpc_hip_ctx *ctx);
+
 /* channel point x of stream mt19937_64(seed): set_channel_param semantics, frame position := 0 */
 int ldpc_hip_stream_begin(ldpc_hip_ctx *ctx, int channel, uint64_t seed, double x);
 /* advance the stream by n frames without decoding them */

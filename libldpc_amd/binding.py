@@ -46,6 +46,11 @@ class ldpc_hip_syndrome_decode(ct.Structure):
                 ("scale", ct.c_double), ("offset", ct.c_double), ("flags", ct.c_int)]
 
 
+class ldpc_hip_syndrome_decode_layered(ct.Structure):
+    _fields_ = [("iterations", ct.c_uint32), ("early_term", ct.c_int), ("msg_bits", ct.c_int), ("app_bits", ct.c_int),
+                ("step", ct.c_double), ("scale", ct.c_double), ("offset", ct.c_double), ("flags", ct.c_int)]
+
+
 _lib = None
 
 
@@ -133,6 +138,11 @@ def load_library(path=LIB_PATH):
     L.ldpc_hip_syndrome_decode_batch.argtypes = [vp, ct.POINTER(ldpc_hip_syndrome_decode), u64, vp, i32, vp, i32, vp, vp, vp, vp, vp]
     L.ldpc_hip_syndrome_decode_lds_bytes.restype = ct.c_int64
     L.ldpc_hip_syndrome_decode_lds_bytes.argtypes = [vp]
+    L.ldpc_hip_syndrome_decode_layered_batch.restype = i32
+    L.ldpc_hip_syndrome_decode_layered_batch.argtypes = [vp, ct.POINTER(ldpc_hip_syndrome_decode_layered), u64, vp, i32, vp, i32, vp, vp, vp,
+                                                         vp, vp]
+    L.ldpc_hip_syndrome_decode_layered_lds_bytes.restype = ct.c_int64
+    L.ldpc_hip_syndrome_decode_layered_lds_bytes.argtypes = [vp]
     L.ldpc_hip_stream_begin.restype = i32
     L.ldpc_hip_stream_begin.argtypes = [vp, i32, u64, ct.c_double]
     L.ldpc_hip_stream_skip.restype = i32
@@ -774,40 +784,69 @@ class HipDecoder:
         the returned word leaves unmet: 0 iff it has the syndrome) and "llr_out" (float64 [n][nc]); iterations=0 returns the
         quantized input.  include/ldpc_amd.h, ldpc_hip_syndrome_decode_batch.  Inputs and the buffers in `out` are numpy
         arrays or torch tensors, host or device; a wrong dtype raises TypeError, a wrong shape ValueError."""
-        name = str(llr.dtype).replace("torch.", "")
-        if name not in self.LLR_TYPES:
-            raise TypeError(f"syndrome_decode_batch takes float64, float32, float16 or int8 LLRs, not {llr.dtype}")
-        fmt = 0
-        if syndrome is not None:
-            ns, fmt = self._bits(syndrome, self.mc, "syndrome_decode_batch")
-        if shared_llr:
-            if tuple(llr.shape) not in ((self.nc,), (1, self.nc)):
-                raise ValueError(f"syndrome_decode_batch: a shared llr is [{self.nc}] or [1][{self.nc}], not {tuple(llr.shape)}")
-            if syndrome is None:
-                raise ValueError("syndrome_decode_batch: shared_llr needs a syndrome (its rows count the frames)")
-            n = ns
-        else:
-            if len(llr.shape) != 2 or int(llr.shape[1]) != self.nc:
-                raise ValueError(f"syndrome_decode_batch: llr is [n][{self.nc}], not {tuple(llr.shape)}")
-            n = int(llr.shape[0])
-            if syndrome is not None and ns != n:
-                raise ValueError(f"syndrome_decode_batch: {n} rows of llr against {ns} of syndrome")
-        if not 0 <= int(iterations) < 2**32:
-            raise ValueError(f"syndrome_decode_batch: iterations={iterations}")
-        spec = {"hard_bits": ((n, (self.nc + 31) // 32), np.uint32), "iters": ((n,), np.uint32), "weight": ((n,), np.uint32),
-                "llr_out": ((n, self.nc), np.float64)}
-        bufs = self._wanted(want, out, spec)
-        self._check_bufs("syndrome_decode_batch", bufs, spec)
+        who = "syndrome_decode_batch"
+        kind, n, fmt, bufs = self._syndrome_decode_call(who, llr, syndrome, shared_llr, iterations, want, out)
         p = ldpc_hip_syndrome_decode(int(iterations), int(bool(early_term)), int(q_bits), float(step), float(scale), float(offset),
                                      self.SYNDROME_SHARED_LLR if shared_llr else 0)
-        self._check(self.lib.ldpc_hip_syndrome_decode_batch(self.ctx, ct.byref(p), n, _ptr(llr), self.LLR_TYPES[name], _ptr(syndrome), fmt,
+        self._check(self.lib.ldpc_hip_syndrome_decode_batch(self.ctx, ct.byref(p), n, _ptr(llr), kind, _ptr(syndrome), fmt,
                                                             _ptr(bufs.get("hard_bits")), _ptr(bufs.get("iters")), _ptr(bufs.get("weight")),
                                                             _ptr(bufs.get("llr_out")), stream), "ldpc_hip_syndrome_decode_batch")
         return bufs
 
+    def _syndrome_decode_call(self, who, llr, syndrome, shared_llr, iterations, want, out):
+        """What the two decoders toward a syndrome check of their arguments before the library sees them -> the LLR type, the
+        frames, the syndrome's format and the output buffers."""
+        name = str(llr.dtype).replace("torch.", "")
+        if name not in self.LLR_TYPES:
+            raise TypeError(f"{who} takes float64, float32, float16 or int8 LLRs, not {llr.dtype}")
+        fmt = 0
+        if syndrome is not None:
+            ns, fmt = self._bits(syndrome, self.mc, who)
+        if shared_llr:
+            if tuple(llr.shape) not in ((self.nc,), (1, self.nc)):
+                raise ValueError(f"{who}: a shared llr is [{self.nc}] or [1][{self.nc}], not {tuple(llr.shape)}")
+            if syndrome is None:
+                raise ValueError(f"{who}: shared_llr needs a syndrome (its rows count the frames)")
+            n = ns
+        else:
+            if len(llr.shape) != 2 or int(llr.shape[1]) != self.nc:
+                raise ValueError(f"{who}: llr is [n][{self.nc}], not {tuple(llr.shape)}")
+            n = int(llr.shape[0])
+            if syndrome is not None and ns != n:
+                raise ValueError(f"{who}: {n} rows of llr against {ns} of syndrome")
+        if not 0 <= int(iterations) < 2**32:
+            raise ValueError(f"{who}: iterations={iterations}")
+        spec = {"hard_bits": ((n, (self.nc + 31) // 32), np.uint32), "iters": ((n,), np.uint32), "weight": ((n,), np.uint32),
+                "llr_out": ((n, self.nc), np.float64)}
+        bufs = self._wanted(want, out, spec)
+        self._check_bufs(who, bufs, spec)
+        return self.LLR_TYPES[name], n, fmt, bufs
+
     def syndrome_decode_lds_bytes(self):
         """LDS bytes one frame of syndrome_decode_batch takes (-1: the call does not take the code)."""
         return int(self.lib.ldpc_hip_syndrome_decode_lds_bytes(self.ctx))
+
+    def syndrome_decode_layered_batch(self, llr, syndrome=None, iterations=50, early_term=True, msg_bits=6, app_bits=8, step=0.25,
+                                      scale=1.0, offset=0.0, shared_llr=False, want=("hard_bits", "iters", "weight"), out=None,
+                                      stream=None):
+        """syndrome_decode_batch on the layered (row-serial) schedule in fixed point: messages of msg_bits bits (2..8), saturating
+        totals of app_bits bits (msg_bits..16), LLR step `step` and the correction (scale, offset); about half the sweeps of the
+        flooding call, and "iters" counts sweeps.  Arguments, outputs and buffers as there; nothing is read from the context's
+        settings; iterations=0 returns the quantized input.  Takes the codes of the layered schedule (check nodes of degree
+        2..8).  include/ldpc_amd.h, ldpc_hip_syndrome_decode_layered_batch."""
+        who = "syndrome_decode_layered_batch"
+        kind, n, fmt, bufs = self._syndrome_decode_call(who, llr, syndrome, shared_llr, iterations, want, out)
+        p = ldpc_hip_syndrome_decode_layered(int(iterations), int(bool(early_term)), int(msg_bits), int(app_bits), float(step), float(scale),
+                                             float(offset), self.SYNDROME_SHARED_LLR if shared_llr else 0)
+        self._check(self.lib.ldpc_hip_syndrome_decode_layered_batch(self.ctx, ct.byref(p), n, _ptr(llr), kind, _ptr(syndrome), fmt,
+                                                                    _ptr(bufs.get("hard_bits")), _ptr(bufs.get("iters")),
+                                                                    _ptr(bufs.get("weight")), _ptr(bufs.get("llr_out")), stream),
+                    "ldpc_hip_syndrome_decode_layered_batch")
+        return bufs
+
+    def syndrome_decode_layered_lds_bytes(self):
+        """LDS bytes one frame of syndrome_decode_layered_batch takes (-1: the call does not take the code)."""
+        return int(self.lib.ldpc_hip_syndrome_decode_layered_lds_bytes(self.ctx))
 
     def stream_begin(self, channel, seed, x):
         """Channel point x of mt19937_64(seed); also resets the encoder (a fresh channel object)."""

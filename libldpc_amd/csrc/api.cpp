@@ -554,6 +554,29 @@ int64_t ldpc_hip_syndrome_decode_lds_bytes(const ldpc_hip_ctx *ctx)
     return bytes;
 }
 
+int ldpc_hip_syndrome_decode_layered_batch(ldpc_hip_ctx *ctx, const ldpc_hip_syndrome_decode_layered *p, uint64_t n, const void *llr,
+                                           int llr_type, const void *syndrome, int syndrome_format, uint32_t *hard_bits, uint32_t *iters,
+                                           uint32_t *weight, double *llr_out, void *hip_stream)
+{
+    return guarded([&] {
+        Engine::SyndromeDecodeLayeredSpec spec;
+        if (p)
+        {
+            spec.iterations = p->iterations, spec.early_term = p->early_term, spec.msg_bits = p->msg_bits, spec.app_bits = p->app_bits;
+            spec.step = p->step, spec.scale = p->scale, spec.offset = p->offset, spec.flags = p->flags;
+        }
+        ctx->eng->syndrome_decode_layered_batch(p ? &spec : nullptr, n, llr, llr_type, syndrome, syndrome_format, hard_bits, iters, weight,
+                                                llr_out, hip_stream);
+    });
+}
+
+int64_t ldpc_hip_syndrome_decode_layered_lds_bytes(const ldpc_hip_ctx *ctx)
+{
+    int64_t bytes = -1; // (the plan builder allocates; -1 for every code the layered plan refuses)
+    guarded([&] { bytes = ctx->eng->syndrome_decode_layered_lds_bytes(); });
+    return bytes;
+}
+
 int64_t ldpc_hip_layered_fixed_direct_lds_bytes(const ldpc_hip_ctx *ctx)
 {
     int64_t bytes = -1; // (the plan builder allocates; -1 for every code the layered plan refuses)

@@ -2259,6 +2259,103 @@ void Engine::syndrome_decode_batch(const SyndromeDecodeSpec *spec, uint64_t n, c
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Fixed-point layered min-sum decoding toward a given syndrome (kernels_syndrome_decode_layered.hip)
+int64_t Engine::syndrome_decode_layered_lds_bytes()
+{
+    const int64_t bytes = plan_.mc <= 0 ? -1 : layered_fixed_direct_lds_bytes(); // (the syndrome rides in the records: no byte more)
+    return bytes <= static_cast<int64_t>(kCuLdsBytes) ? bytes : -1;
+}
+
+std::string Engine::syndrome_decode_layered_refusal(const SyndromeDecodeLayeredSpec *spec, int llr_type, int syndrome_format)
+{
+    const char *entry = "ldpc_hip_syndrome_decode_layered_batch";
+    const std::string who = std::string(entry) + ": ";
+    if (!spec)
+        return who + "null parameters";
+    if (spec->msg_bits < 2 || spec->msg_bits > 8)
+        return who + "msg_bits " + std::to_string(spec->msg_bits) + " is outside 2..8";
+    if (spec->app_bits < spec->msg_bits || spec->app_bits > 16)
+        return who + "app_bits " + std::to_string(spec->app_bits) + " is outside msg_bits..16";
+    if (!(spec->step > 0.0) || spec->step < 0x1p-20 || spec->step > 0x1p20) // (a NaN fails the first)
+        return who + "the step must lie in [2^-20, 2^20]";
+    if (!(spec->scale > 0.0) || spec->scale > 1.0)
+        return who + "the scale must lie in (0, 1]";
+    if (!(spec->offset >= 0.0) || spec->offset > 1e6)
+        return who + "the offset must lie in [0, 1e6]";
+    if (spec->early_term != 0 && spec->early_term != 1)
+        return who + "early_term " + std::to_string(spec->early_term) + " is neither 0 nor 1";
+    if (spec->flags & ~kSyndromeSharedLlr)
+        return who + "unknown flag bits " + std::to_string(spec->flags & ~kSyndromeSharedLlr);
+    if (llr_type_bytes(llr_type) == 0)
+        return who + "unknown LLR type " + std::to_string(llr_type) + " (0 = binary64, 1 = binary32, 2 = binary16, 3 = int8)";
+    if (std::string why = bits_format_refusal(entry, "syndrome", syndrome_format); !why.empty())
+        return why;
+    if (syndrome_decode_layered_lds_bytes() < 0)
+        return who + "the code of " + std::to_string(plan_.mc) + " x " + std::to_string(plan_.nc) +
+               " is not taken: the layered schedule takes codes whose check nodes all have degree 2..8, with at most 65 535 columns and no "
+               "isolated variable node, and a frame within the 160 KB of LDS of a CU (ldpc_hip_syndrome_decode_layered_lds_bytes; there is "
+               "no other kernel)";
+    return "";
+}
+
+void Engine::syndrome_decode_layered_batch(const SyndromeDecodeLayeredSpec *spec, uint64_t n, const void *llr, int llr_type,
+                                           const void *syndrome, int syndrome_format, uint32_t *hard_bits, uint32_t *iters, uint32_t *weight,
+                                           double *llr_out, void *stream)
+{
+    if (const std::string why = syndrome_decode_layered_refusal(spec, llr_type, syndrome_format); !why.empty())
+        throw std::runtime_error(why);
+    if (n && !llr)
+        throw std::runtime_error("ldpc_hip_syndrome_decode_layered_batch: null llr");
+    if (n == 0 || (!hard_bits && !iters && !weight && !llr_out))
+        return;
+    upload_plan();
+    upload_layer_plan();
+    if (!sdl_step_row_) // lane l of step s holds the l-th of the step's check nodes in file order (plan.cpp, build_layer_plan)
+    {
+        const LayerPlan &L = layer_plan();
+        std::vector<uint32_t> step_row(L.steps.size() * kWaveSize, 0), filled(L.steps.size(), 0);
+        for (size_t row = 0; row < L.step_of_row.size(); ++row)
+        {
+            const size_t si = static_cast<size_t>(L.step_of_row[row]);
+            step_row[si * kWaveSize + filled[si]++] = static_cast<uint32_t>(row);
+        }
+        sdl_step_row_ = static_cast<const uint32_t *>(upload_table(step_row.data(), step_row.size() * 4, "check nodes of the steps"));
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint64_t nc = static_cast<uint64_t>(plan_.nc), mc = static_cast<uint64_t>(plan_.mc), words = (nc + 31) / 32;
+    const bool shared = (spec->flags & kSyndromeSharedLlr) != 0;
+    SyndromeDecodeLayeredArgs a{};
+    a.nc = static_cast<uint32_t>(nc), a.mc = static_cast<uint32_t>(mc), a.words = static_cast<uint32_t>(words);
+    a.syn_words = static_cast<uint32_t>((mc + 31) / 32);
+    a.iterations = spec->iterations, a.early_term = spec->early_term;
+    a.llr_type = llr_type, a.syndrome_format = syndrome_format, a.shared_llr = shared ? 1 : 0;
+    a.q = quantizer_args<LayeredFixedArgs>(spec->step, spec->msg_bits, spec->scale, spec->offset); // (the same host routine)
+    a.q.pmax = (1 << (spec->app_bits - 1)) - 1;
+    a.lds_bytes = static_cast<uint32_t>(syndrome_decode_layered_lds_bytes());
+    a.col_rank = dev_.col_rank, a.step_row = sdl_step_row_;
+    const size_t elem = llr_type_bytes(llr_type), in_row = elem * nc, syn_row = bits_row_bytes(syndrome_format, mc);
+    DeviceBuffer &llr_stage = llr_type == kLlrF64 ? stage_in_ : stage_typed_;
+    if (shared) // one row for every frame: staged once
+        a.llr = stage_input(llr, in_row, llr_stage, stream);
+    const uint64_t sub = std::max<uint64_t>(gf2_sub_batch() / elem, 1); // (elements of up to 8 bytes, not bits)
+    for (uint64_t done = 0; done < n; done += sub)
+    {
+        const uint64_t m = std::min(sub, n - done);
+        if (!shared)
+            a.llr = stage_input(static_cast<const char *>(llr) + in_row * done, in_row * m, llr_stage, stream);
+        a.syndrome = syndrome ? stage_input(static_cast<const char *>(syndrome) + syn_row * done, syn_row * m, stage_in_b_, stream) : nullptr;
+        OutStage st;
+        a.hard_bits = st.route(hard_bits ? hard_bits + done * words : nullptr, stage_sd_[0], 4 * m * words);
+        a.iters = st.route(iters ? iters + done : nullptr, stage_sd_[1], 4 * m);
+        a.weight = st.route(weight ? weight + done : nullptr, stage_sd_[2], 4 * m);
+        a.llr_out = st.route(llr_out ? llr_out + done * nc : nullptr, stage_sd_[3], 8 * m * nc);
+        a.n = m;
+        check(launch_syndrome_decode_layered(a, dev_layer_, s), "syndrome_decode_layered_batch");
+        st.flush(s, &pin_out_);
+    }
+}
+
 void Engine::stream_rewind_encoder(uint64_t frames_back, void *stream)
 {
     if (!code_->has_G() || frames_back == 0 || counter_) // (counter-based noise: a codeword depends on its frame index alone)

@@ -414,6 +414,20 @@ class Engine
     int64_t syndrome_decode_lds_bytes();
     void syndrome_decode_batch(const SyndromeDecodeSpec *spec, uint64_t n, const void *llr, int llr_type, const void *syndrome,
                                int syndrome_format, uint32_t *hard_bits, uint32_t *iters, uint32_t *weight, double *llr_out, void *stream);
+    // ... on the layered schedule in fixed point (include/ldpc_amd.h, ldpc_hip_syndrome_decode_layered_batch;
+    // kernels_syndrome_decode_layered.hip) on the tables of layer_plan().  As above: everything is in the spec
+    struct SyndromeDecodeLayeredSpec
+    {
+        uint32_t iterations = 0;
+        int early_term = 0, msg_bits = 0, app_bits = 0;
+        double step = 0.0, scale = 0.0, offset = 0.0;
+        int flags = 0;
+    };
+    std::string syndrome_decode_layered_refusal(const SyndromeDecodeLayeredSpec *spec, int llr_type, int syndrome_format);
+    int64_t syndrome_decode_layered_lds_bytes();
+    void syndrome_decode_layered_batch(const SyndromeDecodeLayeredSpec *spec, uint64_t n, const void *llr, int llr_type, const void *syndrome,
+                                       int syndrome_format, uint32_t *hard_bits, uint32_t *iters, uint32_t *weight, double *llr_out,
+                                       void *stream);
 
     // ---- fused channel + decode on the reference's noise stream ----
     // set_channel_param semantics (channel.cpp:37-42): the stream restarts at frame 0.
@@ -625,6 +639,7 @@ class Engine
     DeviceBuffer stage_osd_[5];                 // the outputs of osd_batch for host buffers
     DeviceBuffer stage_sd_[4];                  // ... and of syndrome_decode_batch
     const uint32_t *sd_cn_row_ = nullptr;       // Plan::cn_rank_row on the device, at the first syndrome_decode_batch
+    const uint32_t *sdl_step_row_ = nullptr;    // (step, lane) -> file row, at the first syndrome_decode_layered_batch
     uint64_t gf2_sub_batch() const; // frames per launch: staging buffers stay modest, no grid dimension overflows
     // a host input of a batch call on the device (small ones through page-locked memory); a device pointer comes back as it is
     const void *stage_input(const void *src, size_t bytes, DeviceBuffer &stage, void *stream);

@@ -624,6 +624,33 @@ struct SyndromeDecodeArgs
 };
 int launch_syndrome_decode(const SyndromeDecodeArgs &a, const DevQmsPlan &Q, void *stream);
 
+// ---- fixed-point layered min-sum decoding toward a given syndrome (kernels_syndrome_decode_layered.hip; include/ldpc_amd.h,
+// ldpc_hip_syndrome_decode_layered_batch): one wave per frame on the tables of DevLayerPlan, the typed LLRs read in place.
+// LDS of one frame: plan.hpp, layered_fixed_direct_region_bytes — the syndrome bit of a check node is bit 31 of its record ----
+constexpr uint32_t kSdlSyndromeBit = 0x80000000u;
+struct SyndromeDecodeLayeredArgs
+{
+    uint32_t nc, mc;
+    uint32_t words, syn_words;  // ceil(nc / 32), ceil(mc / 32)
+    uint32_t iterations;
+    int32_t early_term;
+    int32_t llr_type;           // LlrType: the kernel reads the elements in place
+    int32_t syndrome_format;    // BitsFormat (not read where syndrome is null)
+    int32_t shared_llr;         // llr is one row [nc] for every frame
+    uint32_t lds_bytes;         // layered_fixed_direct_region_bytes(record slots, nc)
+    LayeredFixedArgs q;         // the quantizer, the two limits, the correction table
+    const uint32_t *col_rank;   // [nc] column -> VN rank (DevPlan)
+    const uint32_t *step_row;   // [n_steps][64]: the row of H in file order of the step's lane-th check node (lanes >= count: 0)
+    const void *llr;            // [n][nc] (or [nc]) elements of llr_type, column order
+    const void *syndrome;       // [n][mc] bytes or [n][syn_words] words, row order; nullptr = all zero
+    uint32_t *hard_bits;        // [n][words] or nullptr
+    uint32_t *iters;            // [n] or nullptr
+    uint32_t *weight;           // [n] or nullptr
+    double *llr_out;            // [n][nc] or nullptr
+    uint64_t n;                 // <= 2^20
+};
+int launch_syndrome_decode_layered(const SyndromeDecodeLayeredArgs &a, const DevLayerPlan &L, void *stream);
+
 // opt-in non-parity ternary min-sum, bit-sliced over 32 frames per workgroup (kernels_ternary.hip; include/ldpc_amd.h,
 // ldpc_hip_set_min_sum_ternary) on the general plan.  a.ms_* are not read.  With a.llr_out null the planes of A are left out
 // of the group's LDS (plan.hpp, ternary_lds_bytes)
