@@ -940,6 +940,84 @@ int ldpc_hip_syndrome_decode_layered_batch(ldpc_hip_ctx *ctx, const ldpc_hip_syn
    per CU. */
 int64_t ldpc_hip_syndrome_decode_layered_lds_bytes(const ldpc_hip_ctx *ctx);
 
+/* GRADIENT-DESCENT BIT FLIPPING of frames toward a given syndrome (libldpc_amd/csrc/kernels_bit_flip.hip): the
+   hard-decision, low-complexity family beside the message-passing decoders — GDBF (Wadayama, Nakamura, Yagita, Funahashi,
+   Usami, Takumi, "Gradient descent bit flipping algorithms for decoding LDPC codes", IEEE Trans. Commun. 2010) with soft
+   reliabilities and multi-bit flipping, and its probabilistic variant PGDBF (Rasheed, Ivanis, Vasic, "Fault-tolerant
+   probabilistic gradient-descent bit flipping decoder", IEEE Commun. Lett. 2014) on the counter generator of
+   ldpc_hip_set_noise.  A frame's whole state is a byte and a bit per column and a bit per check node.  NON-PARITY (the
+   reference has no such decoder).
+   The common rules are those of ldpc_hip_syndrome_decode_batch, word for word: device or host buffers, checks before the GPU
+   naming the entry in ldpc_hip_last_error, n == 0 returns 0 after them, every output may be NULL (all NULL: nothing is
+   launched), ordered on hip_stream, one launch per 2^20 frames at most, a frame's results do not depend on which frames
+   share its call or its workgroup, every output bit is determined.  NO SETTING AND NO STATE OF THE STREAM INTERFACE IS READ OR
+   CHANGED: everything the call uses is in *p (the noise mode of ldpc_hip_set_noise included: the draws below are this
+   call's own).
+   In:  llr[n][nc] of llr_type (F64 / F32 / F16 / I8), column order, read in place; one row [nc] with
+        LDPC_HIP_SYNDROME_SHARED_LLR in p->flags.  A caller with hard decisions only passes I8 values +-1 with q_bits = 2.
+        syndrome[n][mc] U8 or PACKED32, bit r = check node r in file row order (what ldpc_hip_syndrome_batch writes), NULL =
+        all zero, the bits of a row's last word from mc on ignored.
+   Out: hard_bits[n][ceil(nc / 32)] with the bits of a row's last word from nc on 0, iters[n], weight[n].
+   Arithmetic, all integer after the quantizer, with Qmax = 2^(q_bits-1) - 1, inv = fl(1 / step), w = check_weight:
+     1. Quantizer: item 1 of ldpc_hip_syndrome_decode_batch.  L[v] = clamp(rint(fl(W[v] * inv)), -Qmax, +Qmax), W the element
+        widened exactly to binary64; a NaN gives 0, infinities saturate.  For LDPC_HIP_LLR_I8, L = clamp(k, -Qmax, +Qmax).
+        y[v] = (L[v] <= 0), r[v] = |L[v]|, x := y.
+     2. Round t = 0, 1, ...: u[c] = s[c] XOR the XOR of x over the entries of row c (an entry listed twice counts twice).  If
+        every u[c] is 0 the frame is finished with iters = t: a word that meets s is never flipped.  If t == iterations the
+        frame is finished with iters = iterations.
+     3. The penalty of every one of the nc columns: P[v] = w U[v] + (x[v] != y[v] ? +r[v] : -r[v]), U[v] the sum of u[c] over
+        the entries (c, v) of H (an entry listed twice adds twice).  With w = 2 and r = 1 everywhere this orders the columns
+        exactly as PGDBF's energy "unsatisfied neighbours + disagreement with the channel" does.
+     4. Pmax = the largest P[v] of the frame; the candidates are the v with P[v] >= Pmax - margin.
+     5. With flip_threshold == 0xFFFFFFFF every candidate flips (GDBF; nothing is drawn).  Otherwise candidate v flips iff
+        its draw < flip_threshold, the draw being word v & 3 of Philox4x32-10 block t ceil(nc / 4) + (v >> 2) of frame
+        first_frame + f under TAG 3 and p->seed (key and counter layout: ldpc_hip_set_noise; ldpc_hip_philox returns the same
+        words).  A round in which nothing flips still counts.  The same frames come out of any split of a batch into calls,
+        once first_frame is set accordingly.
+     6. weight[f] = the number of u[c] != 0 on the final word: 0 iff the returned word has syndrome s.  A frame that meets s
+        only after its last round has iters = iterations and weight 0.
+     7. iterations == 0 returns the quantized input's decisions, iters = 0 and the weight of that.
+   Identities (tests/test_bit_flip_host.py on the mirror tests/bit_flip_ref.py, tests/test_gpu_bit_flip.py on the GPU): (a)
+   translation — on frames without a quantized zero, decoding L (1 - 2 x0) toward s XOR H x0 returns the word of (L, s) XOR
+   x0 with the same iters and weight, in both modes: the draws depend on (frame, round, column) alone; (b) prefix — a run of
+   k rounds agrees with a longer one on every frame that finished within k.
+   Refused (host only, -1): a null p; iterations above 65535; q_bits outside 2..8; a step that is NaN, <= 0 or outside
+   [2^-20, 2^20]; check_weight outside 1..255; margin above 65535; an unknown flag bit, llr_type or syndrome_format; a NULL
+   llr with n > 0; a code the call does not take.
+   Which codes it takes: every code the library loads with at most 65 535 columns and 65 535 check nodes whose frame
+   (below) fits the 160 KB of LDS — any degrees, isolated columns, entries listed twice; otherwise
+   ldpc_hip_bit_flip_lds_bytes returns -1 and there is no other kernel.
+   How it runs: one wave per frame, up to four frames to a workgroup (as many as keep the group within 40 KB), no workgroup
+   barrier; the two adjacency tables of H (row -> columns, column -> rows, u16 indices, file order) built once per context
+   and uploaded at the first call.  The prologue quantizes the elements it reads in place to a byte per column, packs x by a
+   ballot per 64 columns and forms u once, a lane per check node, with s folded in.  A round walks the columns twice, a lane
+   per column: the first walk forms P from the bits of u and reduces the maximum across the wave, the second forms P again
+   in the lanes that can hold a candidate and flips: the bit of x, and the bits of the column's check nodes in the NEXT
+   round's copy of u (LDS atomics), so u is never recomputed from x.  The stop test is a ballot over the words of u, the
+   weight a popcount of them, the packed decisions the words of x. */
+typedef struct
+{
+    uint32_t iterations;     /* 0..65535 flip rounds at most */
+    int q_bits;              /* 2..8: width of the reliabilities */
+    double step;             /* 2^-20 .. 2^20 */
+    uint32_t check_weight;   /* 1..255: w above */
+    uint32_t margin;         /* 0..65535: flip every column within `margin` of the frame's largest penalty */
+    uint32_t flip_threshold; /* 0xFFFFFFFF: every candidate flips (GDBF, no draws); else a candidate flips iff its draw < this */
+    uint64_t seed;           /* of the draws */
+    uint64_t first_frame;    /* frame f of the call draws as frame first_frame + f */
+    int flags;               /* LDPC_HIP_SYNDROME_SHARED_LLR or 0 */
+} ldpc_hip_bit_flip;
+int ldpc_hip_bit_flip_batch(ldpc_hip_ctx *ctx, const ldpc_hip_bit_flip *p, uint64_t n, const void *llr, int llr_type,
+                            const void *syndrome, int syndrome_format, uint32_t *hard_bits, uint32_t *iters, uint32_t *weight,
+                            void *hip_stream);
+/* LDS bytes one frame of ldpc_hip_bit_flip_batch takes on this context's code (host only), -1 for a code the call does not
+   take.  Every term rounded up to 16:
+     bytes = r16(nc) + r16(4 ceil(nc / 32)) + 2 r16(4 ceil(mc / 32))
+   — the nc quantized inputs, a byte each (sign = y, magnitude = r); the word x, a bit per column; the unmet checks u, a bit
+   per check node, of this round and of the next.  tests/golden/h.txt (nc = 1152, mc = 1024): 1 152 + 144 + 2 * 128 = 1 552
+   bytes; a CU's 32 waves are reached before its LDS. */
+int64_t ldpc_hip_bit_flip_lds_bytes(const ldpc_hip_ctx *ctx);
+
 /* channel point x of stream mt19937_64(seed): set_channel_param semantics, frame position := 0 */
 int ldpc_hip_stream_begin(ldpc_hip_ctx *ctx, int channel, uint64_t seed, double x);
 /* advance the stream by n frames without decoding them */

@@ -51,6 +51,12 @@ class ldpc_hip_syndrome_decode_layered(ct.Structure):
                 ("step", ct.c_double), ("scale", ct.c_double), ("offset", ct.c_double), ("flags", ct.c_int)]
 
 
+class ldpc_hip_bit_flip(ct.Structure):
+    _fields_ = [("iterations", ct.c_uint32), ("q_bits", ct.c_int), ("step", ct.c_double), ("check_weight", ct.c_uint32),
+                ("margin", ct.c_uint32), ("flip_threshold", ct.c_uint32), ("seed", ct.c_uint64), ("first_frame", ct.c_uint64),
+                ("flags", ct.c_int)]
+
+
 _lib = None
 
 
@@ -143,6 +149,10 @@ def load_library(path=LIB_PATH):
                                                          vp, vp]
     L.ldpc_hip_syndrome_decode_layered_lds_bytes.restype = ct.c_int64
     L.ldpc_hip_syndrome_decode_layered_lds_bytes.argtypes = [vp]
+    L.ldpc_hip_bit_flip_batch.restype = i32
+    L.ldpc_hip_bit_flip_batch.argtypes = [vp, ct.POINTER(ldpc_hip_bit_flip), u64, vp, i32, vp, i32, vp, vp, vp, vp]
+    L.ldpc_hip_bit_flip_lds_bytes.restype = ct.c_int64
+    L.ldpc_hip_bit_flip_lds_bytes.argtypes = [vp]
     L.ldpc_hip_stream_begin.restype = i32
     L.ldpc_hip_stream_begin.argtypes = [vp, i32, u64, ct.c_double]
     L.ldpc_hip_stream_skip.restype = i32
@@ -847,6 +857,39 @@ class HipDecoder:
     def syndrome_decode_layered_lds_bytes(self):
         """LDS bytes one frame of syndrome_decode_layered_batch takes (-1: the call does not take the code)."""
         return int(self.lib.ldpc_hip_syndrome_decode_layered_lds_bytes(self.ctx))
+
+    def bit_flip_batch(self, llr, syndrome=None, *, iterations=50, q_bits=2, step=1.0, check_weight=2, margin=0, flip_prob=1.0, seed=0,
+                       first_frame=0, shared_llr=False, want=("hard_bits", "iters", "weight"), out=None, stream=None):
+        """Gradient-descent bit flipping toward a given syndrome: in each of at most `iterations` rounds every column within
+        `margin` of the frame's largest penalty check_weight * (unmet check nodes of the column) +- (its reliability, + where
+        the bit differs from the input's decision) flips; with flip_prob < 1 each such column flips with that probability
+        (PGDBF), drawn from Philox under tag 3, `seed` and frame index first_frame + f.  Reliabilities of q_bits bits (2..8)
+        with LLR step `step`; hard decisions are int8 +-1 with q_bits=2.  llr, syndrome, shared_llr, "hard_bits", "iters" (the
+        rounds run) and "weight" as in syndrome_decode_batch; there is no "llr_out".  flip_prob 1.0 is the threshold
+        0xFFFFFFFF (no draws), any other value floor(flip_prob * 2^32).  include/ldpc_amd.h, ldpc_hip_bit_flip_batch."""
+        who = "bit_flip_batch"
+        if "llr_out" in tuple(want) or "llr_out" in (out or {}):
+            raise ValueError(f"{who}: there is no llr_out (outputs: hard_bits, iters, weight)")
+        if not 0.0 <= float(flip_prob) <= 1.0:
+            raise ValueError(f"{who}: flip_prob={flip_prob} is outside [0, 1]")
+        for name, v in (("check_weight", check_weight), ("margin", margin)):
+            if not 0 <= int(v) < 2**32:
+                raise ValueError(f"{who}: {name}={v}")
+        for name, v in (("seed", seed), ("first_frame", first_frame)):
+            if not 0 <= int(v) < 2**64:
+                raise ValueError(f"{who}: {name}={v}")
+        kind, n, fmt, bufs = self._syndrome_decode_call(who, llr, syndrome, shared_llr, iterations, want, out)
+        threshold = 0xFFFFFFFF if float(flip_prob) == 1.0 else int(float(flip_prob) * 2.0**32)  # (exact: a power of two)
+        p = ldpc_hip_bit_flip(int(iterations), int(q_bits), float(step), int(check_weight), int(margin), threshold, int(seed),
+                              int(first_frame), self.SYNDROME_SHARED_LLR if shared_llr else 0)
+        self._check(self.lib.ldpc_hip_bit_flip_batch(self.ctx, ct.byref(p), n, _ptr(llr), kind, _ptr(syndrome), fmt,
+                                                     _ptr(bufs.get("hard_bits")), _ptr(bufs.get("iters")), _ptr(bufs.get("weight")), stream),
+                    "ldpc_hip_bit_flip_batch")
+        return bufs
+
+    def bit_flip_lds_bytes(self):
+        """LDS bytes one frame of bit_flip_batch takes (-1: the call does not take the code)."""
+        return int(self.lib.ldpc_hip_bit_flip_lds_bytes(self.ctx))
 
     def stream_begin(self, channel, seed, x):
         """Channel point x of mt19937_64(seed); also resets the encoder (a fresh channel object)."""

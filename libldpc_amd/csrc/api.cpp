@@ -577,6 +577,28 @@ int64_t ldpc_hip_syndrome_decode_layered_lds_bytes(const ldpc_hip_ctx *ctx)
     return bytes;
 }
 
+int ldpc_hip_bit_flip_batch(ldpc_hip_ctx *ctx, const ldpc_hip_bit_flip *p, uint64_t n, const void *llr, int llr_type, const void *syndrome,
+                            int syndrome_format, uint32_t *hard_bits, uint32_t *iters, uint32_t *weight, void *hip_stream)
+{
+    return guarded([&] {
+        Engine::BitFlipSpec spec;
+        if (p)
+        {
+            spec.iterations = p->iterations, spec.q_bits = p->q_bits, spec.step = p->step;
+            spec.check_weight = p->check_weight, spec.margin = p->margin, spec.flip_threshold = p->flip_threshold;
+            spec.seed = p->seed, spec.first_frame = p->first_frame, spec.flags = p->flags;
+        }
+        ctx->eng->bit_flip_batch(p ? &spec : nullptr, n, llr, llr_type, syndrome, syndrome_format, hard_bits, iters, weight, hip_stream);
+    });
+}
+
+int64_t ldpc_hip_bit_flip_lds_bytes(const ldpc_hip_ctx *ctx)
+{
+    int64_t bytes = -1; // (-1 for a code the call does not take)
+    guarded([&] { bytes = ctx->eng->bit_flip_lds_bytes(); });
+    return bytes;
+}
+
 int64_t ldpc_hip_layered_fixed_direct_lds_bytes(const ldpc_hip_ctx *ctx)
 {
     int64_t bytes = -1; // (the plan builder allocates; -1 for every code the layered plan refuses)

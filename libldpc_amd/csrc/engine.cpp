@@ -2356,6 +2356,103 @@ void Engine::syndrome_decode_layered_batch(const SyndromeDecodeLayeredSpec *spec
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Gradient-descent bit flipping toward a given syndrome (kernels_bit_flip.hip)
+int64_t Engine::bit_flip_lds_bytes() const
+{
+    if (plan_.nc <= 0 || plan_.nc > 0xFFFF || plan_.mc <= 0 || plan_.mc > 0xFFFF) // (the tables hold 16-bit indices)
+        return -1;
+    const size_t bytes = ldpc_amd::bit_flip_lds_bytes(static_cast<size_t>(plan_.nc), static_cast<size_t>(plan_.mc));
+    return bytes <= kCuLdsBytes ? static_cast<int64_t>(bytes) : -1;
+}
+
+std::string Engine::bit_flip_refusal(const BitFlipSpec *spec, int llr_type, int syndrome_format) const
+{
+    const char *entry = "ldpc_hip_bit_flip_batch";
+    const std::string who = std::string(entry) + ": ";
+    if (!spec)
+        return who + "null parameters";
+    if (spec->iterations > 0xFFFFu)
+        return who + "iterations " + std::to_string(spec->iterations) + " is beyond 65535";
+    if (spec->q_bits < 2 || spec->q_bits > 8)
+        return who + "q_bits " + std::to_string(spec->q_bits) + " is outside 2..8";
+    if (!(spec->step > 0.0) || spec->step < 0x1p-20 || spec->step > 0x1p20) // (a NaN fails the first)
+        return who + "the step must lie in [2^-20, 2^20]";
+    if (spec->check_weight < 1 || spec->check_weight > 255)
+        return who + "check_weight " + std::to_string(spec->check_weight) + " is outside 1..255";
+    if (spec->margin > 0xFFFFu)
+        return who + "margin " + std::to_string(spec->margin) + " is beyond 65535";
+    if (spec->flags & ~kSyndromeSharedLlr)
+        return who + "unknown flag bits " + std::to_string(spec->flags & ~kSyndromeSharedLlr);
+    if (llr_type_bytes(llr_type) == 0)
+        return who + "unknown LLR type " + std::to_string(llr_type) + " (0 = binary64, 1 = binary32, 2 = binary16, 3 = int8)";
+    if (std::string why = bits_format_refusal(entry, "syndrome", syndrome_format); !why.empty())
+        return why;
+    if (bit_flip_lds_bytes() < 0)
+        return who + "the code of " + std::to_string(plan_.mc) + " x " + std::to_string(plan_.nc) +
+               " is not taken: more than 65 535 columns or check nodes, or a frame beyond the 160 KB of LDS of a CU "
+               "(ldpc_hip_bit_flip_lds_bytes; there is no other kernel)";
+    return "";
+}
+
+void Engine::bit_flip_batch(const BitFlipSpec *spec, uint64_t n, const void *llr, int llr_type, const void *syndrome, int syndrome_format,
+                            uint32_t *hard_bits, uint32_t *iters, uint32_t *weight, void *stream)
+{
+    if (const std::string why = bit_flip_refusal(spec, llr_type, syndrome_format); !why.empty())
+        throw std::runtime_error(why);
+    if (n && !llr)
+        throw std::runtime_error("ldpc_hip_bit_flip_batch: null llr");
+    if (n == 0 || (!hard_bits && !iters && !weight))
+        return;
+    bind_device();
+    if (!bf_row_ptr_) // H by rows and by columns, each in file order, repeated entries included
+    {
+        const SparseGF2 &H = code_->H;
+        const std::vector<uint32_t> rp(H.rptr.begin(), H.rptr.end()), cp(H.cptr.begin(), H.cptr.end());
+        const std::vector<uint16_t> rc(H.rcol.begin(), H.rcol.end()), cr(H.crow.begin(), H.crow.end());
+        bf_row_col_ = static_cast<const uint16_t *>(upload_table(rc.data(), rc.size() * 2, "rows of H (16 bits)"));
+        bf_col_row_ = static_cast<const uint16_t *>(upload_table(cr.data(), cr.size() * 2, "columns of H (16 bits)"));
+        bf_col_ptr_ = static_cast<const uint32_t *>(upload_table(cp.data(), cp.size() * 4, "columns of H (16 bits)"));
+        bf_row_ptr_ = static_cast<const uint32_t *>(upload_table(rp.data(), rp.size() * 4, "rows of H (16 bits)")); // last: the mark
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint64_t nc = static_cast<uint64_t>(plan_.nc), mc = static_cast<uint64_t>(plan_.mc), words = (nc + 31) / 32;
+    const bool shared = (spec->flags & kSyndromeSharedLlr) != 0;
+    BitFlipArgs a{};
+    a.nc = static_cast<uint32_t>(nc), a.mc = static_cast<uint32_t>(mc), a.words = static_cast<uint32_t>(words);
+    a.syn_words = static_cast<uint32_t>((mc + 31) / 32);
+    a.iterations = spec->iterations;
+    a.llr_type = llr_type, a.syndrome_format = syndrome_format, a.shared_llr = shared ? 1 : 0;
+    a.qmax = (1 << (spec->q_bits - 1)) - 1, a.inv = 1.0 / spec->step; // (the quantizer of quantizer_args)
+    a.check_weight = static_cast<int32_t>(spec->check_weight), a.margin = static_cast<int32_t>(spec->margin);
+    a.flip_threshold = spec->flip_threshold;
+    a.k0 = static_cast<uint32_t>(spec->seed), a.k1 = static_cast<uint32_t>(spec->seed >> 32);
+    a.draw_blocks = static_cast<uint32_t>((nc + 3) / 4);
+    a.frame_bytes = static_cast<uint32_t>(bit_flip_lds_bytes());
+    a.group_frames = bit_flip_group_frames(a.frame_bytes);
+    a.row_ptr = bf_row_ptr_, a.row_col = bf_row_col_, a.col_ptr = bf_col_ptr_, a.col_row = bf_col_row_;
+    const size_t elem = llr_type_bytes(llr_type), in_row = elem * nc, syn_row = bits_row_bytes(syndrome_format, mc);
+    DeviceBuffer &llr_stage = llr_type == kLlrF64 ? stage_in_ : stage_typed_;
+    if (shared) // one row for every frame: staged once
+        a.llr = stage_input(llr, in_row, llr_stage, stream);
+    const uint64_t sub = std::max<uint64_t>(gf2_sub_batch() / elem, 1); // (elements of up to 8 bytes, not bits)
+    for (uint64_t done = 0; done < n; done += sub)
+    {
+        const uint64_t m = std::min(sub, n - done);
+        if (!shared)
+            a.llr = stage_input(static_cast<const char *>(llr) + in_row * done, in_row * m, llr_stage, stream);
+        a.syndrome = syndrome ? stage_input(static_cast<const char *>(syndrome) + syn_row * done, syn_row * m, stage_in_b_, stream) : nullptr;
+        OutStage st;
+        a.hard_bits = st.route(hard_bits ? hard_bits + done * words : nullptr, stage_sd_[0], 4 * m * words);
+        a.iters = st.route(iters ? iters + done : nullptr, stage_sd_[1], 4 * m);
+        a.weight = st.route(weight ? weight + done : nullptr, stage_sd_[2], 4 * m);
+        a.first_frame = spec->first_frame + done;
+        a.n = m;
+        check(launch_bit_flip(a, s), "bit_flip_batch");
+        st.flush(s, &pin_out_);
+    }
+}
+
 void Engine::stream_rewind_encoder(uint64_t frames_back, void *stream)
 {
     if (!code_->has_G() || frames_back == 0 || counter_) // (counter-based noise: a codeword depends on its frame index alone)

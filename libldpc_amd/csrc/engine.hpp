@@ -428,6 +428,21 @@ class Engine
     void syndrome_decode_layered_batch(const SyndromeDecodeLayeredSpec *spec, uint64_t n, const void *llr, int llr_type, const void *syndrome,
                                        int syndrome_format, uint32_t *hard_bits, uint32_t *iters, uint32_t *weight, double *llr_out,
                                        void *stream);
+    // gradient-descent bit flipping toward a given syndrome (include/ldpc_amd.h, ldpc_hip_bit_flip_batch;
+    // kernels_bit_flip.hip) on the two adjacency tables of H in file order.  As above: everything is in the spec
+    struct BitFlipSpec
+    {
+        uint32_t iterations = 0;
+        int q_bits = 0;
+        double step = 0.0;
+        uint32_t check_weight = 0, margin = 0, flip_threshold = 0;
+        uint64_t seed = 0, first_frame = 0;
+        int flags = 0;
+    };
+    std::string bit_flip_refusal(const BitFlipSpec *spec, int llr_type, int syndrome_format) const;
+    int64_t bit_flip_lds_bytes() const;
+    void bit_flip_batch(const BitFlipSpec *spec, uint64_t n, const void *llr, int llr_type, const void *syndrome, int syndrome_format,
+                        uint32_t *hard_bits, uint32_t *iters, uint32_t *weight, void *stream);
 
     // ---- fused channel + decode on the reference's noise stream ----
     // set_channel_param semantics (channel.cpp:37-42): the stream restarts at frame 0.
@@ -640,6 +655,8 @@ class Engine
     DeviceBuffer stage_sd_[4];                  // ... and of syndrome_decode_batch
     const uint32_t *sd_cn_row_ = nullptr;       // Plan::cn_rank_row on the device, at the first syndrome_decode_batch
     const uint32_t *sdl_step_row_ = nullptr;    // (step, lane) -> file row, at the first syndrome_decode_layered_batch
+    const uint32_t *bf_row_ptr_ = nullptr, *bf_col_ptr_ = nullptr; // the rows and the columns of H, file order, u16 indices,
+    const uint16_t *bf_row_col_ = nullptr, *bf_col_row_ = nullptr; // at the first bit_flip_batch
     uint64_t gf2_sub_batch() const; // frames per launch: staging buffers stay modest, no grid dimension overflows
     // a host input of a batch call on the device (small ones through page-locked memory); a device pointer comes back as it is
     const void *stage_input(const void *src, size_t bytes, DeviceBuffer &stage, void *stream);

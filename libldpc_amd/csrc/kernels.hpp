@@ -651,6 +651,56 @@ struct SyndromeDecodeLayeredArgs
 };
 int launch_syndrome_decode_layered(const SyndromeDecodeLayeredArgs &a, const DevLayerPlan &L, void *stream);
 
+// ---- gradient-descent bit flipping toward a given syndrome (kernels_bit_flip.hip; include/ldpc_amd.h,
+// ldpc_hip_bit_flip_batch): one wave per frame, several frames to a workgroup, on the two adjacency tables of H in file
+// order (u16 indices), the typed LLRs read in place ----
+// LDS of one frame (include/ldpc_amd.h, ldpc_hip_bit_flip_lds_bytes), every part rounded up to 16 bytes: the quantized
+// inputs (a byte each: sign = y, magnitude = r), the word x (a bit per column), the unmet checks u (a bit per check node)
+// twice: the round's and the next round's
+constexpr size_t bit_flip_round16(size_t x) { return (x + 15) & ~size_t(15); }
+constexpr size_t bit_flip_lds_bytes(size_t nc, size_t mc)
+{
+    return bit_flip_round16(nc) + bit_flip_round16(4 * ((nc + 31) / 32)) + 2 * bit_flip_round16(4 * ((mc + 31) / 32));
+}
+constexpr uint32_t kBitFlipMaxFrames = 4; // frames (waves) of a workgroup at most
+// frames of a workgroup: as many as kBitFlipMaxFrames whose LDS stays within a quarter of the CU's, one at least
+constexpr uint32_t bit_flip_group_frames(size_t frame_bytes)
+{
+    const size_t fit = (160 * 1024 / 4) / (frame_bytes ? frame_bytes : 1);
+    return fit >= kBitFlipMaxFrames ? kBitFlipMaxFrames : (fit >= 1 ? static_cast<uint32_t>(fit) : 1u);
+}
+constexpr uint32_t kBitFlipEveryCandidate = 0xFFFFFFFFu; // flip_threshold: no draws
+struct BitFlipArgs
+{
+    uint32_t nc, mc;            // both 1..65535
+    uint32_t words, syn_words;  // ceil(nc / 32), ceil(mc / 32)
+    uint32_t iterations;        // <= 65535
+    int32_t llr_type;           // LlrType: the kernel reads the elements in place
+    int32_t syndrome_format;    // BitsFormat (not read where syndrome is null)
+    int32_t shared_llr;         // llr is one row [nc] for every frame
+    int32_t qmax;               // 2^(q_bits - 1) - 1, 1..127
+    double inv;                 // fl(1 / step)
+    int32_t check_weight;       // w, 1..255
+    int32_t margin;             // 0..65535
+    uint32_t flip_threshold;    // kBitFlipEveryCandidate, or a candidate flips iff its draw is below
+    uint32_t k0, k1;            // the Philox key: seed & 0xFFFFFFFF, seed >> 32
+    uint64_t first_frame;       // frame f draws as frame first_frame + f
+    uint32_t draw_blocks;       // ceil(nc / 4): the Philox blocks of one round
+    uint32_t frame_bytes;       // bit_flip_lds_bytes(nc, mc)
+    uint32_t group_frames;      // bit_flip_group_frames(frame_bytes)
+    const uint32_t *row_ptr;    // [mc + 1]: the rows of H in file order, repeated entries included
+    const uint16_t *row_col;    // columns, < nc
+    const uint32_t *col_ptr;    // [nc + 1]: the columns of H, the entries of each in file order
+    const uint16_t *col_row;    // rows, < mc
+    const void *llr;            // [n][nc] (or [nc]) elements of llr_type, column order
+    const void *syndrome;       // [n][mc] bytes or [n][syn_words] words, row order; nullptr = all zero
+    uint32_t *hard_bits;        // [n][words] or nullptr
+    uint32_t *iters;            // [n] or nullptr
+    uint32_t *weight;           // [n] or nullptr
+    uint64_t n;                 // <= 2^20
+};
+int launch_bit_flip(const BitFlipArgs &a, void *stream);
+
 // opt-in non-parity ternary min-sum, bit-sliced over 32 frames per workgroup (kernels_ternary.hip; include/ldpc_amd.h,
 // ldpc_hip_set_min_sum_ternary) on the general plan.  a.ms_* are not read.  With a.llr_out null the planes of A are left out
 // of the group's LDS (plan.hpp, ternary_lds_bytes)
