@@ -131,7 +131,8 @@ void ldpc_hip_set_fast_mode(ldpc_hip_ctx *ctx, int mode);
    frame high, tag); tag 0 AWGN: transmitted bit i is normal i % 4 of block i / 4, two binary32 Box-Muller pairs per block,
    u = (w0 + 0.5) / 2^32, angle w1 / 2^32 revolutions (so |n| <= sqrt(66 ln 2) = 6.764); tag 1 BSC / BEC: bit i flipped /
    erased when (w[i % 4] of block i / 4 + 0.5) / 2^32 < eps; tag 2 encoder (a generator matrix loaded): info bit j is bit
-   j % 32 of word (j / 32) % 4 of block j / 128, and frame f's codeword is u_f G (no running sum over the frames).  Only error
+   j % 32 of word (j / 32) % 4 of block j / 128, and frame f's codeword is u_f G (no running sum over the frames); tag 3 the flip draws of ldpc_hip_bit_flip_batch and tag 4
+   the gamma table of ldpc_hip_relay_decode_batch, both stated there (batch interface: no stream state).  Only error
    rates (statistically) compare with the reference; ldpc_hip_stream_skip is O(1), ldpc_hip_stream_raw_draws fails, a
    sharded step exchanges nothing.  Does not combine with ldpc_hip_set_fast_mode (ldpc_hip_stream_decode fails).  Part 1
    (simulate(), decode(), ...) always uses the reference stream. */
@@ -1017,6 +1018,103 @@ int ldpc_hip_bit_flip_batch(ldpc_hip_ctx *ctx, const ldpc_hip_bit_flip *p, uint6
    per check node, of this round and of the next.  tests/golden/h.txt (nc = 1152, mc = 1024): 1 152 + 144 + 2 * 128 = 1 552
    bytes; a CU's 32 waves are reached before its LDS. */
 int64_t ldpc_hip_bit_flip_lds_bytes(const ldpc_hip_ctx *ctx);
+
+/* MIN-SUM WITH MEMORY, RUN AS A RELAY OF LEGS, toward a given syndrome (libldpc_amd/csrc/kernels_relay_decode.hip): the
+   message-passing decoder for the degenerate check matrices of quantum LDPC and surface codes (column degree 2, many
+   equal-weight solutions, trapping sets everywhere), on which plain min-sum swings between solutions instead of choosing
+   one.  DMem-BP (Mueller, Alexander, Beverland, Buehler, Johnson, Maurer, Vandeth, "Improved belief propagation is
+   sufficient for real-time decoding of quantum memory", 2025): a column's prior for an iteration is a mix of its input
+   and its own previous total, by a strength gamma per column.  Relay-BP (the same authors): several such runs ("legs") are
+   chained, each with its own gamma, some of them negative, each starting from the totals the last one left; every word
+   that meets the syndrome is priced and the cheapest returned.  No elimination (ldpc_hip_osd_syndrome_batch), a byte per
+   message of LDS.  NON-PARITY (the reference has no such decoder).
+   The common rules are those of ldpc_hip_syndrome_decode_batch, word for word: device or host buffers, checks before the GPU
+   naming the entry in ldpc_hip_last_error, n == 0 returns 0 after them, every output may be NULL (all NULL: nothing is
+   launched), ordered on hip_stream, one launch per 2^20 frames at most, a frame's results do not depend on which frames
+   share its call or its workgroup, every output bit is determined.  NO SETTING AND NO STATE OF THE STREAM INTERFACE IS READ OR
+   CHANGED: everything the call uses is in *p and gamma.
+   In:  llr, llr_type, syndrome, syndrome_format: exactly as in ldpc_hip_syndrome_decode_batch — llr[n][nc] of llr_type
+        (F64 / F32 / F16 / I8), column order, read in place in their own type, ONE row [nc] with
+        LDPC_HIP_SYNDROME_SHARED_LLR in p->flags; syndrome[n][mc] U8 or PACKED32, bit r = check node r in file row order,
+        NULL = all zero, the bits of a row's last word from mc on ignored.
+        gamma[legs][nc], int8, column order, shared by all frames (device or host): g means a strength of g / 64.  Values
+        outside -64..64 are clamped to that range by the kernel.  NULL = all zero.
+   Out: hard_bits[n][ceil(nc / 32)] (the bits of a row's last word from nc on 0), iters[n], weight[n], solutions[n],
+        best_leg[n], cost[n].
+   Arithmetic, with q = p->q_bits, D = p->step, Qmax = 2^(q-1) - 1, inv = fl(1 / D) and lut built from (p->scale, p->offset) by
+   the same host routine as everywhere.  All integer after the quantizer:
+     1. Quantizer: item 1 of ldpc_hip_syndrome_decode_batch.  L[v] = clamp(rint(fl(W[v] * inv)), -Qmax, +Qmax), W the element
+        widened exactly to binary64; a NaN gives 0, infinities saturate.  For LDPC_HIP_LLR_I8, L = clamp(k, -Qmax, +Qmax).
+        y[v] = (L[v] <= 0).
+     2. The state is the totals A[v], carried from leg to leg, and the messages.  Before leg 0, A := L.
+     3. Leg l runs at most T iterations, T = first_iterations for l = 0 and leg_iterations otherwise.  At the start of a leg
+        every check-to-variable message is 0.
+     4. Iteration, memory term.  For every column, with g = gamma[l][v] clamped to -64..64: p = g (A[v] - L[v]) (fits 32
+        bits), d = sign(p) ((|p| + 32) >> 6) (rounds half away from zero: the decoder stays sign-symmetric),
+        Lambda[v] = clamp(L[v] + d, -32767, +32767), A[v] being the total the previous iteration or leg left.
+     5. Variable nodes: v2c_e = clamp(Lambda[v] + (the sum of the column's c2v) - c2v_e, -Qmax, +Qmax).  In a leg's first
+        iteration the c2v are 0, so v2c = clamp(Lambda[v]).
+     6. Check nodes: items 3 and 4 of ldpc_hip_set_min_sum_quantization with the sign change of
+        ldpc_hip_syndrome_decode_batch: the message is negative iff (the number of other v2c < 0) + s[c] is odd.
+     7. Totals: A[v] = Lambda[v] + the sum of the column's c2v of this iteration; hard[v] = (A[v] <= 0).
+     8. Test: if XOR of hard over the row == s[c] for every check node, the leg ends at this iteration, of index i counted
+        from 0, and hard is a SOLUTION.  Its cost is the sum of |L[v]| over the columns with hard[v] != y[v] (fits 32 bits).
+        It replaces the kept word iff no word is kept yet or its cost is STRICTLY smaller (the earliest wins ties).  A leg
+        that never meets s ends after T iterations.  In either case the next leg starts from these A.
+     9. The frame ends after leg legs - 1, or as soon as stop_after legs have produced a solution.
+    10. hard_bits = the kept word; if there is none, the decisions of the last iteration run.  iters = the sum, over the
+        legs run, of i for a leg that met s and of T for one that did not (one leg counts exactly as
+        ldpc_hip_syndrome_decode_batch).  weight = the check nodes the returned word does not meet: 0 iff a solution was
+        found.  solutions = the legs that met s.  best_leg and cost = those of the kept word, both 0xFFFFFFFF when there is
+        none.
+   Identity: with legs = 1 and gamma NULL or all zero, hard_bits, iters and weight are those of
+   ldpc_hip_syndrome_decode_batch with early_term = 1 and iterations = first_iterations, for any s and any setting.
+   Prefix: a call with k legs agrees, in every output, with a call with K > k legs on the first k rows of the same gamma, on
+   every frame whose solutions reached stop_after within k legs.
+   (tests/test_relay_decode_host.py on the mirror tests/relay_decode_ref.py, tests/test_gpu_relay_decode.py on the GPU.)
+   Refused (host only, -1): a null p; legs outside 1..256; first_iterations or leg_iterations outside 1..65535; stop_after
+   outside 1..legs; q_bits outside 2..8; a step that is NaN, <= 0 or outside [2^-20, 2^20]; a scale outside (0, 1], an offset
+   outside [0, 1e6], a NaN in either; form outside 0..2; an unknown flag bit, llr_type or syndrome_format; a NULL llr with
+   n > 0; a code the call does not take, or a form the code does not fit.
+   Which codes it takes: those of ldpc_hip_syndrome_decode_batch — every check node with at least two entries, at most 65 535
+   columns — whose frame (below) fits 160 KB of LDS.  Form 2 additionally needs FOUR frames to fit 160 KB.
+   How it runs: one kernel body on the tables of quantized min-sum, the column map and the check-node order of
+   ldpc_hip_syndrome_decode_batch, templated on the threads that share a frame.  Form 1: a workgroup of 256 threads per
+   frame, workgroup barriers between the passes, the stop test through two vote words.  Form 2: a wave per frame and four
+   frames to a workgroup, no workgroup barrier (a wave's LDS operations execute in order), the stop test a ballot: for codes
+   of 72 to a few hundred columns with very many shots, where 256 threads would mostly idle.  Form 0 chooses: form 2 where
+   it fits and the code has at most 384 columns and 384 check nodes.  All forms return the same
+   bits.  The memory term is formed inside the variable-node pass from the total it is about to overwrite (no further pass,
+   no further array); the leg's gamma is read from global memory through the rank -> column map; the cost (a reduction)
+   and the kept word (a ballot per 64 columns into LDS, column order) are formed only in iterations that met s.
+   A gamma table: HipDecoder.relay_gammas (libldpc_amd/binding.py) draws one from ldpc_hip_philox under TAG 4: row 0 is one
+   value everywhere, row l >= 1, column v is lo + ((draw * (hi - lo + 1)) >> 32), the draw being word v & 3 of block v >> 2
+   of frame l (tags 0..2: ldpc_hip_set_noise; tag 3: ldpc_hip_bit_flip_batch). */
+typedef struct
+{
+    uint32_t legs;             /* 1..256 */
+    uint32_t first_iterations; /* 1..65535: iterations leg 0 may take */
+    uint32_t leg_iterations;   /* 1..65535: iterations every later leg may take */
+    uint32_t stop_after;       /* 1..legs: the call ends for a frame once this many legs have met s */
+    int q_bits;                /* 2..8 */
+    double step;               /* 2^-20 .. 2^20 */
+    double scale;              /* (0, 1] */
+    double offset;             /* [0, 1e6] */
+    int form;                  /* 0 = the library chooses, 1 = a workgroup per frame, 2 = a wave per frame; same results */
+    int flags;                 /* LDPC_HIP_SYNDROME_SHARED_LLR or 0 */
+} ldpc_hip_relay_decode;
+int ldpc_hip_relay_decode_batch(ldpc_hip_ctx *ctx, const ldpc_hip_relay_decode *p, uint64_t n, const void *llr, int llr_type,
+                                const void *syndrome, int syndrome_format, const int8_t *gamma, uint32_t *hard_bits,
+                                uint32_t *iters, uint32_t *weight, uint32_t *solutions, uint32_t *best_leg, uint32_t *cost,
+                                void *hip_stream);
+/* LDS bytes one frame of ldpc_hip_relay_decode_batch takes on this context's code in `form` (host only; 0 = either form),
+   -1 for a code the call does not take, a form outside 0..2, or form 2 on a code of which four frames exceed 160 KB.  With
+   `slots` as for ldpc_hip_syndrome_decode_lds_bytes and every term rounded up to 16:
+     bytes = r16(slots) + r16(4 nc) + 160 + r16(4 ceil(mc / 32)) + r16(nc) + r16(4 ceil(nc / 32))
+   — the frame of ldpc_hip_syndrome_decode_lds_bytes and behind it the kept word, a bit per column.  The cost's reduction
+   takes the four partial sums that are part of the 160 bytes (form 2 reduces in registers): no byte more.  The same number
+   in both forms; a workgroup of form 2 takes four times as much. */
+int64_t ldpc_hip_relay_decode_lds_bytes(const ldpc_hip_ctx *ctx, int form);
 
 /* channel point x of stream mt19937_64(seed): set_channel_param semantics, frame position := 0 */
 int ldpc_hip_stream_begin(ldpc_hip_ctx *ctx, int channel, uint64_t seed, double x);

@@ -57,6 +57,12 @@ class ldpc_hip_bit_flip(ct.Structure):
                 ("flags", ct.c_int)]
 
 
+class ldpc_hip_relay_decode(ct.Structure):
+    _fields_ = [("legs", ct.c_uint32), ("first_iterations", ct.c_uint32), ("leg_iterations", ct.c_uint32), ("stop_after", ct.c_uint32),
+                ("q_bits", ct.c_int), ("step", ct.c_double), ("scale", ct.c_double), ("offset", ct.c_double), ("form", ct.c_int),
+                ("flags", ct.c_int)]
+
+
 _lib = None
 
 
@@ -153,6 +159,10 @@ def load_library(path=LIB_PATH):
     L.ldpc_hip_bit_flip_batch.argtypes = [vp, ct.POINTER(ldpc_hip_bit_flip), u64, vp, i32, vp, i32, vp, vp, vp, vp]
     L.ldpc_hip_bit_flip_lds_bytes.restype = ct.c_int64
     L.ldpc_hip_bit_flip_lds_bytes.argtypes = [vp]
+    L.ldpc_hip_relay_decode_batch.restype = i32
+    L.ldpc_hip_relay_decode_batch.argtypes = [vp, ct.POINTER(ldpc_hip_relay_decode), u64, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.ldpc_hip_relay_decode_lds_bytes.restype = ct.c_int64
+    L.ldpc_hip_relay_decode_lds_bytes.argtypes = [vp, i32]
     L.ldpc_hip_stream_begin.restype = i32
     L.ldpc_hip_stream_begin.argtypes = [vp, i32, u64, ct.c_double]
     L.ldpc_hip_stream_skip.restype = i32
@@ -485,7 +495,7 @@ class HipDecoder:
 
     def philox(self, seed, tag, frame, first_block, n_blocks):
         """The counter mode's raw words, [n_blocks][4] uint32: blocks first_block.. of `frame` under `tag` (0 AWGN, 1 BSC /
-        BEC, 2 encoder info bits), from the device generator."""
+        BEC, 2 encoder info bits, 3 the draws of bit_flip_batch, 4 the table of relay_gammas), from the device generator."""
         out = np.zeros((int(n_blocks), 4), np.uint32)
         self._check(self.lib.ldpc_hip_philox(self.ctx, int(seed), int(tag), int(frame), int(first_block), int(n_blocks),
                                              _ptr(out), None), "ldpc_hip_philox")
@@ -803,9 +813,10 @@ class HipDecoder:
                                                             _ptr(bufs.get("llr_out")), stream), "ldpc_hip_syndrome_decode_batch")
         return bufs
 
-    def _syndrome_decode_call(self, who, llr, syndrome, shared_llr, iterations, want, out):
-        """What the two decoders toward a syndrome check of their arguments before the library sees them -> the LLR type, the
-        frames, the syndrome's format and the output buffers."""
+    def _syndrome_decode_call(self, who, llr, syndrome, shared_llr, iterations, want, out, further=None):
+        """What the decoders toward a syndrome check of their arguments before the library sees them -> the LLR type, the
+        frames, the syndrome's format and the output buffers.  `further`: the names of uint32 [n] outputs that take the place
+        of llr_out."""
         name = str(llr.dtype).replace("torch.", "")
         if name not in self.LLR_TYPES:
             raise TypeError(f"{who} takes float64, float32, float16 or int8 LLRs, not {llr.dtype}")
@@ -828,6 +839,9 @@ class HipDecoder:
             raise ValueError(f"{who}: iterations={iterations}")
         spec = {"hard_bits": ((n, (self.nc + 31) // 32), np.uint32), "iters": ((n,), np.uint32), "weight": ((n,), np.uint32),
                 "llr_out": ((n, self.nc), np.float64)}
+        if further is not None:
+            del spec["llr_out"]
+            spec.update({k: ((n,), np.uint32) for k in further})
         bufs = self._wanted(want, out, spec)
         self._check_bufs(who, bufs, spec)
         return self.LLR_TYPES[name], n, fmt, bufs
@@ -890,6 +904,55 @@ class HipDecoder:
     def bit_flip_lds_bytes(self):
         """LDS bytes one frame of bit_flip_batch takes (-1: the call does not take the code)."""
         return int(self.lib.ldpc_hip_bit_flip_lds_bytes(self.ctx))
+
+    RELAY_OUTPUTS = ("hard_bits", "iters", "weight", "solutions", "best_leg", "cost")
+    RELAY_NONE, TAG_RELAY = 0xFFFFFFFF, 4
+
+    def relay_decode_batch(self, llr, syndrome=None, gamma=None, *, legs, first_iterations=50, leg_iterations=30, stop_after=1, q_bits=6,
+                           step=0.25, scale=1.0, offset=0.0, form=0, shared_llr=False, want=RELAY_OUTPUTS, out=None, stream=None):
+        """Min-sum with memory, run as a relay of `legs` legs, toward a given syndrome: the decoder for degenerate codes
+        (quantum LDPC, surface codes) on which syndrome_decode_batch swings between solutions.  In every iteration a column's
+        prior is its input plus gamma[leg][column] / 64 times (its previous total - its input); leg 0 may take
+        first_iterations, every later leg leg_iterations, each starts from the totals the last one left; every word that meets
+        the syndrome is priced by the input magnitudes it contradicts, the cheapest is returned, and a frame ends once
+        stop_after legs have met the syndrome.  gamma is int8 [legs][nc] in column order, host or device, shared by all frames
+        (None = all zero; relay_gammas draws one).  llr, syndrome, shared_llr, q_bits, step, scale, offset as in
+        syndrome_decode_batch.  form: 0 = the library chooses, 1 = a workgroup per frame, 2 = a wave per frame (same results).
+        "hard_bits", "iters" (summed over the legs run) and "weight" as there; "solutions" (the legs that met the syndrome),
+        "best_leg" and "cost" (those of the returned word, RELAY_NONE where no leg met it), all uint32 [n].
+        include/ldpc_amd.h, ldpc_hip_relay_decode_batch."""
+        who = "relay_decode_batch"
+        for name, v in (("legs", legs), ("first_iterations", first_iterations), ("leg_iterations", leg_iterations), ("stop_after", stop_after)):
+            if not 0 <= int(v) < 2**32:
+                raise ValueError(f"{who}: {name}={v}")
+        if gamma is not None:
+            if str(gamma.dtype).replace("torch.", "") != "int8":
+                raise TypeError(f"{who}: gamma is int8, not {gamma.dtype}")
+            if tuple(gamma.shape) != (int(legs), self.nc):
+                raise ValueError(f"{who}: gamma is [{int(legs)}][{self.nc}], not {tuple(gamma.shape)}")
+        kind, n, fmt, bufs = self._syndrome_decode_call(who, llr, syndrome, shared_llr, 0, want, out, further=self.RELAY_OUTPUTS[3:])
+        p = ldpc_hip_relay_decode(int(legs), int(first_iterations), int(leg_iterations), int(stop_after), int(q_bits), float(step),
+                                  float(scale), float(offset), int(form), self.SYNDROME_SHARED_LLR if shared_llr else 0)
+        self._check(self.lib.ldpc_hip_relay_decode_batch(self.ctx, ct.byref(p), n, _ptr(llr), kind, _ptr(syndrome), fmt, _ptr(gamma),
+                                                         *(_ptr(bufs.get(k)) for k in self.RELAY_OUTPUTS), stream),
+                    "ldpc_hip_relay_decode_batch")
+        return bufs
+
+    def relay_decode_lds_bytes(self, form=0):
+        """LDS bytes one frame of relay_decode_batch takes in `form` (-1: the call does not take the code in that form)."""
+        return int(self.lib.ldpc_hip_relay_decode_lds_bytes(self.ctx, int(form)))
+
+    def relay_gammas(self, legs, lo, hi, seed, first=0):
+        """A gamma table for relay_decode_batch, int8 [legs][nc]: row 0 is `first` everywhere; row l >= 1, column v is
+        lo + ((draw * (hi - lo + 1)) >> 32), the draw being word v & 3 of Philox block v >> 2 of frame l under tag 4 and `seed`
+        (the device generator: philox)."""
+        if not (1 <= int(legs) <= 256 and -128 <= int(lo) <= int(hi) <= 127 and -128 <= int(first) <= 127):
+            raise ValueError(f"relay_gammas: legs={legs}, lo={lo}, hi={hi}, first={first}")
+        g = np.full((int(legs), self.nc), int(first), np.int8)
+        for leg in range(1, int(legs)):
+            draw = self.philox(seed, self.TAG_RELAY, leg, 0, (self.nc + 3) // 4).reshape(-1)[:self.nc].astype(np.uint64)
+            g[leg] = (int(lo) + ((draw * np.uint64(int(hi) - int(lo) + 1)) >> np.uint64(32)).astype(np.int64)).astype(np.int8)
+        return g
 
     def stream_begin(self, channel, seed, x):
         """Channel point x of mt19937_64(seed); also resets the encoder (a fresh channel object)."""

@@ -17,7 +17,7 @@ OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(PKG, "libldpc.so")
 CLI = os.path.join(PKG, "ldpcsim")
 
-LIB_SOURCES = ["kernels.hip", "kernels_reg.hip", "kernels_reg2.hip", "kernels_reg2u.hip", "kernels_fast.hip", "kernels_layered.hip", "kernels_layered_ms.hip", "kernels_layered_fixed.hip", "kernels_layered_fixed_direct.hip", "kernels_convert.hip", "kernels_gf2.hip", "kernels_channel.hip", "kernels_erasure.hip", "kernels_erasure_solve.hip", "kernels_osd.hip", "kernels_osd_syndrome.hip","kernels_syndrome_decode.hip", "kernels_syndrome_decode_layered.hip", "kernels_bit_flip.hip", "kernels_qms.hip", "kernels_ternary.hip", "kernels_fused.hip", "kernels_bec.hip", "sim_kernels.hip", "rng_kernels.hip", "counter_kernels.hip", "selftest.hip", "engine.cpp", "comm.cpp", "api.cpp", "sim.cpp", "code.cpp", "plan.cpp", "mt64.cpp", "mtstates.cpp"]
+LIB_SOURCES = ["kernels.hip", "kernels_reg.hip", "kernels_reg2.hip", "kernels_reg2u.hip", "kernels_fast.hip", "kernels_layered.hip", "kernels_layered_ms.hip", "kernels_layered_fixed.hip", "kernels_layered_fixed_direct.hip", "kernels_convert.hip", "kernels_gf2.hip", "kernels_channel.hip", "kernels_erasure.hip", "kernels_erasure_solve.hip", "kernels_osd.hip", "kernels_osd_syndrome.hip","kernels_syndrome_decode.hip", "kernels_syndrome_decode_layered.hip", "kernels_bit_flip.hip", "kernels_relay_decode.hip","kernels_qms.hip", "kernels_ternary.hip", "kernels_fused.hip", "kernels_bec.hip", "sim_kernels.hip", "rng_kernels.hip", "counter_kernels.hip", "selftest.hip", "engine.cpp", "comm.cpp", "api.cpp", "sim.cpp", "code.cpp", "plan.cpp", "mt64.cpp", "mtstates.cpp"]
 CLI_SOURCES = ["ldpcsim_main.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -ffp-contract=off: every fused multiply-add is written explicitly (detmath.h); results must not

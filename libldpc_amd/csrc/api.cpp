@@ -599,6 +599,30 @@ int64_t ldpc_hip_bit_flip_lds_bytes(const ldpc_hip_ctx *ctx)
     return bytes;
 }
 
+int ldpc_hip_relay_decode_batch(ldpc_hip_ctx *ctx, const ldpc_hip_relay_decode *p, uint64_t n, const void *llr, int llr_type,
+                                const void *syndrome, int syndrome_format, const int8_t *gamma, uint32_t *hard_bits, uint32_t *iters,
+                                uint32_t *weight, uint32_t *solutions, uint32_t *best_leg, uint32_t *cost, void *hip_stream)
+{
+    return guarded([&] {
+        Engine::RelayDecodeSpec spec;
+        if (p)
+        {
+            spec.legs = p->legs, spec.first_iterations = p->first_iterations, spec.leg_iterations = p->leg_iterations;
+            spec.stop_after = p->stop_after, spec.q_bits = p->q_bits, spec.step = p->step, spec.scale = p->scale, spec.offset = p->offset;
+            spec.form = p->form, spec.flags = p->flags;
+        }
+        ctx->eng->relay_decode_batch(p ? &spec : nullptr, n, llr, llr_type, syndrome, syndrome_format, gamma, hard_bits, iters, weight,
+                                     solutions, best_leg, cost, hip_stream);
+    });
+}
+
+int64_t ldpc_hip_relay_decode_lds_bytes(const ldpc_hip_ctx *ctx, int form)
+{
+    int64_t bytes = -1; // (the tables are built on the host at the first call; -1 for a code or a form the call does not take)
+    guarded([&] { bytes = ctx->eng->relay_decode_lds_bytes(form); });
+    return bytes;
+}
+
 int64_t ldpc_hip_layered_fixed_direct_lds_bytes(const ldpc_hip_ctx *ctx)
 {
     int64_t bytes = -1; // (the plan builder allocates; -1 for every code the layered plan refuses)

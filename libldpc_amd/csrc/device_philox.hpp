@@ -25,6 +25,8 @@ enum CounterTag : uint32_t
     kTagDraw = 1, // BSC / BEC
     kTagInfo = 2, // encoder info bits
     kTagFlip = 3, // bit flipping: the draw of column v in round t is word v % 4 of block t * ceil(nc / 4) + v / 4
+    kTagRelay = 4, // relay decoding's gamma table (drawn on the host side, binding.py relay_gammas): row l is frame l,
+                   // column v word v % 4 of block v / 4
 };
 
 __host__ __device__ __forceinline__ uint4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1)

@@ -2453,6 +2453,128 @@ void Engine::bit_flip_batch(const BitFlipSpec *spec, uint64_t n, const void *llr
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Min-sum with memory, run as a relay of legs, toward a given syndrome (kernels_relay_decode.hip)
+// form 2 (a wave per frame) where four frames fit the CU's LDS and neither side of the code has more nodes than
+// kRelayWaveNodes.  Measured on toric codes: form 2 over form 1 is 1.76 x at 72 columns, 1.12 x at
+// 288, 0.90 x at 512, 0.99 x at 800, and 0.40 x on h.txt (1152 x 1024); the rule sits halfway between the last size at which
+// form 2 won and the first at which it lost
+static constexpr int kRelayWaveNodes = 384;
+
+int Engine::relay_form()
+{
+    if (relay_decode_lds_bytes(kRelayFormWave) < 0)
+        return kRelayFormGroup;
+    return plan_.nc <= kRelayWaveNodes && plan_.mc <= kRelayWaveNodes ? kRelayFormWave : kRelayFormGroup;
+}
+
+int64_t Engine::relay_decode_lds_bytes(int form)
+{
+    if (form < 0 || form > kRelayFormWave || syndrome_decode_lds_bytes() < 0) // (the codes of syndrome_decode_batch)
+        return -1;
+    const size_t bytes =
+        ldpc_amd::relay_decode_lds_bytes(qms_plan().slots, static_cast<size_t>(plan_.nc), static_cast<size_t>(plan_.mc));
+    if (form == 0)
+        return bytes <= kCuLdsBytes ? static_cast<int64_t>(bytes) : -1; // (one of the two forms takes it)
+    return bytes * (form == kRelayFormWave ? kRelayWaveFrames : 1) <= kCuLdsBytes ? static_cast<int64_t>(bytes) : -1;
+}
+
+std::string Engine::relay_decode_refusal(const RelayDecodeSpec *spec, int llr_type, int syndrome_format)
+{
+    const char *entry = "ldpc_hip_relay_decode_batch";
+    const std::string who = std::string(entry) + ": ";
+    if (!spec)
+        return who + "null parameters";
+    if (spec->legs < 1 || spec->legs > 256)
+        return who + "legs " + std::to_string(spec->legs) + " is outside 1..256";
+    if (spec->first_iterations < 1 || spec->first_iterations > 0xFFFFu)
+        return who + "first_iterations " + std::to_string(spec->first_iterations) + " is outside 1..65535";
+    if (spec->leg_iterations < 1 || spec->leg_iterations > 0xFFFFu)
+        return who + "leg_iterations " + std::to_string(spec->leg_iterations) + " is outside 1..65535";
+    if (spec->stop_after < 1 || spec->stop_after > spec->legs)
+        return who + "stop_after " + std::to_string(spec->stop_after) + " is outside 1..legs";
+    if (spec->q_bits < 2 || spec->q_bits > 8)
+        return who + "q_bits " + std::to_string(spec->q_bits) + " is outside 2..8";
+    if (!(spec->step > 0.0) || spec->step < 0x1p-20 || spec->step > 0x1p20) // (a NaN fails the first)
+        return who + "the step must lie in [2^-20, 2^20]";
+    if (!(spec->scale > 0.0) || spec->scale > 1.0)
+        return who + "the scale must lie in (0, 1]";
+    if (!(spec->offset >= 0.0) || spec->offset > 1e6)
+        return who + "the offset must lie in [0, 1e6]";
+    if (spec->form < 0 || spec->form > kRelayFormWave)
+        return who + "form " + std::to_string(spec->form) + " is outside 0..2";
+    if (spec->flags & ~kSyndromeSharedLlr)
+        return who + "unknown flag bits " + std::to_string(spec->flags & ~kSyndromeSharedLlr);
+    if (llr_type_bytes(llr_type) == 0)
+        return who + "unknown LLR type " + std::to_string(llr_type) + " (0 = binary64, 1 = binary32, 2 = binary16, 3 = int8)";
+    if (std::string why = bits_format_refusal(entry, "syndrome", syndrome_format); !why.empty())
+        return why;
+    if (relay_decode_lds_bytes(0) < 0)
+        return who + "the code of " + std::to_string(plan_.mc) + " x " + std::to_string(plan_.nc) +
+               " is not taken: more than 65 535 columns, a check node with fewer than two entries, or a frame beyond the 160 KB of LDS "
+               "of a CU (ldpc_hip_relay_decode_lds_bytes; there is no other kernel)";
+    if (relay_decode_lds_bytes(spec->form) < 0)
+        return who + "form " + std::to_string(spec->form) + " does not fit the code of " + std::to_string(plan_.mc) + " x " +
+               std::to_string(plan_.nc) + ": four frames exceed the 160 KB of LDS of a CU (ldpc_hip_relay_decode_lds_bytes)";
+    return "";
+}
+
+void Engine::relay_decode_batch(const RelayDecodeSpec *spec, uint64_t n, const void *llr, int llr_type, const void *syndrome,
+                                int syndrome_format, const int8_t *gamma, uint32_t *hard_bits, uint32_t *iters, uint32_t *weight,
+                                uint32_t *solutions, uint32_t *best_leg, uint32_t *cost, void *stream)
+{
+    if (const std::string why = relay_decode_refusal(spec, llr_type, syndrome_format); !why.empty())
+        throw std::runtime_error(why);
+    if (n && !llr)
+        throw std::runtime_error("ldpc_hip_relay_decode_batch: null llr");
+    if (n == 0 || (!hard_bits && !iters && !weight && !solutions && !best_leg && !cost))
+        return;
+    upload_plan();
+    upload_qms_plan();
+    if (!sd_cn_row_)
+        sd_cn_row_ = static_cast<const uint32_t *>(upload_table(plan_.cn_rank_row.data(), plan_.cn_rank_row.size() * 4, "check node order"));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint64_t nc = static_cast<uint64_t>(plan_.nc), mc = static_cast<uint64_t>(plan_.mc), words = (nc + 31) / 32;
+    const bool shared = (spec->flags & kSyndromeSharedLlr) != 0;
+    RelayDecodeArgs a{};
+    a.nc = static_cast<uint32_t>(nc), a.mc = static_cast<uint32_t>(mc), a.words = static_cast<uint32_t>(words);
+    a.syn_words = static_cast<uint32_t>((mc + 31) / 32);
+    a.legs = spec->legs, a.first_iterations = spec->first_iterations, a.leg_iterations = spec->leg_iterations;
+    a.stop_after = spec->stop_after;
+    a.form = spec->form ? spec->form : relay_form();
+    a.llr_type = llr_type, a.syndrome_format = syndrome_format, a.shared_llr = shared ? 1 : 0;
+    {
+        const QmsArgs q = quantizer_args<QmsArgs>(spec->step, spec->q_bits, spec->scale, spec->offset); // (the same host routine)
+        a.qmax = q.qmax, a.inv = q.inv;
+        std::memcpy(a.lut, q.lut, sizeof a.lut);
+    }
+    a.frame_bytes = static_cast<uint32_t>(relay_decode_lds_bytes(a.form));
+    a.col_rank = dev_.col_rank, a.rank_col = dev_.rank_col, a.cn_row = sd_cn_row_;
+    a.gamma = gamma ? static_cast<const int8_t *>(stage_input(gamma, static_cast<size_t>(spec->legs) * nc, stage_relay_gamma_, stream)) : nullptr;
+    const size_t elem = llr_type_bytes(llr_type), in_row = elem * nc, syn_row = bits_row_bytes(syndrome_format, mc);
+    DeviceBuffer &llr_stage = llr_type == kLlrF64 ? stage_in_ : stage_typed_;
+    if (shared) // one row for every frame: staged once
+        a.llr = stage_input(llr, in_row, llr_stage, stream);
+    const uint64_t sub = std::max<uint64_t>(gf2_sub_batch() / elem, 1); // (elements of up to 8 bytes, not bits)
+    for (uint64_t done = 0; done < n; done += sub)
+    {
+        const uint64_t m = std::min(sub, n - done);
+        if (!shared)
+            a.llr = stage_input(static_cast<const char *>(llr) + in_row * done, in_row * m, llr_stage, stream);
+        a.syndrome = syndrome ? stage_input(static_cast<const char *>(syndrome) + syn_row * done, syn_row * m, stage_in_b_, stream) : nullptr;
+        OutStage st;
+        a.hard_bits = st.route(hard_bits ? hard_bits + done * words : nullptr, stage_sd_[0], 4 * m * words);
+        a.iters = st.route(iters ? iters + done : nullptr, stage_sd_[1], 4 * m);
+        a.weight = st.route(weight ? weight + done : nullptr, stage_sd_[2], 4 * m);
+        a.solutions = st.route(solutions ? solutions + done : nullptr, stage_relay_[0], 4 * m);
+        a.best_leg = st.route(best_leg ? best_leg + done : nullptr, stage_relay_[1], 4 * m);
+        a.cost = st.route(cost ? cost + done : nullptr, stage_relay_[2], 4 * m);
+        a.n = m;
+        check(launch_relay_decode(a, dev_qms_, s), "relay_decode_batch");
+        st.flush(s, &pin_out_);
+    }
+}
+
 void Engine::stream_rewind_encoder(uint64_t frames_back, void *stream)
 {
     if (!code_->has_G() || frames_back == 0 || counter_) // (counter-based noise: a codeword depends on its frame index alone)

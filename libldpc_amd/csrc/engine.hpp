@@ -443,6 +443,21 @@ class Engine
     int64_t bit_flip_lds_bytes() const;
     void bit_flip_batch(const BitFlipSpec *spec, uint64_t n, const void *llr, int llr_type, const void *syndrome, int syndrome_format,
                         uint32_t *hard_bits, uint32_t *iters, uint32_t *weight, void *stream);
+    // min-sum with memory, run as a relay of legs, toward a given syndrome (include/ldpc_amd.h, ldpc_hip_relay_decode_batch;
+    // kernels_relay_decode.hip) on the tables of qms_plan().  As above: everything is in the spec.  `form` 0 = relay_form()
+    struct RelayDecodeSpec
+    {
+        uint32_t legs = 0, first_iterations = 0, leg_iterations = 0, stop_after = 0;
+        int q_bits = 0;
+        double step = 0.0, scale = 0.0, offset = 0.0;
+        int form = 0, flags = 0;
+    };
+    std::string relay_decode_refusal(const RelayDecodeSpec *spec, int llr_type, int syndrome_format);
+    int relay_form(); // the form the library chooses for this code: 2 where it fits and the code is small
+    int64_t relay_decode_lds_bytes(int form);
+    void relay_decode_batch(const RelayDecodeSpec *spec, uint64_t n, const void *llr, int llr_type, const void *syndrome, int syndrome_format,
+                            const int8_t *gamma, uint32_t *hard_bits, uint32_t *iters, uint32_t *weight, uint32_t *solutions,
+                            uint32_t *best_leg, uint32_t *cost, void *stream);
 
     // ---- fused channel + decode on the reference's noise stream ----
     // set_channel_param semantics (channel.cpp:37-42): the stream restarts at frame 0.
@@ -657,6 +672,8 @@ class Engine
     const uint32_t *sdl_step_row_ = nullptr;    // (step, lane) -> file row, at the first syndrome_decode_layered_batch
     const uint32_t *bf_row_ptr_ = nullptr, *bf_col_ptr_ = nullptr; // the rows and the columns of H, file order, u16 indices,
     const uint16_t *bf_row_col_ = nullptr, *bf_col_row_ = nullptr; // at the first bit_flip_batch
+    DeviceBuffer stage_relay_[3];               // relay_decode_batch: its three further outputs (the first three: stage_sd_)
+    DeviceBuffer stage_relay_gamma_;            // ... and a host gamma
     uint64_t gf2_sub_batch() const; // frames per launch: staging buffers stay modest, no grid dimension overflows
     // a host input of a batch call on the device (small ones through page-locked memory); a device pointer comes back as it is
     const void *stage_input(const void *src, size_t bytes, DeviceBuffer &stage, void *stream);

@@ -701,6 +701,54 @@ struct BitFlipArgs
 };
 int launch_bit_flip(const BitFlipArgs &a, void *stream);
 
+// ---- min-sum with memory, run as a relay of legs, toward a given syndrome (kernels_relay_decode.hip; include/ldpc_amd.h,
+// ldpc_hip_relay_decode_batch): the iteration of kernels_syndrome_decode.hip on the tables of DevQmsPlan with a memory term
+// per column and leg, the cheapest word that met the syndrome kept.  One body in two forms: a workgroup of 256 threads per
+// frame, or a wave per frame and four frames to a workgroup ----
+// LDS of one frame (include/ldpc_amd.h, ldpc_hip_relay_decode_lds_bytes): the frame of syndrome_decode_lds_bytes and the kept
+// word, a bit per column.  The cost's reduction takes the four partial sums that frame already holds: no byte more
+constexpr size_t relay_decode_lds_bytes(size_t slots, size_t nc, size_t mc)
+{
+    return syndrome_decode_lds_bytes(slots, nc, mc) + syndrome_decode_round16(4 * ((nc + 31) / 32));
+}
+constexpr uint32_t kRelayWaveFrames = 4;          // form 2: frames (waves) of a workgroup
+constexpr uint32_t kRelayNone = 0xFFFFFFFFu;      // best_leg and cost of a frame without a solution
+enum RelayForm : int32_t
+{
+    kRelayFormGroup = 1, // 256 threads share a frame
+    kRelayFormWave = 2   // 64 threads share a frame
+};
+struct RelayDecodeArgs
+{
+    uint32_t nc, mc;
+    uint32_t words, syn_words;  // ceil(nc / 32), ceil(mc / 32)
+    uint32_t legs;              // 1..256
+    uint32_t first_iterations, leg_iterations; // 1..65535
+    uint32_t stop_after;        // 1..legs
+    int32_t form;               // RelayForm
+    int32_t llr_type;           // LlrType: the kernel reads the elements in place
+    int32_t syndrome_format;    // BitsFormat (not read where syndrome is null)
+    int32_t shared_llr;         // llr is one row [nc] for every frame
+    int32_t qmax;               // 2^(q_bits - 1) - 1, 1..127
+    double inv;                 // fl(1 / step)
+    uint32_t lut[32];           // lut[m], m = 0..qmax, four per word (engine.cpp, correction_lut)
+    uint32_t frame_bytes;       // relay_decode_lds_bytes(slots, nc, mc)
+    const uint32_t *col_rank;   // [nc] column -> VN rank (DevPlan)
+    const uint32_t *rank_col;   // [nc] VN rank -> column (DevPlan): gamma is read by rank
+    const uint32_t *cn_row;     // [mc] check node in the tables' order -> row of H in file order (Plan::cn_rank_row)
+    const void *llr;            // [n][nc] (or [nc]) elements of llr_type, column order
+    const void *syndrome;       // [n][mc] bytes or [n][syn_words] words, row order; nullptr = all zero
+    const int8_t *gamma;        // [legs][nc], column order, in 64ths; nullptr = all zero
+    uint32_t *hard_bits;        // [n][words] or nullptr
+    uint32_t *iters;            // [n] or nullptr
+    uint32_t *weight;           // [n] or nullptr
+    uint32_t *solutions;        // [n] or nullptr
+    uint32_t *best_leg;         // [n] or nullptr
+    uint32_t *cost;             // [n] or nullptr
+    uint64_t n;                 // <= 2^20
+};
+int launch_relay_decode(const RelayDecodeArgs &a, const DevQmsPlan &Q, void *stream);
+
 // opt-in non-parity ternary min-sum, bit-sliced over 32 frames per workgroup (kernels_ternary.hip; include/ldpc_amd.h,
 // ldpc_hip_set_min_sum_ternary) on the general plan.  a.ms_* are not read.  With a.llr_out null the planes of A are left out
 // of the group's LDS (plan.hpp, ternary_lds_bytes)
