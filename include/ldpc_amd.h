@@ -1157,8 +1157,12 @@ int ldpc_hip_selftest_division(ldpc_hip_ctx *ctx, uint64_t n, uint64_t seed, uin
    rather than against the same header compiled for the host: out[i] = fn(a[i] [, b[i]]) for the scalar functions
    (fn 0..9: dm_exp, dm_log, dm_boxplus, dm_ratio_div, dm_ratio_rho, dm_ratio_lambda, dm_e_combine, dm_exp_clamped,
    dm_boxplus_exp, dm_boxplus_log of libldpc_amd/csrc/detmath.h), out[i][0..D) = check-node update of the row
-   a[i][0..D) for fn 10..14 (likelihood-ratio form, D = 3, 4, 5, 6, 8) and fn 15, 16 (LLR domain, D = 4, 6).
-   a, b, out are HOST buffers of n (x D) doubles; b may be NULL for one-operand functions. */
+   a[i][0..D) for fn 10..14 (likelihood-ratio form, D = 3, 4, 5, 6, 8), fn 15, 16 (LLR domain, D = 4, 6), fn 17..19 (shared
+   reciprocals, D = 3, 4, 6) and fn 25..27 (LLR domain, D = 3, 5, 16).  fn 20..24 are the fused form's check nodes (dm_cnf2,
+   dm_cnf3, dm_cnf4 with shared reciprocals, dm_cnf3 and dm_cnf4 with every output divided on its own), rows of D + 2:
+   a[i] = {v_0 .. v_{D-1}, flip | leaf << 4, 0} -> out[i] = {messages, leaf_bit, leaf_tot}, a row of NaN where the node
+   reports a product beyond its range.  fn 28: the range predicates of detmath.h on a[i] as a bit mask held in a double.
+   a, b, out are HOST buffers of n (x row width) doubles; b may be NULL for one-operand functions. */
 int ldpc_hip_selftest_math(ldpc_hip_ctx *ctx, int fn, uint64_t n, const double *a, const double *b, double *out);
 
 /* host-only self-tests of the noise stream's chunk-state bookkeeping (libldpc_amd/csrc/mtstates.hpp; no GPU needed): the

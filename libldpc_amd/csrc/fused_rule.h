@@ -11,7 +11,10 @@
 
 #define DM_FUSED_MAX_SLOTS 8191     /* message slots (edges not ending in a leaf): byte offsets fit 16 bits */
 #define DM_FUSED_MAX_VN_BLOCKS 32   /* blocks of <= 64 variable nodes of equal degree >= 2 (eight per wave) */
-#define DM_FUSED_MAX_LEAF_BLOCKS 16 /* blocks of <= 64 check nodes of one class that have a leaf (four per wave) */
+/* calls on check nodes of one class that have a leaf, two per wave: a call takes two full blocks of 64 nodes or one block.
+   (Counting blocks — sixteen — admitted codes with up to sixteen partly filled ones, which the plan builder cannot place:
+   the kernels then ran the plain ratio form while the oracle ran the fused one, LLR-out apart in the last bits.) */
+#define DM_FUSED_MAX_LEAF_CALLS 8
 #define DM_FUSED_MAX_VN_DEGREE 64
 
 /* Canonical input order of one check node (detmath.h, "Fused form", item 1): neighbours of degree >= 3, then those of
@@ -76,11 +79,12 @@ static inline int dm_fused_applies(int rows, int cols, const int *rptr, const in
             return 0;
         ++class_count[dm_fused_class(rptr[i + 1] - rptr[i], flip, leaf)];
     }
+    /* calls with leaves: a class's full blocks go two to a call, an odd one and a partly filled one take a call each */
     blocks = 0;
     for (i = 0; i < DM_FUSED_NUM_CLASS_KEYS; ++i)
         if (i & 8)
-            blocks += (class_count[i] + 63) / 64;
-    return blocks <= DM_FUSED_MAX_LEAF_BLOCKS;
+            blocks += (class_count[i] / 64 + 1) / 2 + (class_count[i] % 64 != 0);
+    return blocks <= DM_FUSED_MAX_LEAF_CALLS;
 }
 
 #endif /* LDPC_AMD_FUSED_RULE_H */

@@ -895,6 +895,18 @@ enum MathFn : int
     kMathCnRatio3s,     // dm_cn3_shared / dm_cn4_shared: the shared-reciprocal forms
     kMathCnRatio4s,
     kMathCnRatio6s,     // dm_cn6_shared: degree 6, two reciprocals
+    // the fused form's check nodes (detmath.h "Fused form"), one row per node: a[i] = {v_0 .. v_{D-1}, flip | leaf << 4, 0},
+    // out[i] = {m_0 .. m_{D-1}, leaf_bit, leaf_tot}; leaf_tot NaN without a leaf, the whole row NaN where the upper word the
+    // node returns reaches DM_FUSED_P_HI
+    kMathCnf2,          // dm_cnf2
+    kMathCnf3,          // dm_cnf3, shared = 1 (early termination)
+    kMathCnf4,          // dm_cnf4, shared = 1
+    kMathCnf3d,         // dm_cnf3, shared = 0 (hand-over form: every output divided on its own)
+    kMathCnf4d,         // dm_cnf4, shared = 0
+    kMathCnLlr3,        // cn_core<3 / 5 / 16, sum-product>
+    kMathCnLlr5,
+    kMathCnLlr16,
+    kMathPredicates,    // the range predicates of detmath.h on a, as a bit mask (selftest.hip: predicate_mask)
     kMathCount
 };
 int math_selftest_width(int fn); // values per element in a / out (0 = unknown function)

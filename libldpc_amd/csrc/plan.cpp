@@ -497,6 +497,8 @@ FusedPlan build_fused_plan(const LdpcCode &code, const Plan &plan)
         !dm_fused_applies(H.rows, H.cols, H.rptr.data(), H.rcol.data(), H.cptr.data()))
         return f;
     const int W = kDecodeWaves;
+    static_assert(DM_FUSED_MAX_LEAF_CALLS == kDecodeWaves * kFusedLeafCalls && DM_FUSED_MAX_VN_BLOCKS == kDecodeWaves * kFusedVnSlots,
+                  "a code the rule admits has a plan: the oracle decides by the rule alone");
     auto cdeg = [&](int c) { return H.cptr[c + 1] - H.cptr[c]; };
 
     // ---- check nodes by class (key order), rows in file order inside a class, blocks of <= 64 ----

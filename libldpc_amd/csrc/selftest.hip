@@ -55,6 +55,79 @@ __device__ void cn_llr_rows(uint64_t i, const double *a, double *out)
         out[i * D + j] = v[j];
 }
 
+// one node of the fused form with its class as literals, as the kernels' cnf_call has them (kernels_fused.hip)
+template <int D, unsigned FLIP, bool LEAF, bool SHARED>
+__device__ __forceinline__ uint32_t cnf_node(double (&v)[D], uint32_t &lb, double &tot)
+{
+    if constexpr (D == 2)
+        return dm_cnf2(v, FLIP);
+    else if constexpr (D == 3)
+        return dm_cnf3(v, FLIP, LEAF, SHARED, &lb, &tot);
+    else
+        return dm_cnf4(v, FLIP, LEAF, SHARED, &lb, &tot);
+}
+
+// rows {v_0 .. v_{D-1}, flip | leaf << 4, 0} -> {m_0 .. m_{D-1}, leaf_bit, leaf_tot} (kernels.hpp, kMathCnf2); the classes are
+// the nineteen fused_rule.h admits: flipped inputs last among the message inputs, the leaf (its rho_ch) last of all
+template <int D, bool SHARED>
+__device__ void cnf_rows(uint64_t i, const double *a, double *out)
+{
+    constexpr int W = D + 2;
+    const double nan = __builtin_nan("");
+    double v[D];
+#pragma unroll
+    for (int j = 0; j < D; ++j)
+        v[j] = a[i * W + j];
+    const unsigned mode = static_cast<unsigned>(a[i * W + D]);
+    uint32_t lb = 0, h = 0xFFFFFFFFu; // an unknown class: the row comes back as NaN
+    double tot = nan;
+#define CNF_CLASS(flip, leaf) \
+    case (flip) | ((leaf) << 4): h = cnf_node<D, flip, leaf, SHARED>(v, lb, tot); break;
+    if constexpr (D == 2)
+        switch (mode)
+        {
+            CNF_CLASS(0u, 0) CNF_CLASS(2u, 0) CNF_CLASS(3u, 0)
+        default: break;
+        }
+    else if constexpr (D == 3)
+        switch (mode)
+        {
+            CNF_CLASS(0u, 0) CNF_CLASS(4u, 0) CNF_CLASS(6u, 0) CNF_CLASS(7u, 0)
+            CNF_CLASS(0u, 1) CNF_CLASS(2u, 1) CNF_CLASS(3u, 1)
+        default: break;
+        }
+    else
+        switch (mode)
+        {
+            CNF_CLASS(0u, 0) CNF_CLASS(8u, 0) CNF_CLASS(12u, 0) CNF_CLASS(14u, 0) CNF_CLASS(15u, 0)
+            CNF_CLASS(0u, 1) CNF_CLASS(4u, 1) CNF_CLASS(6u, 1) CNF_CLASS(7u, 1)
+        default: break;
+        }
+#undef CNF_CLASS
+    const bool over = h >= DM_FUSED_P_HI;
+#pragma unroll
+    for (int j = 0; j < D; ++j)
+        out[i * W + j] = over ? nan : v[j];
+    out[i * W + D] = over ? nan : static_cast<double>(lb);
+    out[i * W + D + 1] = over ? nan : tot;
+}
+
+// the range predicates of detmath.h as a bit mask, in the order tests/test_gpu_math.py lists them
+__device__ double predicate_mask(double x)
+{
+    const uint32_t hi = dm_hi(x);
+    unsigned m = 0;
+    m |= static_cast<unsigned>(dm_ratio_out_of_range(x) != 0) << 0;
+    m |= static_cast<unsigned>(DM_RATIO_ESCAPED(dm_ratio_key(x))) << 1;
+    m |= static_cast<unsigned>(dm_box_escaped(hi, hi) != 0) << 2;
+    m |= static_cast<unsigned>(DM_SHARED_OVERFLOW(hi)) << 3;
+    m |= static_cast<unsigned>(hi >= DM_FUSED_P_HI) << 4;
+    m |= static_cast<unsigned>(DM_HANDOVER_DUE(dm_handover_key(x))) << 5;
+    m |= static_cast<unsigned>(dm_ratio_llr_refused(x) != 0) << 6;
+    m |= static_cast<unsigned>(dm_llr_tiny(__builtin_fabs(x)) != 0) << 7;
+    return static_cast<double>(m);
+}
+
 __global__ __launch_bounds__(256) void math_selftest_kernel(int fn, uint64_t n, const double *a, const double *b, double *out)
 {
     const uint64_t i = blockIdx.x * 256ull + threadIdx.x;
@@ -82,6 +155,15 @@ __global__ __launch_bounds__(256) void math_selftest_kernel(int fn, uint64_t n, 
     case kMathCnRatio3s: cn_shared_rows<3>(i, a, out); break;
     case kMathCnRatio4s: cn_shared_rows<4>(i, a, out); break;
     case kMathCnRatio6s: cn_shared_rows<6>(i, a, out); break;
+    case kMathCnf2: cnf_rows<2, true>(i, a, out); break;
+    case kMathCnf3: cnf_rows<3, true>(i, a, out); break;
+    case kMathCnf4: cnf_rows<4, true>(i, a, out); break;
+    case kMathCnf3d: cnf_rows<3, false>(i, a, out); break;
+    case kMathCnf4d: cnf_rows<4, false>(i, a, out); break;
+    case kMathCnLlr3: cn_llr_rows<3>(i, a, out); break;
+    case kMathCnLlr5: cn_llr_rows<5>(i, a, out); break;
+    case kMathCnLlr16: cn_llr_rows<16>(i, a, out); break;
+    case kMathPredicates: out[i] = predicate_mask(a[i]); break;
     default: break;
     }
 }
@@ -124,11 +206,12 @@ int math_selftest_width(int fn)
 {
     switch (fn)
     {
-    case kMathCnRatio3: case kMathCnRatio3s: return 3;
-    case kMathCnRatio4: case kMathCnLlr4: case kMathCnRatio4s: return 4;
-    case kMathCnRatio5: return 5;
-    case kMathCnRatio6: case kMathCnLlr6: case kMathCnRatio6s: return 6;
+    case kMathCnRatio3: case kMathCnRatio3s: case kMathCnLlr3: return 3;
+    case kMathCnRatio4: case kMathCnLlr4: case kMathCnRatio4s: case kMathCnf2: return 4;
+    case kMathCnRatio5: case kMathCnLlr5: case kMathCnf3: case kMathCnf3d: return 5;
+    case kMathCnRatio6: case kMathCnLlr6: case kMathCnRatio6s: case kMathCnf4: case kMathCnf4d: return 6;
     case kMathCnRatio8: return 8;
+    case kMathCnLlr16: return 16;
     default: return fn >= 0 && fn < kMathCount ? 1 : 0;
     }
 }

@@ -577,7 +577,7 @@ static double ref_jacobian(double x, double y) /* decoder.h:12-15, libm */
     return (double)(sx * sy) * mn + log((1 + exp(-fabs(x + y))) / (1 + exp(-fabs(x - y))));
 }
 
-static void ref_cn_ratio_ld(int cw, const double *v, double *out) /* rho in, lambda out; divided at every step */
+static void ref_cn_ratio_ldx(int cw, const double *v, long double *out) /* rho in, lambda out; divided at every step */
 {
     long double F[16], B[16];
     F[0] = v[0], B[cw - 1] = v[cw - 1];
@@ -586,10 +586,46 @@ static void ref_cn_ratio_ld(int cw, const double *v, double *out) /* rho in, lam
         F[j] = (1.0L + F[j - 1] * (long double)v[j]) / (F[j - 1] + (long double)v[j]);
         B[cw - 1 - j] = (1.0L + B[cw - j] * (long double)v[cw - 1 - j]) / (B[cw - j] + (long double)v[cw - 1 - j]);
     }
-    out[0] = (double)(1.0L / B[1]);
-    out[cw - 1] = (double)(1.0L / F[cw - 2]);
+    out[0] = 1.0L / B[1];
+    out[cw - 1] = 1.0L / F[cw - 2];
     for (int j = 1; j < cw - 1; ++j)
-        out[j] = (double)((F[j - 1] + B[j + 1]) / (1.0L + F[j - 1] * B[j + 1]));
+        out[j] = (F[j - 1] + B[j + 1]) / (1.0L + F[j - 1] * B[j + 1]);
+}
+
+static void ref_cn_ratio_ld(int cw, const double *v, double *out)
+{
+    long double lam[16];
+    ref_cn_ratio_ldx(cw, v, lam);
+    for (int j = 0; j < cw; ++j)
+        out[j] = (double)lam[j];
+}
+
+/*
+ * A check node of the fused form (kernels.hpp, kMathCnf2: row {v_0 .. v_{D-1}, flip | leaf << 4, 0} -> {m_0 .. m_{D-1},
+ * leaf_bit, leaf_tot}) as what it MEANS: the recursion above over all D inputs, a leaf's channel ratio among them as the
+ * last; message k is lambda_k, or rho_k = 1 / lambda_k where bit k of flip is set; the leaf keeps its entry, its total is
+ * lambda_leaf / rho_ch and its decision (out <= 0 decides 1, a zero total included) lambda_leaf >= rho_ch, both taken in
+ * long double.  Degree 2 divides once: its unflipped outputs are the binary64 quotient, rounded once like the exact value.
+ */
+static void ref_cnf_ld(int D, const double *row, double *out)
+{
+    const unsigned mode = (unsigned)row[D], flip = mode & 15u;
+    const int leaf = (int)(mode >> 4) & 1;
+    long double lam[4];
+    ref_cn_ratio_ldx(D, row, lam);
+    for (int k = 0; k < D - leaf; ++k)
+        if (flip >> k & 1u)
+            out[k] = (double)(1.0L / lam[k]);
+        else
+            out[k] = D == 2 ? 1.0 / row[1 - k] : (double)lam[k];
+    out[D] = 0.0, out[D + 1] = NAN;
+    if (leaf)
+    {
+        const long double rho_ch = row[D - 1];
+        out[D - 1] = row[D - 1];
+        out[D] = (double)(lam[D - 1] >= rho_ch);
+        out[D + 1] = (double)(lam[D - 1] / rho_ch);
+    }
 }
 
 static void ref_cn_llr(int cw, const double *v, double *out) /* decoder.cpp:31-44 with the libm jacobian */
@@ -608,14 +644,18 @@ static void ref_cn_llr(int cw, const double *v, double *out) /* decoder.cpp:31-4
 
 static int math_width(int fn)
 {
-    static const int w[] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 3, 4, 5, 6, 8, 4, 6, 3, 4, 6};
+    static const int w[] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 3, 4, 5, 6, 8, 4, 6, 3, 4, 6,
+                            4, 5, 6, 5, 6, /* cnf2, cnf3, cnf4, cnf3d, cnf4d: degree + 2 */
+                            3, 5, 16,      /* cn_llr3, cn_llr5, cn_llr16 */
+                            1};            /* predicates */
     return fn >= 0 && fn < (int)(sizeof w / sizeof w[0]) ? w[fn] : 0;
 }
+enum { FN_CNF2 = 20, FN_CNF3, FN_CNF4, FN_CNF3D, FN_CNF4D, FN_CN_LLR3, FN_CN_LLR5, FN_CN_LLR16, FN_PREDICATES };
 
 int orc_math_ref(int fn, uint64_t n, const double *a, const double *b, double *out)
 {
     const int w = math_width(fn);
-    if (!w)
+    if (!w || fn == FN_PREDICATES) /* (the predicates' reference is a handful of comparisons, written out in the test) */
         return -1;
     for (uint64_t i = 0; i < n; ++i)
     {
@@ -632,7 +672,8 @@ int orc_math_ref(int fn, uint64_t n, const double *a, const double *b, double *o
         case 7: out[i] = exp(fmin(fmax(a[i], -700.0), 700.0)); break;
         case 8: out[i] = exp(-fmin(a[i], 700.0)); break;
         case 9: out[i] = log(a[i]); break;
-        case 15: case 16: ref_cn_llr(w, a + i * w, out + i * w); break;
+        case 15: case 16: case FN_CN_LLR3: case FN_CN_LLR5: case FN_CN_LLR16: ref_cn_llr(w, a + i * w, out + i * w); break;
+        case FN_CNF2: case FN_CNF3: case FN_CNF4: case FN_CNF3D: case FN_CNF4D: ref_cnf_ld(w - 2, a + i * w, out + i * w); break;
         default: ref_cn_ratio_ld(w, a + i * w, out + i * w); break;
         }
     }
@@ -667,6 +708,42 @@ static void det_cn_shared(int cw, const double *v, double *out) /* rows whose de
         out[j] = (over || e6) ? NAN : c2v[j];
 }
 
+static void det_cnf(int D, int shared, const double *row, double *out) /* dm_cnf2/3/4 on one row; overflow flagged: NaN */
+{
+    const unsigned mode = (unsigned)row[D], flip = mode & 15u;
+    const int leaf = (int)(mode >> 4) & 1;
+    double v[4], tot = NAN;
+    uint32_t lb = 0, h;
+    for (int j = 0; j < D; ++j)
+        v[j] = row[j];
+    if (D == 2)
+        h = dm_cnf2(v, flip);
+    else if (D == 3)
+        h = dm_cnf3(v, flip, leaf, shared, &lb, &tot);
+    else
+        h = dm_cnf4(v, flip, leaf, shared, &lb, &tot);
+    const int over = h >= DM_FUSED_P_HI;
+    for (int j = 0; j < D; ++j)
+        out[j] = over ? NAN : v[j];
+    out[D] = over ? NAN : (double)lb;
+    out[D + 1] = over ? NAN : tot;
+}
+
+static double det_predicates(double x) /* the range predicates as a bit mask, in the order of tests/test_gpu_math.py */
+{
+    const uint32_t hi = dm_hi(x);
+    unsigned m = 0;
+    m |= (unsigned)(dm_ratio_out_of_range(x) != 0) << 0;
+    m |= (unsigned)(DM_RATIO_ESCAPED(dm_ratio_key(x)) != 0) << 1;
+    m |= (unsigned)(dm_box_escaped(hi, hi) != 0) << 2;
+    m |= (unsigned)(DM_SHARED_OVERFLOW(hi) != 0) << 3;
+    m |= (unsigned)(hi >= DM_FUSED_P_HI) << 4;
+    m |= (unsigned)(DM_HANDOVER_DUE(dm_handover_key(x)) != 0) << 5;
+    m |= (unsigned)(dm_ratio_llr_refused(x) != 0) << 6;
+    m |= (unsigned)(dm_llr_tiny(fabs(x)) != 0) << 7;
+    return (double)m;
+}
+
 int orc_math_det(int fn, uint64_t n, const double *a, const double *b, double *out)
 {
     const int w = math_width(fn);
@@ -675,6 +752,9 @@ int orc_math_det(int fn, uint64_t n, const double *a, const double *b, double *o
     for (uint64_t i = 0; i < n; ++i)
         switch (fn)
         {
+        case FN_CNF2: case FN_CNF3: case FN_CNF4: det_cnf(w - 2, 1, a + i * w, out + i * w); break;
+        case FN_CNF3D: case FN_CNF4D: det_cnf(w - 2, 0, a + i * w, out + i * w); break;
+        case FN_PREDICATES: out[i] = det_predicates(a[i]); break;
         case 0: out[i] = dm_exp(a[i]); break;
         case 1: out[i] = dm_log(a[i]); break;
         case 2: out[i] = dm_boxplus(a[i], b[i]); break;
@@ -685,7 +765,7 @@ int orc_math_det(int fn, uint64_t n, const double *a, const double *b, double *o
         case 7: out[i] = dm_exp_clamped(a[i]); break;
         case 8: out[i] = dm_boxplus_exp(a[i]); break;
         case 9: out[i] = dm_boxplus_log(a[i]); break;
-        case 15: case 16:
+        case 15: case 16: case FN_CN_LLR3: case FN_CN_LLR5: case FN_CN_LLR16:
         {
             dec_t d;
             double v2c[16], c2v[16], F[16], B[16];
@@ -852,6 +932,7 @@ static int fused_applies(const orc_code *c)
     const spm *H = &c->H;
     return handover_applies(c) && dm_fused_applies(H->rows, H->cols, H->rptr, H->rnode, H->cptr);
 }
+int orc_code_fused(const orc_code *c) { return fused_applies(c); }
 
 /* one check-node pass of the fused form; handover: the pass that ends the ratio form (every output as lambda, separately
    divided, leaf included) and leaves c2v[] as LLRs for the LLR-domain form to continue with */

@@ -77,6 +77,8 @@ int orc_decode_bec(const orc_code *c, int early_term, unsigned iterations, int d
 /* ORC_MATH_DET, sum-product with early termination: frames finished by the likelihood-ratio form / handed back
    to the LLR-domain form since the last reset (test introspection; single-threaded use only) */
 void orc_ratio_stats(uint64_t *done, uint64_t *escaped, int reset);
+/* whether ORC_MATH_DET takes the fused form on this code (libldpc_amd/csrc/fused_rule.h): must equal the kernels' plan */
+int orc_code_fused(const orc_code *c);
 
 /* ---- channel + decoder object: channel.cpp (one per reference OpenMP thread) ---- */
 orc_chan *orc_chan_new(const orc_code *c, int chan_type, uint64_t seed, int math_mode,

@@ -4,6 +4,7 @@ Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import this
 """
 import ctypes as ct
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -40,7 +41,7 @@ def lib():
     L.orc_code_load.argtypes = [ct.c_char_p, ct.c_char_p]
     L.orc_code_free.argtypes = [vp]
     for name in ("nc", "mc", "kc", "nnz", "nct", "mct", "kct", "max_degree", "num_puncture",
-                 "num_shorten", "has_G", "g_rows", "g_cols", "g_nnz"):
+                 "num_shorten", "has_G", "g_rows", "g_cols", "g_nnz", "fused"):
         f = getattr(L, "orc_code_" + name)
         f.restype, f.argtypes = i32, [vp]
     L.orc_code_edges.argtypes = [vp, vp, vp]
@@ -91,7 +92,7 @@ class Code:
         if not self.h:
             raise OSError("oracle: cannot open " + pc_file)
         for name in ("nc", "mc", "kc", "nnz", "nct", "mct", "kct", "max_degree", "num_puncture",
-                     "num_shorten", "has_G", "g_rows", "g_cols", "g_nnz"):
+                     "num_shorten", "has_G", "g_rows", "g_cols", "g_nnz", "fused"):
             setattr(self, name, getattr(L, "orc_code_" + name)(self.h))
         self.edge_row = np.zeros(self.nnz, np.int32)
         self.edge_col = np.zeros(self.nnz, np.int32)
@@ -279,7 +280,19 @@ def ref_dump(h, g, chan, dec, iters, early, seed, x, skip, count, tmp):
 
 
 MATH_FNS = ("exp", "log", "boxplus", "ratio_div", "ratio_rho", "ratio_lambda", "e_combine", "exp_clamped", "boxplus_exp",
-            "boxplus_log", "cn_ratio3", "cn_ratio4", "cn_ratio5", "cn_ratio6", "cn_ratio8", "cn_llr4", "cn_llr6", "cn_ratio3s", "cn_ratio4s", "cn_ratio6s")
+            "boxplus_log", "cn_ratio3", "cn_ratio4", "cn_ratio5", "cn_ratio6", "cn_ratio8", "cn_llr4", "cn_llr6", "cn_ratio3s", "cn_ratio4s", "cn_ratio6s",
+            "cnf2", "cnf3", "cnf4", "cnf3d", "cnf4d", "cn_llr3", "cn_llr5", "cn_llr16", "predicates")
+
+# The check nodes of the fused form (detmath.h dm_cnf2 / dm_cnf3 / dm_cnf4): rows [v_0 .. v_{D-1}, flip | leaf << 4, 0] in,
+# [m_0 .. m_{D-1}, leaf_bit, leaf_tot] out.  The classes (flip, leaf) are those fused_rule.h admits: the flipped inputs are
+# the last among the message inputs, a leaf (entry = its rho_ch) is the last input.  cnf3 / cnf4: shared reciprocals, as under
+# early termination; cnf3d / cnf4d: every output divided on its own, the hand-over form.
+CNF_DEGREE = {"cnf2": 2, "cnf3": 3, "cnf4": 4, "cnf3d": 3, "cnf4d": 4}
+CNF_CLASSES = {2: ((0, 0), (2, 0), (3, 0)),
+               3: ((0, 0), (4, 0), (6, 0), (7, 0), (0, 1), (2, 1), (3, 1)),
+               4: ((0, 0), (8, 0), (12, 0), (14, 0), (15, 0), (0, 1), (4, 1), (6, 1), (7, 1))}
+CNF_SHARED_LIMIT = {"cnf3": 100.0, "cnf4": 50.0}  # |L| of the inputs up to which every product inverted stays below 2^897
+CNF_TIE_ROWS, CNF_OVERFLOW_L = 8, 160.0
 
 
 def math_eval(fn, a, b=None, det=False):
@@ -353,7 +366,33 @@ def math_points(fn, n, seed):
         L = np.concatenate([rng.uniform(-lim, lim, (n // 2, d)), rng.normal(0, 6, (n - n // 2 - 2, d)).clip(-lim, lim),
                             np.full((1, d), lim), np.full((1, d), -lim)])
         return np.exp(L), None
-    d = int(fn[-1])
+    if fn in CNF_DEGREE:
+        # n rows PER CLASS: half uniform over the form's range, half normal(0, 6), the two corner rows; on a leaf class rho_ch
+        # is drawn like the other inputs and the last CNF_TIE_ROWS rows are exact ties of the leaf's decision (v_0 = 1 and
+        # rho_ch = 1: lambda(c2v to the leaf) is 1 whatever the other inputs are); on the shared forms four more rows have
+        # every |L| = 160, where the products of denominators the classes invert leave the double range (all +160) or do not
+        d = CNF_DEGREE[fn]
+        lim = CNF_SHARED_LIMIT.get(fn, 240 * np.log(2.0) * (1 - 1e-12))
+        rows = []
+        for flip, leaf in CNF_CLASSES[d]:
+            extra = [np.full((1, d), lim), np.full((1, d), -lim)]
+            if fn in CNF_SHARED_LIMIT:
+                extra += [np.full((2, d), CNF_OVERFLOW_L), np.full((2, d), -CNF_OVERFLOW_L)]
+            if leaf:
+                tie = rng.uniform(-lim, lim, (CNF_TIE_ROWS, d))
+                tie[:, 0] = tie[:, d - 1] = 0.0
+                extra.append(tie)
+            m = n - sum(len(e) for e in extra)
+            L = np.concatenate([rng.uniform(-lim, lim, (m // 2, d)), rng.normal(0, 6, (m - m // 2, d)).clip(-lim, lim)] + extra)
+            rows.append(np.concatenate([np.exp(L), np.full((n, 1), float(flip | leaf << 4)), np.zeros((n, 1))], axis=1))
+        return np.concatenate(rows), None
+    if fn == "predicates":
+        # every threshold of detmath.h's range predicates with its two neighbours, the special values, all of them negated too
+        thr = np.array([2.0**240, 2.0**-240, 2.0**220, 2.0**-220, 2.0**897, 166.0, 2.0**-52])
+        x = np.concatenate([thr, np.nextafter(thr, 0.0), np.nextafter(thr, np.inf),
+                            [0.0, 5e-324, np.finfo(np.float64).tiny, np.finfo(np.float64).max, np.inf, np.nan, 1.0, 2.5, 1e-3, 200.0]])
+        return np.concatenate([x, -x]), None
+    d = int(re.search(r"\d+$", fn).group())
     if fn.startswith("cn_ratio"):
         lim = 240 * np.log(2.0) * (1 - 1e-12)
         L = np.concatenate([rng.uniform(-lim, lim, (n // 2, d)), rng.normal(0, 6, (n - n // 2 - 2, d)),
@@ -370,4 +409,7 @@ def math_points(fn, n, seed):
     L[q:q + e] = (rng.uniform(39.5, 40.5, (e, 1)) + rng.exponential(30, (e, d))) * rng.choice([-1, 1], (e, d))
     L[q + e:q + 2 * e] = (rng.uniform(50, 1e4, (e, 1)) + rng.uniform(0, 1, (e, d)) * rng.uniform(590, 610, (e, 1))) * rng.choice([-1, 1], (e, d))
     L[q + 2 * e:q + 3 * e] = rng.uniform(-2000, 2000, (e, d))
+    # an input with 0 < |v| < 2^-52 (detmath.h dm_llr_tiny: e^-|v| rounds to 1, the node takes the direct box-plus)
+    t = min(16, n // 8)
+    L[n - 2 - t:n - 2][np.arange(t), rng.integers(0, d, t)] = np.ldexp(rng.uniform(0.5, 1, t), rng.integers(-1073, -52, t)) * rng.choice([-1, 1], t)
     return L, None

@@ -37,6 +37,9 @@ CASES = [
     # name, nc, mc, CN degree pool, puncture, shorten, skipped columns, expected residency
     ("lds_small_irregular", 300, 150, [2, 3, 4], (5, 6, 7), (), (), "lds"),
     ("lds_wide_cn", 600, 200, [5, 6, 7, 8], (), (10, 11), (3,), "lds"),
+    # the same shape with the two columns punctured instead: a shortened column's LLR is refused by the ratio form at admission
+    # (every frame of lds_wide_cn is decoded again in the LLR domain); here frames finish in the ratio form (KEPT_IN_RATIO_FORM)
+    ("lds_wide_cn_kept", 600, 200, [5, 6, 7, 8], (10, 11), (), (3,), "lds"),
     ("mem_cn12", 900, 100, [9, 12, 16], (), (), (), "memory"),
     ("reg_tile_8x4", 9000, 6000, [3, 4], (1, 2, 3), (), (7,), "registers"),
     ("reg_tile_2x8", 3000, 2000, [8], (), (), (), "registers"),
@@ -47,6 +50,9 @@ CASES = [
     # a code whose erasure-decoder state (nnz + 2 nc bytes) exceeds 160 KB of LDS: BEC state in device memory
     ("bec_beyond_lds", 70000, 35000, [4], (), (), (), None),
 ]
+# codes on which a value of the ratio form's own (not only the fact that a frame left it) reaches the outputs: the oracle
+# must report frames finished in that form (orc.ratio_stats) at an AWGN point with early termination
+KEPT_IN_RATIO_FORM = ("lds_wide_cn_kept",)
 
 
 def make_code_by_degrees(path, vn_degs, cn_degs, rng):
@@ -132,6 +138,7 @@ def test_random_code_bit_exact(case, tmp_path):
     if residency:
         assert d.residency == residency, d.residency
     # channel points chosen so that some frames converge and some do not
+    kept = 0  # frames the oracle finished in the ratio form, over the sum-product AWGN points with early termination
     for ch, x, ms, early, iters in (("AWGN", 3.0, False, True, 20), ("AWGN", 1.0, True, True, 15),
                                     ("AWGN", 2.0, False, False, 4), ("AWGN", 9.0, False, True, 20),
                                     ("AWGN", 13.0, False, True, 20), ("BSC", 0.03, False, True, 20),
@@ -142,10 +149,13 @@ def test_random_code_bit_exact(case, tmp_path):
         d.stream_begin(ch, 3, x)
         d.stream_skip(1)
         r = d.stream_decode(5, early_term=early, iterations=iters, decoding="BP_MS" if ms else "BP", want=OUT)
+        orc.ratio_stats(reset=True)
         o = code.run_frames(ch, x, seed=3, skip=1, count=5, min_sum=ms, early_term=early, iters=iters,
                             math=orc.MATH_DET, bec_compat=False)
+        kept += orc.ratio_stats()[0] if (ch, ms, early) == ("AWGN", False, True) else 0
         for k in OUT:
             assert np.array_equal(r[k], o[k].astype(r[k].dtype)), (name, ch, x, k)
+    assert kept > 0 or name not in KEPT_IN_RATIO_FORM, name
 
 
 def test_edge_case_batches():
@@ -219,7 +229,64 @@ FUSED_CASES = [
     # block of degree 20 (slot table: wider than the register-held offsets) and blocks of degree 3 and 5 beside a wide one
     ("fused_general", [(2, 0, 60), (3, 0, 300), (3, 1, 120), (4, 0, 200), (4, 1, 160)],
      [2] * 600 + [3] * 200 + [5] * 60 + [20] * 10 + [12] * 10 + [6] * 20, (0, 1, 900), (5,)),
+    # the general instantiation on a code whose frames FINISH in the fused form: fused_general's shortened column is refused at
+    # admission and its twenty wide variable nodes push every frame out of the box, so all of its results come from the redo
+    # path.  No shortening and two wide nodes here; the check-node classes (4, 0, 0) and (4, 0, 4) — dm_cnf4 with nothing and
+    # with everything flipped, shared reciprocals — occur in no other test code
+    ("fused_general_finishes", [(2, 0, 60), (3, 0, 300), (3, 1, 120), (4, 0, 200), (4, 1, 160)],
+     [2] * 600 + [3] * 200 + [5] * 60 + [20] * 2 + [4] * 70 + [6] * 20, (0, 1, 900), ()),
 ]
+# fused_general_finishes' degrees on another graph (the name seeds it): 68 check nodes of class (3, 1, 1) and 70 of (4, 1, 1),
+# a full and a partly filled block each, make nine calls with leaves where four waves take two each.  The rule that admits a
+# code (fused_rule.h) once counted blocks, admitted this one, and the oracle ran the fused form while the kernels, whose plan
+# builder cannot place nine calls, ran the plain ratio form: LLR-out 3e-14 apart.  Neither side takes it now.
+FUSED_NINE_LEAF_CALLS = ("fused_general_kept",) + FUSED_CASES[-1][1:]
+# channel, point, min-sum, early termination, iterations, frames (stream seed 4, two frames skipped)
+FUSED_POINTS = (("AWGN", 2.0, False, True, 25, 6), ("AWGN", 6.0, False, True, 25, 6), ("AWGN", 14.0, False, True, 20, 6),
+                ("AWGN", 3.0, False, False, 30, 6), ("AWGN", 8.0, False, False, 45, 6), ("AWGN", 2.0, True, False, 20, 6),
+                ("AWGN", 1.0, True, True, 15, 6), ("BSC", 0.04, False, True, 25, 6))
+# below the waterfall: frames take many iterations and stay inside the box of the ratio form
+FUSED_LOW_POINTS = (("AWGN", 0.0, False, True, 30, 8), ("AWGN", 1.0, False, True, 30, 8))
+
+
+def fused_code(case, directory):
+    name, cn_spec, vn_degs, punct, short = case
+    rng = np.random.default_rng(zlib.crc32(name.encode()))
+    return make_fused_code(str(directory / f"{name}.txt"), rng, cn_spec, vn_degs, punct, short)
+
+
+def fused_oracle_run(code, point, math, counts=None):
+    """One point on the oracle; counts[point] = (frames finished in a ratio form, frames that went on to the LLR domain, frames
+    whose first attempt — the fused form — was given up) as the det-mode oracle counts them."""
+    ch, x, ms, early, iters, n = point
+    orc.ratio_stats(reset=True)
+    o = code.run_frames(ch, x, seed=4, skip=2, count=n, min_sum=ms, early_term=early, iters=iters, math=math)
+    if counts is not None:
+        counts[point] = orc.ratio_stats() + (orc.ratio_second(),)
+    return o
+
+
+def check_fused_counts(name, code, plan, counts):
+    """Which results of the fused form the points keep (sum-product with early termination; n = frames of the point):
+    fused_general keeps none — has_shortened: its shortened column's LLR is refused at admission, every frame is decoded again
+    from scratch and what the test sees of the fused form there is only that the frame left it; every other code finishes
+    frames in a ratio form, and on fused_general_finishes — the general instantiation, slot table, two leaf calls per wave,
+    classes (4, 0, 0) and (4, 0, 4) — there is a point where the fused form finishes every frame and one where it finishes
+    some and gives others up."""
+    et = {p: c for p, c in counts.items() if not p[2] and p[3]}
+    assert len(et) >= 4
+    if name == "fused_general":
+        assert plan["has_shortened"] == 1 and all(done == 0 for done, _, _ in et.values()), et
+        return
+    assert any(done > 0 for done, _, _ in et.values()), et
+    if name == "fused_general_finishes":
+        assert plan["small"] == 0 and plan["vnb"] > 4 and plan["cnl"] == 2 and plan["table_entries"] > 1, plan
+        deg = np.bincount(code.edge_col, minlength=code.nc)
+        classes = {(len(c), int((deg[c] == 1).sum()), int((deg[c] == 2).sum()))
+                   for c in (code.edge_col[code.edge_row == r] for r in range(code.mc))}
+        assert {(4, 0, 0), (4, 0, 4)} <= classes, classes
+        assert any(second == 0 and done == p[5] for p, (done, _, second) in et.items()), et
+        assert any(0 < p[5] - second < p[5] for p, (_, _, second) in et.items()), et
 
 
 @pytest.mark.parametrize("case", FUSED_CASES, ids=[c[0] for c in FUSED_CASES])
@@ -228,27 +295,49 @@ def test_fused_form_on_random_codes(case, tmp_path):
     and without the LLR output), the slot-table path, degree-2 check nodes, partly filled blocks, leaves and degree-2
     neighbours anywhere in a row's file order, punctured and shortened columns — sum-product with early termination (three
     launches: frames escape at high SNR), without (hand-over), min-sum without early termination, BSC; bit for bit against
-    the det-mode oracle, which must have taken the fused form too (fused_rule.h is shared; the plan reports it)."""
+    the det-mode oracle, which must have taken the fused form too (fused_rule.h is shared; the plan reports it).  The oracle
+    counts how many frames each point finishes in the fused form: check_fused_counts says what must be kept, and why
+    fused_general keeps nothing."""
     import libldpc_amd
-    name, cn_spec, vn_degs, punct, short = case
-    rng = np.random.default_rng(zlib.crc32(name.encode()))
-    path = make_fused_code(str(tmp_path / f"{name}.txt"), rng, cn_spec, vn_degs, punct, short)
+    name = case[0]
+    path = fused_code(case, tmp_path)
     code = orc.Code(path)
     d = libldpc_amd.HipDecoder(path)
     assert (d.nc, d.mc, d.nnz) == (code.nc, code.mc, code.nnz) and d.residency == "lds"
     assert d.fused_plan()["ok"] == 1, d.fused_plan()
     if name == "fused_general":
         assert d.fused_plan()["vnb"] > 4 and d.fused_plan()["cnl"] == 2, d.fused_plan()
-    for ch, x, ms, early, iters in (("AWGN", 2.0, False, True, 25), ("AWGN", 6.0, False, True, 25), ("AWGN", 14.0, False, True, 20),
-                                    ("AWGN", 3.0, False, False, 30), ("AWGN", 8.0, False, False, 45), ("AWGN", 2.0, True, False, 20),
-                                    ("AWGN", 1.0, True, True, 15), ("BSC", 0.04, False, True, 25)):
-        o = code.run_frames(ch, x, seed=4, skip=2, count=6, min_sum=ms, early_term=early, iters=iters, math=orc.MATH_DET)
+    counts = {}
+    for point in FUSED_POINTS + (FUSED_LOW_POINTS if name == "fused_general_finishes" else ()):
+        ch, x, ms, early, iters, n = point
+        o = fused_oracle_run(code, point, orc.MATH_DET, counts)
         for want in (OUT, ("iters", "bit_errors", "hard")):
             d.stream_begin(ch, 4, x)
             d.stream_skip(2)
-            r = d.stream_decode(6, early_term=early, iterations=iters, decoding="BP_MS" if ms else "BP", want=want)
+            r = d.stream_decode(n, early_term=early, iterations=iters, decoding="BP_MS" if ms else "BP", want=want)
             for k in want:
                 assert np.array_equal(r[k], o[k].astype(r[k].dtype)), (name, ch, x, ms, early, k, len(want))
+    check_fused_counts(name, code, d.fused_plan(), counts)
+
+
+def test_code_the_fused_plan_cannot_place(tmp_path):
+    """FUSED_NINE_LEAF_CALLS: the kernels' plan and the oracle's rule agree that the fused form does not take it, and the plain
+    ratio form decodes it bit for bit like the oracle, with frames that finish in that form."""
+    import libldpc_amd
+    path = fused_code(FUSED_NINE_LEAF_CALLS, tmp_path)
+    code = orc.Code(path)
+    d = libldpc_amd.HipDecoder(path)
+    assert d.residency == "lds" and d.fused_plan()["ok"] == 0 and code.fused == 0, (d.fused_plan(), code.fused)
+    counts = {}
+    for point in (FUSED_LOW_POINTS[0], FUSED_POINTS[0], FUSED_POINTS[3]):
+        ch, x, ms, early, iters, n = point
+        o = fused_oracle_run(code, point, orc.MATH_DET, counts)
+        d.stream_begin(ch, 4, x)
+        d.stream_skip(2)
+        r = d.stream_decode(n, early_term=early, iterations=iters, decoding="BP", want=OUT)
+        for k in OUT:
+            assert np.array_equal(r[k], o[k].astype(r[k].dtype)), (point, k)
+    assert counts[FUSED_LOW_POINTS[0]][0] > 0, counts
 
 
 @pytest.mark.parametrize("name,vn,cn,residency,form", [

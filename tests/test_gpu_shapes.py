@@ -14,10 +14,13 @@ import numpy as np
 import pytest
 
 import orc
-from test_gpu_random_codes import CASES, make_code, make_code_by_degrees
+from test_gpu_random_codes import (CASES, FUSED_CASES, FUSED_LOW_POINTS, FUSED_POINTS, fused_code, fused_oracle_run, make_code,
+                                   make_code_by_degrees)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5  # north_star: LLRs within 1e-5
+# the points at which the fused codes are held to the reference's arithmetic (sum-product only: min-sum has no transcendental)
+FUSED_REFERENCE_POINTS = tuple(p for p in FUSED_POINTS if not p[2]) + FUSED_LOW_POINTS
 
 
 def assert_reference_parity(code, got, ref, early, iters, what):
@@ -93,6 +96,29 @@ def test_random_code_vs_reference_arithmetic(case, tmp_path):
         got = d.stream_decode(5, early_term=early, iterations=iters, decoding="BP", want=("iters", "bit_errors", "hard", "llr_out"))
         ref = code.run_frames(ch, x, seed=3, skip=1, count=5, early_term=early, iters=iters, math=orc.MATH_LIBM)
         n_conv += assert_reference_parity(code, got, ref, early, iters, (name, ch, x))
+    assert n_conv > 0
+
+
+@pytest.mark.parametrize("case", FUSED_CASES, ids=[c[0] for c in FUSED_CASES])
+def test_fused_codes_vs_reference_arithmetic(case, tmp_path):
+    """Every code of test_fused_form_on_random_codes against the libm-mode oracle = the reference's arithmetic: the det-mode
+    oracle those runs are held to calls the same dm_cnf2 / dm_cnf3 / dm_cnf4 as the kernels, so equality with it says nothing
+    about the formulas of the classes h.txt does not contain.  The sum-product points of that test, and two points below
+    the waterfall where frames finish in the fused form (tests/test_fused_forms_host.py asserts, without a GPU, that they do
+    and that det and libm mode agree there)."""
+    import libldpc_amd
+    path = fused_code(case, tmp_path)
+    code = orc.Code(path)
+    d = libldpc_amd.HipDecoder(path)
+    assert d.fused_plan()["ok"] == 1, d.fused_plan()
+    n_conv = 0
+    for point in FUSED_REFERENCE_POINTS:
+        ch, x, _, early, iters, n = point
+        d.stream_begin(ch, 4, x)
+        d.stream_skip(2)
+        got = d.stream_decode(n, early_term=early, iterations=iters, decoding="BP", want=("iters", "bit_errors", "hard", "llr_out"))
+        ref = fused_oracle_run(code, point, orc.MATH_LIBM)
+        n_conv += assert_reference_parity(code, got, ref, early, iters, (case[0],) + point)
     assert n_conv > 0
 
 
